@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the PitRemove -> D8FlowDir -> AreaD8 pipeline (BASELINE.json metric: Mcells/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size n | --nx X --ny Y]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size n | --nx X --ny Y] [--dump-outputs DIR]
 
 One "step" = one pass of the three-stage pipeline over one synthetic fractal DEM that is already
 resident in HBM (generated on the device by tdx_synth_dem_dev).
@@ -26,6 +26,9 @@ and `--workload decay` times configs[4] itself: DinfDecayAccum -wg -o on ONE ras
 (the D-infinity angles come from PitRemove -> DinfFlowDir on the same strips, outside the timed region).
 `--in-process` (N > 1): the N strips are N rank threads of THIS process on the library's own rank group (tdx_group: RCCL when every
 rank has a GPU, peer copies when ranks share one - how eight 65536 x 8192 strips run on one 288 GB GPU); functional check, no torchrun.
+`--dump-outputs DIR`: after the timed steps, what the last timed step returned (fel, p, sd8, ad8; dsca for `--workload decay`) goes to
+DIR/<name>.npy as float32, at most 64 MB in all (a fixed seeded sample of cells beyond that, see dump_outputs), so that two builds can be
+compared output for output: the inputs depend on the arguments alone.
 """
 import argparse
 import json
@@ -92,7 +95,39 @@ def parse():
     ap.add_argument("--segments", type=int, default=0, choices=(0, 1, 2), help="--in-process: segment trace of the timed steps (2: one rank on the device at a "
                     "time) -> projected_ngpu_ms in the line (taudem_amd.distributed.project_critical_path)")
     ap.add_argument("--segments-out", default="", help="--segments: also write every rank's segment list to this JSON file (scripts/project_8gpu.py reads it)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps: the rasters the last timed step returned as DIR/<name>.npy "
+                    "(float32; a fixed seeded sample of cells when they exceed 64 MB together; one set per rank when N > 1)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_CELLS = 1 << 21
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(torch, outdir, arrays, rank=0, world=1):
+    """Writes the rasters of `arrays` (name -> 2-D device tensor, every one of the same shape) as outdir/<name>.npy in float32 (p's int16 codes
+    convert exactly); with world > 1 ranks each rank writes its own strip as outdir/<name>.rank<r>.npy within 1/world of the budget.  When the
+    rasters exceed the budget together, each is reduced to the same DUMP_SAMPLE_CELLS / world cells, drawn by a fixed seed from the raster's shape
+    alone and listed (row-major flat indices, ascending) in outdir/sample_index[.rank<r>].npy as float64."""
+    import numpy as np
+
+    suffix = f".rank{rank}" if world > 1 else ""
+    os.makedirs(outdir, exist_ok=True)
+    shape = tuple(next(iter(arrays.values())).shape)
+    cells = shape[0] * shape[1]
+    idx = None
+    if 4 * cells * len(arrays) > DUMP_MAX_BYTES // world:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(cells, size=min(cells, DUMP_SAMPLE_CELLS // world), replace=False))
+        np.save(os.path.join(outdir, f"sample_index{suffix}.npy"), pick.astype(np.float64))
+        idx = torch.from_numpy(pick).to(next(iter(arrays.values())).device)
+    for name, t in arrays.items():
+        assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        v = t if idx is None else torch.take(t, idx)
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), v.to(torch.float32).cpu().numpy())
 
 
 def self_launch(args):
@@ -330,7 +365,7 @@ def config4_8strips_leg(torch, T, args, rccl_latency_us=None, lone_stage_ms=None
     assumed latencies; scripts/project_8gpu.py)."""
     import copy
     a = copy.copy(args)
-    a.workload, a.warmup, a.steps, a.segments, a.segments_out = "d8", 1, 1, 2, ""
+    a.workload, a.warmup, a.steps, a.segments, a.segments_out, a.dump_outputs = "d8", 1, 1, 2, "", ""
     a.rccl_latency_us = rccl_latency_us
     line = strips_in_process(torch, T, a, 8, 65536, 65536)
     if lone_stage_ms and "projected_ngpu_ms" in line:   # work of the eight strips against eight lone strips (no neighbours): what the exchanges' re-relaxations add
@@ -455,6 +490,10 @@ def strips_in_process(torch, T, args, world, nx, ny):
                     st = step()
                 torch.cuda.synchronize(); bar.wait()
                 res["elapsed"] = time.perf_counter() - t0
+                if args.dump_outputs:
+                    own = slice(1, nyl + 1)
+                    dump_outputs(torch, args.dump_outputs, {"dsca": job.out[own]} if args.workload == "decay" else
+                                 {"fel": fel[own], "p": p[own], "sd8": sd8[own], "ad8": ad8[own]}, r, world)
                 if args.segments:   # the group's own transport: one exchange / one vote as the protocol issues them, all ranks at once
                     import ctypes as C
                     lat = (C.c_double * 2)()
@@ -598,6 +637,8 @@ def main():
             st = job.step()
         sync()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(torch, args.dump_outputs, {"dsca": job.out[1:job.nyl + 1]}, rank, world)
         evaluated, outlets = job.evaluated_cells(torch), len(job.outlets[0])
         if dist.is_initialized():
             t = torch.tensor([elapsed, float(evaluated), float(outlets)], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
@@ -684,6 +725,9 @@ def main():
                         a[k] += v
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:   # before the pass below writes the same buffers again
+        own = slice(None) if comm is None else slice(1, nyl + 1)
+        dump_outputs(torch, args.dump_outputs, {"fel": fel[own], "p": p[own], "sd8": sd8[own], "ad8": ad8[own]}, rank, world)
     # One more pass of the same step, outside the timed region, with every launch of the tile-relaxation kernel
     # bracketed by HIP events on the library's stream (two event records per launch would cost ~5 % inside it):
     # the dominant kernel's average launch duration for the roofline object.
