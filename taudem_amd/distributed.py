@@ -29,6 +29,19 @@ def partition_rows(ny: int, size: int):
     return out
 
 
+def strip_rows(per_row, y0: int, y1: int):
+    """Global per-row values (cell sizes dxc / dyc of ny rows) -> the y1 - y0 + 2 rows of the strip array of [y0, y1): the halo rows
+    are the global rows y0 - 1 and y1, clamped into the raster (rows_of in taudem_amd/csrc/tool_strips.hpp).  A scalar stays a scalar.
+    The clamp is the 1-rank reference: a strip's edge cells read the neighbouring global row, whatever the cut."""
+    a = np.asarray(per_row, dtype=np.float64)
+    if a.ndim == 0:
+        return float(a)
+    ny = a.shape[0]
+    if not (0 <= y0 < y1 <= ny):
+        raise ValueError(f"strip rows [{y0}, {y1}) outside the {ny} rows given")
+    return np.ascontiguousarray(a[np.clip(np.arange(y0 - 1, y1 + 1), 0, ny - 1)])
+
+
 class StripComm:
     """tdx_comm backed by a torch.distributed process group (ranks ordered north to south)."""
 

@@ -71,6 +71,8 @@ def make_case(name, O):
         return O.synth_dem((300, 260), 13), {"TDX_AD8_BIG_THRESHOLD": "40"}
     if name == "wide":
         return O.synth_dem((1000, 1400), 3), {}
+    if name == "geographic":         # per-row cell sizes (gpu_test: the coarse band of tests/cellsizes.py)
+        return O.synth_dem((300, 260), 29), {}
     raise ValueError(name)
 
 
@@ -80,7 +82,7 @@ def gpu_test(case):
 
     import taudem_amd as T
     from oracle import oracle as O
-    from taudem_amd.distributed import StripComm, StripPipeline, partition_rows
+    from taudem_amd.distributed import StripComm, StripPipeline, partition_rows, strip_rows
 
     rank, size = dist.get_rank(), dist.get_world_size()
     ndev = torch.cuda.device_count()
@@ -92,6 +94,14 @@ def gpu_test(case):
     ny, nx = dem.shape
     y0, y1 = partition_rows(ny, size)[rank]
     nyl = y1 - y0
+    # cell sizes: global (the oracle's) and this strip's rows with their halo rows (strip_rows)
+    if case.startswith("geographic"):
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from cellsizes import rows
+        d8x, d8y = dfx, dfy = rows("band", ny)
+    else:
+        d8x, d8y, dfx, dfy = 30.0, 30.0, 30.0, 20.0
+    s8x, s8y, sfx, sfy = (strip_rows(a, y0, y1) for a in (d8x, d8y, dfx, dfy))
     ctx = T.Context(device)
     comm = StripComm(nx, device=device)
     pipe = StripPipeline(ctx, comm, nx, nyl)
@@ -99,7 +109,7 @@ def gpu_test(case):
     d_dem.fill_(12345.0)   # halo rows are the library's business: poison them
     d_dem[1:nyl + 1] = torch.from_numpy(dem[y0:y1]).to(d_dem.device)
     fel, st1 = pipe.pitremove(d_dem, -9999.0)
-    p, sd8, st2 = pipe.d8flowdir(fel, -3.0e38, 30.0, 30.0)
+    p, sd8, st2 = pipe.d8flowdir(fel, -3.0e38, s8x, s8y)
     outs = {"fel": fel, "p": p, "sd8": sd8}
     for cc in (True, False):
         a, st3 = pipe.aread8(p, -32768, contcheck=cc)
@@ -120,14 +130,14 @@ def gpu_test(case):
         dmf = (0.9 + 0.1 * rng.random(dem.shape, dtype=np.float32)).astype(np.float32)
         d_w = pipe.empty(torch.float32); d_w.zero_(); d_w[1:nyl + 1] = torch.from_numpy(wgt[y0:y1]).to(d_w.device)
         d_dm = pipe.empty(torch.float32); d_dm.zero_(); d_dm[1:nyl + 1] = torch.from_numpy(dmf[y0:y1]).to(d_dm.device)
-        ang, slp, std = pipe.dinfflowdir(fel, -3.0e38, 30.0, 20.0)
+        ang, slp, std = pipe.dinfflowdir(fel, -3.0e38, sfx, sfy)
         outs["ang"], outs["slp"] = ang, slp
-        outs["sca"] = pipe.areadinf(ang, dx=30.0, dy=20.0, contcheck=True)[0].clone()
-        outs["sca_w_nc"], sta = pipe.areadinf(ang, dx=30.0, dy=20.0, weights=d_w, contcheck=False)
+        outs["sca"] = pipe.areadinf(ang, dx=sfx, dy=sfy, contcheck=True)[0].clone()
+        outs["sca_w_nc"], sta = pipe.areadinf(ang, dx=sfx, dy=sfy, weights=d_w, contcheck=False)
         outs["sca_w_nc"] = outs["sca_w_nc"].clone()
-        outs["dsca_nc"] = pipe.dinfdecayaccum(ang, d_dm, dx=30.0, dy=20.0, contcheck=False)[0].clone()
-        outs["sca_o_nc"] = pipe.areadinf(ang, dx=30.0, dy=20.0, contcheck=False, outlets=lo)[0].clone()
-        outs["dsca_w_o_nc"] = pipe.dinfdecayaccum(ang, d_dm, dx=30.0, dy=20.0, weights=d_w, contcheck=False, outlets=lo)[0].clone()
+        outs["dsca_nc"] = pipe.dinfdecayaccum(ang, d_dm, dx=sfx, dy=sfy, contcheck=False)[0].clone()
+        outs["sca_o_nc"] = pipe.areadinf(ang, dx=sfx, dy=sfy, contcheck=False, outlets=lo)[0].clone()
+        outs["dsca_w_o_nc"] = pipe.dinfdecayaccum(ang, d_dm, dx=sfx, dy=sfy, weights=d_w, contcheck=False, outlets=lo)[0].clone()
     gathered = {}
     for k, t in outs.items():
         mine = t[1:nyl + 1].cpu().contiguous()
@@ -147,7 +157,7 @@ def gpu_test(case):
                 return np.array_equal(a.view(np.uint32), b.view(np.uint32))
             return np.array_equal(a, b)
         fel_o = O.pitremove(dem, -9999.0)
-        p_o, sd8_o, sto = O.d8flowdir(fel_o, -3.0e38, 30.0, 30.0)
+        p_o, sd8_o, sto = O.d8flowdir(fel_o, -3.0e38, d8x, d8y)
         assert same(gathered["fel"], fel_o), f"{case}: fel differs from the oracle ({(gathered['fel'] != fel_o).sum()} cells)"
         assert same(gathered["sd8"], sd8_o), f"{case}: sd8 differs"
         assert same(gathered["p"], p_o), f"{case}: p differs from the oracle ({(gathered['p'] != p_o).sum()} cells)"
@@ -162,17 +172,17 @@ def gpu_test(case):
             a_o = O.aread8(p_o, -32768, weights_nodata=-9999.0, **kw)
             assert same(gathered[key], a_o), f"{case}: {key} differs from the oracle ({(gathered[key] != a_o).sum()} cells)"
         if dinf:
-            ang_o, slp_o, _ = O.dinfflowdir(fel_o, -3.0e38, 30.0, 20.0)
+            ang_o, slp_o, _ = O.dinfflowdir(fel_o, -3.0e38, dfx, dfy)
             assert same(gathered["ang"], ang_o), f"{case}: ang differs from the oracle ({(gathered['ang'] != ang_o).sum()} cells)"
             assert same(gathered["slp"], slp_o), f"{case}: slp differs"
             def close(a, b, name):   # gate of the north star: 1e-6 relative on D-infinity areas (observed: identical bits)
                 ok = (a == b) | (np.abs(a - b) <= 1e-6 * np.abs(b))
                 assert ok.all(), f"{case}: {name}: {(~ok).sum()} cells beyond 1e-6 relative"
-            close(gathered["sca"], O.areadinf(ang_o, dx=30.0, dy=20.0, contcheck=True), "sca")
-            close(gathered["sca_w_nc"], O.areadinf(ang_o, dx=30.0, dy=20.0, weights=wgt, contcheck=False), "sca_w_nc")
-            close(gathered["dsca_nc"], O.dinfdecayaccum(ang_o, dmf, dx=30.0, dy=20.0, contcheck=False), "dsca_nc")
-            close(gathered["sca_o_nc"], O.areadinf(ang_o, dx=30.0, dy=20.0, contcheck=False, outlets=og), "sca_o_nc")
-            close(gathered["dsca_w_o_nc"], O.dinfdecayaccum(ang_o, dmf, dx=30.0, dy=20.0, weights=wgt, contcheck=False, outlets=og), "dsca_w_o_nc")
+            close(gathered["sca"], O.areadinf(ang_o, dx=dfx, dy=dfy, contcheck=True), "sca")
+            close(gathered["sca_w_nc"], O.areadinf(ang_o, dx=dfx, dy=dfy, weights=wgt, contcheck=False), "sca_w_nc")
+            close(gathered["dsca_nc"], O.dinfdecayaccum(ang_o, dmf, dx=dfx, dy=dfy, contcheck=False), "dsca_nc")
+            close(gathered["sca_o_nc"], O.areadinf(ang_o, dx=dfx, dy=dfy, contcheck=False, outlets=og), "sca_o_nc")
+            close(gathered["dsca_w_o_nc"], O.dinfdecayaccum(ang_o, dmf, dx=dfx, dy=dfy, weights=wgt, contcheck=False, outlets=og), "dsca_w_o_nc")
         print(f"strip_worker {case}: {size} ranks bit-exact vs oracle; pit outer rounds {st1['cells_evaluated']}, "
               f"flat iterations {st2['flat_iterations']}, ad8 outer rounds {st3['rounds']}, exchanges {comm.exchanges}, allreduces {comm.allreduces}",
               flush=True)

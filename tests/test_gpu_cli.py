@@ -20,13 +20,21 @@ def run(tool, *args):
     return r.stdout
 
 
-@pytest.mark.parametrize("case", ["plain", "rect_dxdy"])
+def _geotransform(g):
+    """(geotransform, geographic) the golden case's rasters were written with (tests/golden/make_golden.py)"""
+    ny = g["dem"].shape[0]
+    dx, dy = float(g["dx"]), float(g["dy"])
+    if bool(g["geographic"]):
+        return (-111.9, dx, 0.0, 41.9, 0.0, -dy), True
+    return (1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy), False
+
+
+@pytest.mark.parametrize("case", ["plain", "rect_dxdy", "geographic"])
 def test_cli_d8_chain_matches_reference_outputs(tmp_path, case):
     g = load_golden(case)
-    ny, nx = g["dem"].shape
-    dx, dy = float(g["dx"]), float(g["dy"])
+    gt, geo = _geotransform(g)
     f = lambda s: str(tmp_path / s)  # noqa: E731
-    T.write_raster(f("dem.tif"), np.ascontiguousarray(g["dem"]), float(g["nodata"]), geotransform=(1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy))
+    T.write_raster(f("dem.tif"), np.ascontiguousarray(g["dem"]), float(g["nodata"]), geotransform=gt, geographic=geo)
     out = run("pitremove", "-z", f("dem.tif"), "-fel", f("demfel.tif"))
     assert "PitRemove version 5.4.0" in out and "Compute time" in out          # banner + timing block of src/flood.cpp:61,517-519
     run("d8flowdir", "-fel", f("demfel.tif"), "-p", f("demp.tif"), "-sd8", f("demsd8.tif"))
@@ -45,21 +53,24 @@ def test_cli_d8_chain_matches_reference_outputs(tmp_path, case):
     assert ainfo["nodata"] == -1.0 and tuple(ainfo["geotransform"]) == tuple(info["geotransform"])   # src/aread8.cpp:310-311, tiffIO.cpp:344-349
 
 
-def test_cli_dinf_chain_matches_reference_outputs(tmp_path):
-    g = load_golden("plain")
-    ny, nx = g["dem"].shape
-    dx, dy = float(g["dx"]), float(g["dy"])
+@pytest.mark.parametrize("case", ["plain", "geographic"])
+def test_cli_dinf_chain_matches_reference_outputs(tmp_path, case):
+    g = load_golden(case)
+    gt, geo = _geotransform(g)
     f = lambda s: str(tmp_path / s)  # noqa: E731
-    T.write_raster(f("fel.tif"), np.ascontiguousarray(g["fel"]), -3.0e38, geotransform=(1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy))
+    T.write_raster(f("fel.tif"), np.ascontiguousarray(g["fel"]), -3.0e38, geotransform=gt, geographic=geo)
+    T.write_raster(f("dm.tif"), np.ascontiguousarray(g["dm"]), -9999.0, geotransform=gt, geographic=geo)
     run("dinfflowdir", "-fel", f("fel.tif"), "-ang", f("ang.tif"), "-slp", f("slp.tif"))
     run("areadinf", "-ang", f("ang.tif"), "-sca", f("sca.tif"))
+    run("dinfdecayaccum", "-ang", f("ang.tif"), "-dm", f("dm.tif"), "-dsca", f("dsca.tif"))
     ang, _ = T.read_raster(f("ang.tif"), np.float32)
     slp, _ = T.read_raster(f("slp.tif"), np.float32)
     sca, _ = T.read_raster(f("sca.tif"), np.float32)
+    dsca, _ = T.read_raster(f("dsca.tif"), np.float32)
     assert bits_equal(ang, g["ang"]), describe_diff(ang, g["ang"], "ang")
     assert bits_equal(slp, g["slp"]), describe_diff(slp, g["slp"], "slp")
-    ok = np.isclose(sca, g["sca"], rtol=1e-6, atol=0) | (sca == g["sca"])
-    assert ok.all(), f"sca: {(~ok).sum()} cells beyond 1e-6 relative"
+    assert bits_equal(sca, g["sca"]), describe_diff(sca, g["sca"], "sca")
+    assert bits_equal(dsca, g["dsca"]), describe_diff(dsca, g["dsca"], "dsca")
 
 
 REF = os.path.join(ROOT, "oracle", "_ref")

@@ -28,11 +28,29 @@ def _case(seed):
 # (TDX_FUZZ_SEEDS=n: a longer one-off sweep, e.g. after a change of the strip protocol; TDX_FUZZ_SCALE=k: rasters up to k x larger on each side)
 @pytest.mark.parametrize("seed", range(int(os.environ.get("TDX_FUZZ_SEEDS", "32"))))
 def test_random_cut_random_raster(seed, oracle, monkeypatch):
+    _fuzz(seed, oracle, monkeypatch, _case(seed), 30.0, 25.0, f"seed {seed}")
+
+
+# Per-row cell sizes (tests/cellsizes.py): the coarse geographic band (70 N -> 40 N) and `wild` rows, each strip given its rows through
+# taudem_amd.distributed.strip_rows - a halo row's sizes are those of the neighbouring global row - and the restatement the global rows.
+# Seeds 100 + i: other shapes and cuts than the constant-size seeds above.
+@pytest.mark.parametrize("kind", ["geographic", "wild"])
+@pytest.mark.parametrize("seed", range(int(os.environ.get("TDX_FUZZ_SEEDS", "32")) // 2))
+def test_random_cut_random_raster_per_row_sizes(seed, kind, oracle, monkeypatch):
+    from cellsizes import rows
+
+    case = _case(100 + seed)
+    dx, dy = rows("band" if kind == "geographic" else "wild", case[0], seed=seed)
+    _fuzz(100 + seed, oracle, monkeypatch, case, dx, dy, f"seed {100 + seed} ({kind} rows)")
+
+
+def _fuzz(seed, oracle, monkeypatch, case, dx, dy, label):
+    """dx, dy: scalars or the global per-row arrays."""
     import torch
 
-    from taudem_amd.distributed import StripGroup, StripPipeline, partition_rows
+    from taudem_amd.distributed import StripGroup, StripPipeline, partition_rows, strip_rows
 
-    ny, nx, world, holes, thr, eager, rng = _case(seed)
+    ny, nx, world, holes, thr, eager, rng = case
     dem = oracle.synth_dem((ny, nx), 500 + seed)
     for _ in range(holes):
         y0, x0 = int(rng.integers(0, ny - 5)), int(rng.integers(0, nx - 5))
@@ -40,22 +58,22 @@ def test_random_cut_random_raster(seed, oracle, monkeypatch):
     w = rng.random((ny, nx), dtype=np.float32) + np.float32(0.25)
     dm = (rng.random((ny, nx), dtype=np.float32) * np.float32(0.1) + np.float32(0.9)).astype(np.float32)
     fel_o = oracle.pitremove(dem, -9999.0)
-    p_o, sd8_o, _ = oracle.d8flowdir(fel_o, -3.0e38, 30.0, 25.0)
-    ang_o, slp_o, _ = oracle.dinfflowdir(fel_o, -3.0e38, 30.0, 25.0)
+    p_o, sd8_o, _ = oracle.d8flowdir(fel_o, -3.0e38, dx, dy)
+    ang_o, slp_o, _ = oracle.dinfflowdir(fel_o, -3.0e38, dx, dy)
     a_o = oracle.aread8(p_o, -32768, contcheck=False)
     aw_o = oracle.aread8(p_o, -32768, weights=w, contcheck=True)
-    sca_o = oracle.areadinf(ang_o, ANG_ND, 30.0, 25.0, contcheck=False)
+    sca_o = oracle.areadinf(ang_o, ANG_ND, dx, dy, contcheck=False)
     # outlets: a handful of cells with large D8 area (inside the raster, wherever they fall relative to the cut)
     flat = np.argsort(a_o, axis=None)[-400:]
     pick = rng.choice(flat, size=5, replace=False)
     oy, ox = np.unravel_index(pick, a_o.shape)
     outl = (ox.astype(np.int32), oy.astype(np.int32))
     ao_o = oracle.aread8(p_o, -32768, contcheck=False, outlets=outl)
-    d_o = oracle.dinfdecayaccum(ang_o, dm, dx=30.0, dy=25.0, weights=w, contcheck=False, outlets=outl)
+    d_o = oracle.dinfdecayaccum(ang_o, dm, dx=dx, dy=dy, weights=w, contcheck=False, outlets=outl)
     # the reverse sweeps (round 6: a tile routine of their own): a disturbance grid of scattered cells, the weights as the accumulated quantity
     dg = (rng.random((ny, nx)) < 0.02).astype(np.int32)
-    dep_o = oracle.dinfupdependence(ang_o, dg, dx=30.0, dy=25.0)
-    racc_o, dmax_o = oracle.dinfrevaccum(ang_o, w, dx=30.0, dy=25.0)
+    dep_o = oracle.dinfupdependence(ang_o, dg, dx=dx, dy=dy)
+    racc_o, dmax_o = oracle.dinfrevaccum(ang_o, w, dx=dx, dy=dy)
     monkeypatch.setenv("TDX_AD8_BIG_THRESHOLD", str(thr))
     monkeypatch.setenv("TDX_SWEEP_EAGER_ROUNDS", str(eager))
     monkeypatch.setenv("TDX_REACH_EAGER_ROUNDS", str(eager))
@@ -67,6 +85,7 @@ def test_random_cut_random_raster(seed, oracle, monkeypatch):
             nyl = y1 - y0
             pipe = StripPipeline(c, comm, nx, nyl)
             sl = slice(1, nyl + 1)
+            sdx, sdy = strip_rows(dx, y0, y1), strip_rows(dy, y0, y1)
 
             def put(a, dt):
                 t = pipe.empty(dt)
@@ -74,21 +93,21 @@ def test_random_cut_random_raster(seed, oracle, monkeypatch):
                 return t
             d = put(dem, torch.float32)
             fel, _ = pipe.pitremove(d, -9999.0)
-            p, sd8, _ = pipe.d8flowdir(fel, -3.0e38, 30.0, 25.0)
-            ang, slp, _ = pipe.dinfflowdir(fel, -3.0e38, 30.0, 25.0)
+            p, sd8, _ = pipe.d8flowdir(fel, -3.0e38, sdx, sdy)
+            ang, slp, _ = pipe.dinfflowdir(fel, -3.0e38, sdx, sdy)
             wt, dmt = put(w, torch.float32), put(dm, torch.float32)
             a, _ = pipe.aread8(p, -32768, contcheck=False)
             aw, _ = pipe.aread8(p, -32768, weights=wt, contcheck=True)
-            sca, _ = pipe.areadinf(ang, ANG_ND, 30.0, 25.0, contcheck=False)
+            sca, _ = pipe.areadinf(ang, ANG_ND, sdx, sdy, contcheck=False)
             lo = pipe.local_outlets(outl[0], outl[1], y0)
             ao, _ = pipe.aread8(p, -32768, contcheck=False, outlets=lo)
-            dd, _ = pipe.dinfdecayaccum(ang, dmt, dx=30.0, dy=25.0, weights=wt, contcheck=False, outlets=lo)
-            dep, _ = pipe.dinfupdependence(ang, put(dg, torch.int32), dx=30.0, dy=25.0)
-            racc, dmax, _ = pipe.dinfrevaccum(ang, wt, dx=30.0, dy=25.0)
+            dd, _ = pipe.dinfdecayaccum(ang, dmt, dx=sdx, dy=sdy, weights=wt, contcheck=False, outlets=lo)
+            dep, _ = pipe.dinfupdependence(ang, put(dg, torch.int32), dx=sdx, dy=sdy)
+            racc, dmax, _ = pipe.dinfrevaccum(ang, wt, dx=sdx, dy=sdy)
             return {k: v[sl].cpu().numpy() for k, v in (("fel", fel), ("p", p), ("sd8", sd8), ("ang", ang), ("slp", slp), ("ad8", a), ("ad8_w", aw), ("sca", sca),
                                                         ("ad8_o", ao), ("dsca_o", dd), ("dep", dep), ("racc", racc), ("dmax", dmax))}
         res = grp.run(rank_main)
-    what = f"seed {seed}: {ny} x {nx} in {world} strips, {holes} holes, big-cell threshold {thr}, {eager} rounds between exchanges"
+    what = f"{label}: {ny} x {nx} in {world} strips, {holes} holes, big-cell threshold {thr}, {eager} rounds between exchanges"
     for key, ref in (("fel", fel_o), ("p", p_o), ("sd8", sd8_o), ("ang", ang_o), ("slp", slp_o), ("ad8", a_o), ("ad8_w", aw_o), ("sca", sca_o), ("ad8_o", ao_o),
                      ("dsca_o", d_o), ("dep", dep_o), ("racc", racc_o), ("dmax", dmax_o)):
         got = np.concatenate([r[key] for r in res], axis=0)

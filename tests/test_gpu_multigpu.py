@@ -127,19 +127,22 @@ def test_group_peer_transport_protocol():
     assert not errors, errors
 
 
-@pytest.mark.parametrize("case,ngpus", [("plain", 2), ("holes", 3), ("rect_dxdy", 4)])
+@pytest.mark.parametrize("case,ngpus", [("plain", 2), ("holes", 3), ("rect_dxdy", 4), ("geographic", 3)])
 def test_cli_gpus_n_matches_reference_outputs(tmp_path, case, ngpus):
     """pitremove / d8flowdir / aread8 (+ -wg, -o) / dinfflowdir / areadinf / dinfdecayaccum with --gpus N: pixels identical to the
-    rasters of the real reference tools (which are themselves rank-count independent)."""
+    rasters the real reference tools wrote on ONE rank.  On a projected raster those do not depend on the rank count.  On a geographic
+    one (per-row cell sizes; here 30-row strips, shorter than a tile) the reference's own N-rank rasters do: its halo rows keep the
+    previous row's sizes - the product gives a halo row the neighbouring global row's sizes, the 1-rank result."""
     g = load_golden(case)
     ny, nx = g["dem"].shape
     dx, dy = float(g["dx"]), float(g["dy"])
-    gt = (1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy)
+    geo = bool(g["geographic"])
+    gt = (-111.9, dx, 0.0, 41.9, 0.0, -dy) if geo else (1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy)   # tests/golden/make_golden.py
     f = lambda s: str(tmp_path / s)  # noqa: E731
     N = ["--gpus", str(ngpus)]
-    T.write_raster(f("dem.tif"), np.ascontiguousarray(g["dem"]), float(g["nodata"]), geotransform=gt)
-    T.write_raster(f("w.tif"), np.ascontiguousarray(g["w"]), -9999.0, geotransform=gt)
-    T.write_raster(f("dm.tif"), np.ascontiguousarray(g["dm"]), -9999.0, geotransform=gt)
+    T.write_raster(f("dem.tif"), np.ascontiguousarray(g["dem"]), float(g["nodata"]), geotransform=gt, geographic=geo)
+    T.write_raster(f("w.tif"), np.ascontiguousarray(g["w"]), -9999.0, geotransform=gt, geographic=geo)
+    T.write_raster(f("dm.tif"), np.ascontiguousarray(g["dm"]), -9999.0, geotransform=gt, geographic=geo)
     with open(f("outlets.txt"), "w") as fh:
         for x_, y_ in zip(*g["outlet_xy"]):
             fh.write(f"{float(x_)!r} {float(y_)!r}\n")
@@ -154,7 +157,7 @@ def test_cli_gpus_n_matches_reference_outputs(tmp_path, case, ngpus):
     run("dinfdecayaccum", *N, "-ang", f("ang.tif"), "-dm", f("dm.tif"), "-dsca", f("dsca.tif"))
     from conftest import load_golden_gridnet
     h = load_golden_gridnet(case)
-    T.write_raster(f("gmask.tif"), np.ascontiguousarray(h["mask_i32"]), -1, geotransform=gt)
+    T.write_raster(f("gmask.tif"), np.ascontiguousarray(h["mask_i32"]), -1, geotransform=gt, geographic=geo)
     run("gridnet", "-p", f("p.tif"), "-plen", f("plen.tif"), "-tlen", f("tlen.tif"), "-gord", f("gord.tif"), *N)
     run("gridnet", *N, "-p", f("p.tif"), "-plen", f("plenm.tif"), "-tlen", f("tlenm.tif"), "-gord", f("gordm.tif"), "-mask", f("gmask.tif"), "-thresh", str(int(h["gn_thresh"])))
     run("gridnet", *N, "-p", f("p.tif"), "-plen", f("pleno.tif"), "-tlen", f("tleno.tif"), "-gord", f("gordo.tif"), "-o", f("outlets.txt"))
