@@ -223,6 +223,20 @@ int tdx_dinfrevaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64
 int tdx_dinfrevaccum(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
                      const double* dxc, const double* dyc, const float* w, float w_nodata,
                      float* racc, float* dmax, tdx_stats* stats);
+/* dinfdistdown() src/DinfDistDown.cpp:66-1060: distance from each cell down to the stream along the D-infinity flow.
+ * typemethod 0 h (horizontal, along the flow path), 1 v (vertical drop: with statmethod 0 this is HAND), 2 p (Pythagorean,
+ * sqrt(h^2 + v^2)), 3 s (surface: sqrt(dz^2 + dh^2) per step); statmethod 0 ave, 1 max, 2 min over the receivers.  Stream cells
+ * are those whose src value (int16, the reference's SHORT read) is >= 1.  fel (with fel_nodata) is needed by v, p and s and may be
+ * NULL for h; w (weights applied to the horizontal steps of h, p and s; v ignores them, as the reference does) may be NULL.
+ * contcheck: a cell with a receiver outside the raster or without a result gets nodata.  Result float, nodata -FLT_MAX. */
+int tdx_dinfdistdown_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
+                         const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const int16_t* d_src,
+                         const float* d_w, float w_nodata, int statmethod, int typemethod, int contcheck,
+                         float* d_dd, tdx_stats* stats);
+int tdx_dinfdistdown(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
+                     const double* dxc, const double* dyc, const float* fel, float fel_nodata, const int16_t* src,
+                     const float* w, float w_nodata, int statmethod, int typemethod, int contcheck,
+                     float* dd, tdx_stats* stats);
 /* dsllArea() src/DinfConcLimAccum.cpp:61-326: concentration limited accumulation.  ctpt = csol where the indicator dg (int16,
  * a SHORT grid in the reference) is > 0, else sum over the contributing cells of p * ctpt * q * dm divided by the cell's own q;
  * cells with q <= 0 get no value.  Result float, nodata -FLT_MAX.  Outlets as for tdx_areadinf. */
@@ -349,6 +363,9 @@ int tdx_dinfupdependence_strip(tdx_context* ctx, const tdx_comm* comm, float* d_
                                const double* dxc, const double* dyc, int32_t* d_dg, float* d_dep, tdx_stats* stats);
 int tdx_dinfrevaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                            const double* dxc, const double* dyc, float* d_w, float w_nodata, float* d_racc, float* d_dmax, tdx_stats* stats);
+int tdx_dinfdistdown_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
+                           const double* dxc, const double* dyc, float* d_fel, float fel_nodata, const int16_t* d_src,
+                           float* d_w, float w_nodata, int statmethod, int typemethod, int contcheck, float* d_dd, tdx_stats* stats);
 /* the limited D-infinity accumulations on strips (outlet_row: array row of the strip, as for tdx_areadinf_strip) */
 int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg,
@@ -433,6 +450,10 @@ int tdx_tool_d8flowpathextremeup(const char* pfile, const char* safile, const ch
 int tdx_tool_dinfupdependence(const char* angfile, const char* dgfile, const char* depfile);
 /* int dsaccum(char* angfile, char* wgfile, char* raccfile, char* dmaxfile)   src/DinfRevAccum.cpp:51 */
 int tdx_tool_dinfrevaccum(const char* angfile, const char* wgfile, const char* raccfile, const char* dmaxfile);
+/* int dinfdistdown(char* angfile, char* felfile, char* slpfile, char* wfile, char* srcfile, char* dtsfile, int statmethod,
+ *                  int typemethod, int usew, int concheck)                   src/DinfDistDown.cpp:66-67 (slpfile is never read) */
+int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* slpfile, const char* wfile, const char* srcfile,
+                          const char* dtsfile, int statmethod, int typemethod, int usew, int concheck);
 /* int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile,
  *              char* dgfile, int useOutlets, int contcheck, float cSol)          src/DinfConcLimAccum.cpp:61-62 */
 int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* lyrname,

@@ -1,6 +1,6 @@
 """The accumulation tools beside the headline path (SURVEY.md 8f ranks 2 and 4, config 5's kernel) on one MI355X, HBM-resident inputs:
 weighted AreaD8, D8FlowPathExtremeUp, GridNet, DinfDecayAccum with weights and outlets, DinfUpDependence, DinfRevAccum,
-DinfConcLimAccum, DinfTransLimAccum.  One JSON line with the ms of each (library-side HIP-event time of the call).
+DinfConcLimAccum, DinfTransLimAccum, DinfDistDown (ave v = HAND, ave h; streams = D-infinity area above the 98th percentile).  One JSON line with the ms of each (library-side HIP-event time of the call).
 usage: python scripts/bench_flowalg.py [--size 16384]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,7 +21,7 @@ fel = ctx.pitremove(dem, -9999.0)
 del dem
 p, _ = ctx.d8flowdir(fel, -3.0e38, 30.0, 30.0, want_slope=False)
 ang, slp = ctx.dinfflowdir(fel, -3.0e38, 30.0, 30.0)
-del fel, slp
+del slp
 g = torch.Generator(device=dev).manual_seed(7)
 w = torch.rand((n, n), device=dev, dtype=torch.float32, generator=g)
 w2 = 0.9 + 0.1 * torch.rand((n, n), device=dev, dtype=torch.float32, generator=g)
@@ -46,6 +46,12 @@ timed("dinfdecayaccum_w_outlets", lambda: ctx.dinfdecayaccum(ang, w2, dx=30.0, d
 timed("dinfdecayaccum", lambda: ctx.dinfdecayaccum(ang, w2, dx=30.0, dy=30.0, stats=True))
 timed("dinfupdependence", lambda: ctx.dinfupdependence(ang, dg32, dx=30.0, dy=30.0, stats=True))
 timed("dinfrevaccum", lambda: ctx.dinfrevaccum(ang, w, dx=30.0, dy=30.0, stats=True))
+if not only or only & {"dinfdistdown_ave_v", "dinfdistdown_ave_h"}:
+    sca = ctx.areadinf(ang, dx=30.0, dy=30.0)
+    src = (sca >= torch.quantile(sca[::16, ::16].flatten(), 0.98)).to(torch.int16)
+    del sca
+timed("dinfdistdown_ave_v", lambda: ctx.dinfdistdown(ang, src, fel, stat="ave", kind="v", dx=30.0, dy=30.0, stats=True))
+timed("dinfdistdown_ave_h", lambda: ctx.dinfdistdown(ang, src, None, stat="ave", kind="h", dx=30.0, dy=30.0, stats=True))
 timed("dinfconclimaccum", lambda: ctx.dinfconclimaccum(ang, w2, dg16, w + 0.5, dx=30.0, dy=30.0, stats=True))
 timed("dinftranslimaccum_cs", lambda: ctx.dinftranslimaccum(ang, w, 50.0 * w2, cs=w2, dx=30.0, dy=30.0, stats=True))
 print(json.dumps({"metric": "ms per call", "size": n, "n_gpus": 1, "ms": res,

@@ -153,6 +153,11 @@ _SIGNATURES = {
     "tdx_dinfrevaccum_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
     "tdx_dinfrevaccum": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
     "tdx_dinfrevaccum_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, src, w, w_nodata, statmethod, typemethod, contcheck, dd, stats
+    "tdx_dinfdistdown_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tdx_dinfdistdown": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tdx_dinfdistdown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tdx_tool_dinfdistdown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tdx_tool_dinfupdependence": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     "tdx_tool_dinfrevaccum": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, dg, q, q_nodata, csol, contcheck, ox, oy, n_outlets, ctpt, stats

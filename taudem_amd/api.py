@@ -20,6 +20,18 @@ AREA_NODATA = np.float32(-1.0)              # src/aread8.cpp:193
 ANG_NODATA = np.float32(-3.402823466e38)    # MISSINGFLOAT, src/commonLib.h:80
 
 
+DISTDOWN_STATS = {"ave": 0, "max": 1, "min": 2}                    # -m <stat> of src/DinfDistDownmn.cpp:133-196
+DISTDOWN_KINDS = {"h": 0, "v": 1, "p": 2, "s": 3}                   # -m <type>
+
+
+def _distdown_mode(stat, kind):
+    if stat not in DISTDOWN_STATS:
+        raise ValueError(f"stat must be one of {sorted(DISTDOWN_STATS)}, not {stat!r}")
+    if kind not in DISTDOWN_KINDS:
+        raise ValueError(f"kind must be one of {sorted(DISTDOWN_KINDS)}, not {kind!r}")
+    return DISTDOWN_STATS[stat], DISTDOWN_KINDS[kind]
+
+
 def _is_torch(x):
     return x is not None and type(x).__module__.startswith("torch")
 
@@ -327,6 +339,34 @@ class Context:
         check(self._pick(dev, "tdx_dinfrevaccum")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw,
                                                    float(w_nodata), pr, pm, C.byref(st)), self._h)
         return (racc, dmax, st.as_dict()) if stats else (racc, dmax)
+
+    def dinfdistdown(self, ang, src, fel=None, *, stat="ave", kind="v", weights=None, weights_nodata=-9999.0, contcheck=True, dx=1.0, dy=1.0,
+                     nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
+        """dd = dinfdistdown(ang, fel, src, w)  (src/DinfDistDown.cpp:66): distance from each cell down to the stream (src int16 >= 1).
+
+        kind "h" horizontal, "v" vertical drop (with stat "ave": HAND), "p" Pythagorean, "s" surface; stat "ave", "max" or "min" over
+        the receivers.  `fel` is required for v, p and s; `weights` scale the horizontal steps of h, p and s (v ignores them, as the
+        reference does).  dd float32, nodata -FLT_MAX."""
+        sm, tm = _distdown_mode(stat, kind)
+        if tm != DISTDOWN_KINDS["h"] and fel is None:
+            raise ValueError(f"kind {kind!r} needs fel")
+        ny, nx = ang.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        dd = self._out(ang, np.float32, (ny, nx))
+        use_fel = tm != DISTDOWN_KINDS["h"]
+        use_w = weights is not None and tm != DISTDOWN_KINDS["v"]
+        pa, dev = self._ptr(ang, np.float32, name="ang")
+        ps, sdev = self._ptr(src, np.int16, (ny, nx), "src")
+        pf, fdev = self._ptr(fel if use_fel else None, np.float32, (ny, nx), "fel")
+        pw, wdev = self._ptr(weights if use_w else None, np.float32, (ny, nx), "weights")
+        po, _ = self._ptr(dd, np.float32, (ny, nx), "dd")
+        if sdev != dev or (use_fel and fdev != dev) or (use_w and wdev != dev):
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(ang, src, fel, weights)
+        check(self._pick(dev, "tdx_dinfdistdown")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf,
+                                                   float(fel_nodata), ps, pw, float(weights_nodata), sm, tm, int(bool(contcheck)), po, C.byref(st)), self._h)
+        return (dd, st.as_dict()) if stats else dd
 
     def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=float(ANG_NODATA), dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
                          outlets=None, stats=False):

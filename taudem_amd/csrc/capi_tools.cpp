@@ -10,6 +10,7 @@
 //   tdx_tool_dinfdecayaccum  <- dmarea()    src/dinfdecayaccum.cpp:61-324
 //   tdx_tool_dinfconclimaccum  <- dsllArea()  src/DinfConcLimAccum.cpp:61-326
 //   tdx_tool_dinftranslimaccum <- tlaccum()   src/DinfTransLimAccum.cpp:61-372
+//   tdx_tool_dinfdistdown    <- dinfdistdown()  src/DinfDistDown.cpp:66-1060
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -530,6 +531,69 @@ int tdx_tool_dinfrevaccum(const char* angfile, const char* wgfile, const char* r
     printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
            writet - begint);
     print_gpu_stats("dinfrevaccum", st, ang.info.nx * ang.info.ny);
+    return 0;
+}
+
+// dinfdistdown() (src/DinfDistDown.cpp:66-91) and its four tool functions: files in the reference's order (ang, then fel for v / p / s, w
+// for h / p / s when used, src), each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); slpfile is never read
+int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* srcfile, const char* dtsfile,
+                          int statmethod, int typemethod, int usew, int concheck) {
+    static const char* const banner[4] = {"-h", "-v", "-p", "-s"};
+    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
+    printf("DinfDistDown %s version %s\n", banner[typemethod], TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;   // (v: the weight code is commented out in the reference)
+    Raster ang, fel, w, src;
+    int rc = load_raster(angfile, tdx::DType::F32, ang);
+    if (rc != TDX_OK) return rc;
+    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
+    if (use_fel) {
+        rc = load_raster(felfile, tdx::DType::F32, fel);
+        if (rc != TDX_OK) return rc;
+        if (!compare_rasters(ang.info, angfile, fel.info, felfile)) return mismatch(felfile);
+    }
+    if (use_w) {
+        rc = load_raster(wfile, tdx::DType::F32, w);
+        if (rc != TDX_OK) return rc;
+        if (!compare_rasters(ang.info, angfile, w.info, wfile)) return mismatch(wfile);
+    }
+    rc = load_raster(srcfile, tdx::DType::I16, src);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(ang.info, angfile, src.info, srcfile)) return mismatch(srcfile);
+    const double readt = now_s();
+    std::vector<float> dd(ang.f.size());
+    const float fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            float* d_ang = j.strip<float>(ang.f.data());
+            float* d_fel = use_fel ? j.strip<float>(fel.f.data()) : nullptr;
+            float* d_w = use_w ? j.strip<float>(w.f.data()) : nullptr;
+            int16_t* d_src = j.strip<int16_t>(src.s.data());
+            float* d_dd = j.strip<float>(nullptr);
+            if (!d_ang || (use_fel && !d_fel) || (use_w && !d_w) || !d_src || !d_dd) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
+            const int e = tdx_dinfdistdown_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, fel_nd, d_src, d_w, w_nd,
+                                                 statmethod, typemethod, concheck, d_dd, s);
+            return e != TDX_OK ? e : (j.fetch(dd.data(), d_dd) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_dinfdistdown(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(),
+                              use_fel ? fel.f.data() : nullptr, fel_nd, src.s.data(), use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, dd.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(dtsfile, tdx::DType::F32, dd.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistDown.cpp:363-365)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("dinfdistdown", st, ang.info.nx * ang.info.ny);
     return 0;
 }
 

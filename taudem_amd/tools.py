@@ -80,6 +80,12 @@ def dsaccum(angfile, wgfile, raccfile, dmaxfile):
     return _lib.load().tdx_tool_dinfrevaccum(_b(angfile), _b(wgfile), _b(raccfile), _b(dmaxfile))
 
 
+def dinfdistdown(angfile, felfile, slpfile, wfile, srcfile, dtsfile, statmethod=0, typemethod=0, usew=0, concheck=1):
+    """src/DinfDistDown.cpp:66"""
+    return _lib.load().tdx_tool_dinfdistdown(_b(angfile), _b(felfile), _b(slpfile), _b(wfile), _b(srcfile), _b(dtsfile), int(statmethod), int(typemethod),
+                                             int(usew), int(concheck))
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
