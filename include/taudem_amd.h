@@ -237,6 +237,21 @@ int tdx_dinfdistdown(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny,
                      const double* dxc, const double* dyc, const float* fel, float fel_nodata, const int16_t* src,
                      const float* w, float w_nodata, int statmethod, int typemethod, int contcheck,
                      float* dd, tdx_stats* stats);
+/* dinfdistup() src/DinfDistUp.cpp:65-1214: distance from each cell up to the ridge along the D-infinity flow, over the neighbours that
+ * drain into it (AreaDinf's dependency graph, no outlets).  typemethod 0 h (horizontal, hdisttoridgegrd :94), 1 v (vertical rise,
+ * vrisetoridgegrd :356), 2 p (Pythagorean, sqrt(h^2 + v^2), pdisttoridgegrd :599), 3 s (surface: sqrt(dz^2 + dh^2) per step,
+ * sdisttoridgegrd :922); statmethod 0 ave, 1 max, 2 min over the contributors.  A contributor counts only if its proportion p > 0 and
+ * p > thresh (a float compared in double).  fel (with fel_nodata) is needed by v, p and s and may be NULL for h; p and s give nodata
+ * where the cell's own elevation is nodata, v does not test it (the reference computes with the raw nodata value there).  w (weights
+ * applied to the horizontal steps of h, p and s; v ignores them, as the reference does) may be NULL.  contcheck: a cell with any
+ * neighbour outside the raster or without an angle, or with a contributor without a result, gets nodata.  Ridge cells (no contributor)
+ * get 0.  Result float, nodata -FLT_MAX. */
+int tdx_dinfdistup_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
+                       const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const float* d_w, float w_nodata,
+                       int statmethod, int typemethod, int contcheck, float thresh, float* d_du, tdx_stats* stats);
+int tdx_dinfdistup(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
+                   const double* dxc, const double* dyc, const float* fel, float fel_nodata, const float* w, float w_nodata,
+                   int statmethod, int typemethod, int contcheck, float thresh, float* du, tdx_stats* stats);
 /* dsllArea() src/DinfConcLimAccum.cpp:61-326: concentration limited accumulation.  ctpt = csol where the indicator dg (int16,
  * a SHORT grid in the reference) is > 0, else sum over the contributing cells of p * ctpt * q * dm divided by the cell's own q;
  * cells with q <= 0 get no value.  Result float, nodata -FLT_MAX.  Outlets as for tdx_areadinf. */
@@ -366,6 +381,9 @@ int tdx_dinfrevaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang,
 int tdx_dinfdistdown_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                            const double* dxc, const double* dyc, float* d_fel, float fel_nodata, const int16_t* d_src,
                            float* d_w, float w_nodata, int statmethod, int typemethod, int contcheck, float* d_dd, tdx_stats* stats);
+int tdx_dinfdistup_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
+                         const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const float* d_w, float w_nodata,
+                         int statmethod, int typemethod, int contcheck, float thresh, float* d_du, tdx_stats* stats);
 /* the limited D-infinity accumulations on strips (outlet_row: array row of the strip, as for tdx_areadinf_strip) */
 int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg,
@@ -454,6 +472,10 @@ int tdx_tool_dinfrevaccum(const char* angfile, const char* wgfile, const char* r
  *                  int typemethod, int usew, int concheck)                   src/DinfDistDown.cpp:66-67 (slpfile is never read) */
 int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* slpfile, const char* wfile, const char* srcfile,
                           const char* dtsfile, int statmethod, int typemethod, int usew, int concheck);
+/* int dinfdistup(char* angfile, char* felfile, char* slpfile, char* wfile, char* rtrfile, int statmethod, int typemethod, int usew,
+ *                int concheck, float thresh)                                  src/DinfDistUp.cpp:65-66 (slpfile is never read) */
+int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* slpfile, const char* wfile, const char* rtrfile,
+                        int statmethod, int typemethod, int usew, int concheck, float thresh);
 /* int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile,
  *              char* dgfile, int useOutlets, int contcheck, float cSol)          src/DinfConcLimAccum.cpp:61-62 */
 int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* lyrname,

@@ -1,6 +1,7 @@
 """The accumulation tools beside the headline path (SURVEY.md 8f ranks 2 and 4, config 5's kernel) on one MI355X, HBM-resident inputs:
 weighted AreaD8, D8FlowPathExtremeUp, GridNet, DinfDecayAccum with weights and outlets, DinfUpDependence, DinfRevAccum,
-DinfConcLimAccum, DinfTransLimAccum, DinfDistDown (ave v = HAND, ave h; streams = D-infinity area above the 98th percentile).  One JSON line with the ms of each (library-side HIP-event time of the call).
+DinfConcLimAccum, DinfTransLimAccum, DinfDistDown (ave v = HAND, ave h; streams = D-infinity area above the 98th percentile),
+DinfDistUp (ave h, ave v, ave p).  One JSON line with the ms of each (library-side HIP-event time of the call).
 usage: python scripts/bench_flowalg.py [--size 16384]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -52,6 +53,9 @@ if not only or only & {"dinfdistdown_ave_v", "dinfdistdown_ave_h"}:
     del sca
 timed("dinfdistdown_ave_v", lambda: ctx.dinfdistdown(ang, src, fel, stat="ave", kind="v", dx=30.0, dy=30.0, stats=True))
 timed("dinfdistdown_ave_h", lambda: ctx.dinfdistdown(ang, src, None, stat="ave", kind="h", dx=30.0, dy=30.0, stats=True))
+timed("dinfdistup_ave_h", lambda: ctx.dinfdistup(ang, None, stat="ave", kind="h", dx=30.0, dy=30.0, stats=True))
+timed("dinfdistup_ave_v", lambda: ctx.dinfdistup(ang, fel, stat="ave", kind="v", dx=30.0, dy=30.0, stats=True))
+timed("dinfdistup_ave_p", lambda: ctx.dinfdistup(ang, fel, stat="ave", kind="p", dx=30.0, dy=30.0, stats=True))
 timed("dinfconclimaccum", lambda: ctx.dinfconclimaccum(ang, w2, dg16, w + 0.5, dx=30.0, dy=30.0, stats=True))
 timed("dinftranslimaccum_cs", lambda: ctx.dinftranslimaccum(ang, w, 50.0 * w2, cs=w2, dx=30.0, dy=30.0, stats=True))
 print(json.dumps({"metric": "ms per call", "size": n, "n_gpus": 1, "ms": res,

@@ -158,6 +158,11 @@ _SIGNATURES = {
     "tdx_dinfdistdown": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tdx_dinfdistdown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tdx_tool_dinfdistdown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, w, w_nodata, statmethod, typemethod, contcheck, thresh, du, stats
+    "tdx_dinfdistup_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
+    "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
+    "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
+    "tdx_tool_dinfdistup": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "tdx_tool_dinfupdependence": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     "tdx_tool_dinfrevaccum": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, dg, q, q_nodata, csol, contcheck, ox, oy, n_outlets, ctpt, stats

@@ -20,7 +20,7 @@ AREA_NODATA = np.float32(-1.0)              # src/aread8.cpp:193
 ANG_NODATA = np.float32(-3.402823466e38)    # MISSINGFLOAT, src/commonLib.h:80
 
 
-DISTDOWN_STATS = {"ave": 0, "max": 1, "min": 2}                    # -m <stat> of src/DinfDistDownmn.cpp:133-196
+DISTDOWN_STATS = {"ave": 0, "max": 1, "min": 2}                    # -m <stat> of src/DinfDistDownmn.cpp:133-196 (and of DinfDistUp)
 DISTDOWN_KINDS = {"h": 0, "v": 1, "p": 2, "s": 3}                   # -m <type>
 
 
@@ -367,6 +367,34 @@ class Context:
         check(self._pick(dev, "tdx_dinfdistdown")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf,
                                                    float(fel_nodata), ps, pw, float(weights_nodata), sm, tm, int(bool(contcheck)), po, C.byref(st)), self._h)
         return (dd, st.as_dict()) if stats else dd
+
+    def dinfdistup(self, ang, fel=None, *, stat="ave", kind="h", weights=None, weights_nodata=-9999.0, contcheck=True, thresh=0.0, dx=1.0, dy=1.0,
+                   nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
+        """du = dinfdistup(ang, fel, w)  (src/DinfDistUp.cpp:65): distance from each cell up to the ridge over the neighbours that drain into it.
+
+        kind "h" horizontal, "v" vertical rise, "p" Pythagorean, "s" surface; stat "ave", "max" or "min" over the contributors; a
+        neighbour contributes only if its proportion exceeds `thresh`.  `fel` is required for v, p and s; `weights` scale the horizontal
+        steps of h, p and s (v ignores them, as the reference does).  du float32, nodata -FLT_MAX; ridge cells get 0."""
+        sm, tm = _distdown_mode(stat, kind)
+        if tm != DISTDOWN_KINDS["h"] and fel is None:
+            raise ValueError(f"kind {kind!r} needs fel")
+        ny, nx = ang.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        du = self._out(ang, np.float32, (ny, nx))
+        use_fel = tm != DISTDOWN_KINDS["h"]
+        use_w = weights is not None and tm != DISTDOWN_KINDS["v"]
+        pa, dev = self._ptr(ang, np.float32, name="ang")
+        pf, fdev = self._ptr(fel if use_fel else None, np.float32, (ny, nx), "fel")
+        pw, wdev = self._ptr(weights if use_w else None, np.float32, (ny, nx), "weights")
+        po, _ = self._ptr(du, np.float32, (ny, nx), "du")
+        if (use_fel and fdev != dev) or (use_w and wdev != dev):
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(ang, fel, weights)
+        check(self._pick(dev, "tdx_dinfdistup")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf,
+                                                 float(fel_nodata), pw, float(weights_nodata), sm, tm, int(bool(contcheck)), float(thresh), po,
+                                                 C.byref(st)), self._h)
+        return (du, st.as_dict()) if stats else du
 
     def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=float(ANG_NODATA), dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
                          outlets=None, stats=False):

@@ -11,6 +11,7 @@
 //   tdx_tool_dinfconclimaccum  <- dsllArea()  src/DinfConcLimAccum.cpp:61-326
 //   tdx_tool_dinftranslimaccum <- tlaccum()   src/DinfTransLimAccum.cpp:61-372
 //   tdx_tool_dinfdistdown    <- dinfdistdown()  src/DinfDistDown.cpp:66-1060
+//   tdx_tool_dinfdistup      <- dinfdistup()    src/DinfDistUp.cpp:65-1214
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -594,6 +595,65 @@ int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* 
     printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
            writet - begint);
     print_gpu_stats("dinfdistdown", st, ang.info.nx * ang.info.ny);
+    return 0;
+}
+
+// dinfdistup() (src/DinfDistUp.cpp:65-90) and its four tool functions: files in the reference's order (ang, then fel for v / p / s, w for
+// h / p / s when used), each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); slpfile is never read
+int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* rtrfile, int statmethod,
+                        int typemethod, int usew, int concheck, float thresh) {
+    static const char* const banner[4] = {"-h", "-v", "-p", "-s"};
+    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
+    printf("DinfDistUp %s version %s\n", banner[typemethod], TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;   // (v: the weight code is commented out in the reference)
+    Raster ang, fel, w;
+    int rc = load_raster(angfile, tdx::DType::F32, ang);
+    if (rc != TDX_OK) return rc;
+    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
+    if (use_fel) {
+        rc = load_raster(felfile, tdx::DType::F32, fel);
+        if (rc != TDX_OK) return rc;
+        if (!compare_rasters(ang.info, angfile, fel.info, felfile)) return mismatch(felfile);
+    }
+    if (use_w) {
+        rc = load_raster(wfile, tdx::DType::F32, w);
+        if (rc != TDX_OK) return rc;
+        if (!compare_rasters(ang.info, angfile, w.info, wfile)) return mismatch(wfile);
+    }
+    const double readt = now_s();
+    std::vector<float> du(ang.f.size());
+    const float fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            float* d_ang = j.strip<float>(ang.f.data());
+            float* d_fel = use_fel ? j.strip<float>(fel.f.data()) : nullptr;
+            float* d_w = use_w ? j.strip<float>(w.f.data()) : nullptr;
+            float* d_du = j.strip<float>(nullptr);
+            if (!d_ang || (use_fel && !d_fel) || (use_w && !d_w) || !d_du) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
+            const int e = tdx_dinfdistup_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, fel_nd, d_w, w_nd, statmethod,
+                                               typemethod, concheck, thresh, d_du, s);
+            return e != TDX_OK ? e : (j.fetch(du.data(), d_du) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_dinfdistup(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), use_fel ? fel.f.data() : nullptr,
+                            fel_nd, use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, thresh, du.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(rtrfile, tdx::DType::F32, du.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistUp.cpp:321-322)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("dinfdistup", st, ang.info.nx * ang.info.ny);
     return 0;
 }
 

@@ -446,6 +446,26 @@ class StripPipeline:
                                                    _tptr(dd, torch.float32, self.shape, "dd"), C.byref(st)), self.ctx._h)
         return dd, st.as_dict()
 
+    def dinfdistup(self, ang, fel=None, *, stat="ave", kind="h", weights=None, weights_nodata=-9999.0, contcheck=True, thresh=0.0, dx=1.0, dy=1.0,
+                   nodata=-3.402823466e38, fel_nodata=-3.0e38):
+        """du = dinfdistup(ang, fel, w) on this strip (src/DinfDistUp.cpp:65): du float32 (nodata -FLT_MAX)."""
+        from .api import DISTDOWN_KINDS, _distdown_mode
+
+        torch = self.torch
+        sm, tm = _distdown_mode(stat, kind)
+        if tm != DISTDOWN_KINDS["h"] and fel is None:
+            raise ValueError(f"kind {kind!r} needs fel")
+        dxc, dyc = self._cells(dx, dy)
+        du = self.empty(torch.float32)
+        pf = _tptr(fel, torch.float32, self.shape, "fel") if tm != DISTDOWN_KINDS["h"] else None
+        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None and tm != DISTDOWN_KINDS["v"] else None
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_dinfdistup_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
+                                                 C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf, float(fel_nodata), pw, float(weights_nodata),
+                                                 sm, tm, int(bool(contcheck)), float(thresh), _tptr(du, torch.float32, self.shape, "du"), C.byref(st)), self.ctx._h)
+        return du, st.as_dict()
+
     def dinfdecayaccum(self, ang, dm, nodata=-3.402823466e38, dm_nodata=-9999.0, dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
         torch = self.torch
         dxc, dyc = self._cells(dx, dy)

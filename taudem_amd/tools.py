@@ -86,6 +86,12 @@ def dinfdistdown(angfile, felfile, slpfile, wfile, srcfile, dtsfile, statmethod=
                                              int(usew), int(concheck))
 
 
+def dinfdistup(angfile, felfile, slpfile, wfile, rtrfile, statmethod=0, typemethod=0, usew=0, concheck=1, thresh=0.0):
+    """src/DinfDistUp.cpp:65"""
+    return _lib.load().tdx_tool_dinfdistup(_b(angfile), _b(felfile), _b(slpfile), _b(wfile), _b(rtrfile), int(statmethod), int(typemethod), int(usew),
+                                           int(concheck), float(thresh))
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
