@@ -237,6 +237,26 @@ int tdx_dinfdistdown(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny,
                      const double* dxc, const double* dyc, const float* fel, float fel_nodata, const int16_t* src,
                      const float* w, float w_nodata, int statmethod, int typemethod, int contcheck,
                      float* dd, tdx_stats* stats);
+/* distgrid() src/D8HDistToStrm.cpp:57-260 (D8HDistToStrm): horizontal distance along the D8 flow path down to the stream.  Stream cells
+ * are those whose src value (int32, the reference's LONG read) is not src_nodata and is >= thresh - whatever p is there, nodata
+ * included; they get 0.  Every other cell gets dist[j][p] + its receiver's distance, with dist[j][k] = sqrt(d1^2 dxc^2 + d2^2 dyc^2)
+ * of its row j in double, stored as float.  Cells draining off the raster, into a cell without a result or around a cycle get nodata
+ * (-FLT_MAX), as do p == 0 cells that are not stream cells. */
+int tdx_d8hdisttostrm_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* d_src,
+                          int32_t src_nodata, int32_t thresh, const double* dxc, const double* dyc, float* d_dist, tdx_stats* stats);
+int tdx_d8hdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* src,
+                      int32_t src_nodata, int32_t thresh, const double* dxc, const double* dyc, float* dist, tdx_stats* stats);
+/* gagewatershed() src/gagewatershed.cpp:56-360 (GageWatershed): every cell gets the id of the first gauge downstream of it.  Outlets are
+ * HOST arrays of global column / row (the reference's geoToGlobalXY) and ids (NULL: index + 1); those off the raster are skipped and
+ * the first one on a cell wins.  gw int32, nodata MISSINGLONG (-2147483647).  placed / iddown: HOST arrays of n_outlets - placed[i] = 1
+ * where outlet i labels its cell, iddown[i] the `-id` file's column: for the placed gauge G with id ids[i] whose downstream neighbour D
+ * lies in the raster and is labelled, iddown[first j with ids[j] == ids[i]] = gw(D); -1 elsewhere. */
+int tdx_gagewatershed_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* outlet_x,
+                          const int32_t* outlet_y, const int32_t* ids, int64_t n_outlets, int32_t* d_gw, int32_t* placed,
+                          int32_t* iddown, tdx_stats* stats);
+int tdx_gagewatershed(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* outlet_x,
+                      const int32_t* outlet_y, const int32_t* ids, int64_t n_outlets, int32_t* gw, int32_t* placed, int32_t* iddown,
+                      tdx_stats* stats);
 /* dinfdistup() src/DinfDistUp.cpp:65-1214: distance from each cell up to the ridge along the D-infinity flow, over the neighbours that
  * drain into it (AreaDinf's dependency graph, no outlets).  typemethod 0 h (horizontal, hdisttoridgegrd :94), 1 v (vertical rise,
  * vrisetoridgegrd :356), 2 p (Pythagorean, sqrt(h^2 + v^2), pdisttoridgegrd :599), 3 s (surface: sqrt(dz^2 + dh^2) per step,
@@ -384,6 +404,14 @@ int tdx_dinfdistdown_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang,
 int tdx_dinfdistup_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                          const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const float* d_w, float w_nodata,
                          int statmethod, int typemethod, int contcheck, float thresh, float* d_du, tdx_stats* stats);
+/* the reverse D8 tools on strips (dxc / dyc: per-row cell sizes of the ny_local + 2 strip rows; outlet_row: array row of the strip,
+ * outside the owned rows = on another rank).  placed / iddown come back reduced over the ranks: the same on every rank. */
+int tdx_d8hdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata,
+                            const int32_t* d_src, int32_t src_nodata, int32_t thresh, const double* dxc, const double* dyc,
+                            float* d_dist, tdx_stats* stats);
+int tdx_gagewatershed_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata,
+                            const int32_t* outlet_x, const int32_t* outlet_row, const int32_t* ids, int64_t n_outlets, int32_t* d_gw,
+                            int32_t* placed, int32_t* iddown, tdx_stats* stats);
 /* the limited D-infinity accumulations on strips (outlet_row: array row of the strip, as for tdx_areadinf_strip) */
 int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg,
@@ -476,6 +504,12 @@ int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* 
  *                int concheck, float thresh)                                  src/DinfDistUp.cpp:65-66 (slpfile is never read) */
 int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* slpfile, const char* wfile, const char* rtrfile,
                         int statmethod, int typemethod, int usew, int concheck, float thresh);
+/* int distgrid(char* pfile, char* srcfile, char* distfile, int thresh)          src/D8HDistToStrm.cpp:57 */
+int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh);
+/* int gagewatershed(char* pfile, char* wfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* idfile, int writeid,
+ *                   int writeupid, char* upidfile)                            src/gagewatershed.cpp:56 (writeupid = 1 is refused) */
+int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* datasrc, const char* lyrname, int uselyrname, int lyrno,
+                           const char* idfile, int writeid, int writeupid, const char* upidfile);
 /* int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile,
  *              char* dgfile, int useOutlets, int contcheck, float cSol)          src/DinfConcLimAccum.cpp:61-62 */
 int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* lyrname,

@@ -56,6 +56,14 @@ timed("dinfdistdown_ave_h", lambda: ctx.dinfdistdown(ang, src, None, stat="ave",
 timed("dinfdistup_ave_h", lambda: ctx.dinfdistup(ang, None, stat="ave", kind="h", dx=30.0, dy=30.0, stats=True))
 timed("dinfdistup_ave_v", lambda: ctx.dinfdistup(ang, fel, stat="ave", kind="v", dx=30.0, dy=30.0, stats=True))
 timed("dinfdistup_ave_p", lambda: ctx.dinfdistup(ang, fel, stat="ave", kind="p", dx=30.0, dy=30.0, stats=True))
+if not only or only & {"d8hdisttostrm", "gagewatershed"}:
+    ad8 = ctx.aread8(p)
+    src8 = (ad8 >= torch.quantile(ad8[::16, ::16].flatten(), 0.98)).to(torch.int32)
+    del ad8
+    gy, gx = torch.nonzero(src8[::128, ::128], as_tuple=True)   # ~1 gauge per 128 x 128 block that has a stream cell at its corner
+    gauges = ((gx * 128).cpu().numpy().astype(np.int32), (gy * 128).cpu().numpy().astype(np.int32))
+timed("d8hdisttostrm", lambda: ctx.d8hdisttostrm(p, src8, dx=30.0, dy=30.0, stats=True))
+timed("gagewatershed", lambda: ctx.gagewatershed(p, gauges, stats=True))
 timed("dinfconclimaccum", lambda: ctx.dinfconclimaccum(ang, w2, dg16, w + 0.5, dx=30.0, dy=30.0, stats=True))
 timed("dinftranslimaccum_cs", lambda: ctx.dinftranslimaccum(ang, w, 50.0 * w2, cs=w2, dx=30.0, dy=30.0, stats=True))
 print(json.dumps({"metric": "ms per call", "size": n, "n_gpus": 1, "ms": res,

@@ -159,6 +159,14 @@ _SIGNATURES = {
     "tdx_dinfdistdown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tdx_tool_dinfdistdown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, w, w_nodata, statmethod, typemethod, contcheck, thresh, du, stats
+    "tdx_d8hdisttostrm_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "tdx_d8hdisttostrm": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "tdx_d8hdisttostrm_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "tdx_tool_d8hdisttostrm": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
+    "tdx_gagewatershed_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "tdx_gagewatershed": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "tdx_gagewatershed_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "tdx_tool_gagewatershed": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
     "tdx_dinfdistup_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),

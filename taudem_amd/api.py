@@ -368,6 +368,51 @@ class Context:
                                                    float(fel_nodata), ps, pw, float(weights_nodata), sm, tm, int(bool(contcheck)), po, C.byref(st)), self._h)
         return (dd, st.as_dict()) if stats else dd
 
+    def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=int(P_NODATA), src_nodata=-2147483647, stats=False):
+        """dist = distgrid(p, src)  (src/D8HDistToStrm.cpp:57): horizontal distance along the D8 flow path down to the stream.
+
+        Stream cells are those where src (int32, the reference's LONG read) is not src_nodata and is >= thresh, whatever p is there;
+        they get 0.  dist float32, nodata -FLT_MAX (off the raster, into a cell without a result, around a cycle)."""
+        ny, nx = p.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        dist = self._out(p, np.float32, (ny, nx))
+        pp, dev = self._ptr(p, np.int16, name="p")
+        ps, sdev = self._ptr(src, np.int32, (ny, nx), "src")
+        po, _ = self._ptr(dist, np.float32, (ny, nx), "dist")
+        if sdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(p, src)
+        check(self._pick(dev, "tdx_d8hdisttostrm")(self._h, pp, nx, ny, int(nodata), ps, int(src_nodata), int(thresh), C.c_void_p(dxc.ctypes.data),
+                                                   C.c_void_p(dyc.ctypes.data), po, C.byref(st)), self._h)
+        return (dist, st.as_dict()) if stats else dist
+
+    def gagewatershed(self, p, outlets, *, nodata=int(P_NODATA), stats=False):
+        """gw, id_table = gagewatershed(p, outlets)  (src/gagewatershed.cpp:56): every cell gets the id of the first gauge downstream of it.
+
+        outlets: (columns, rows[, ids]) global indices (ids default to 1..n, as the outlet reader's); outlets off the raster are skipped and
+        the first one on a cell wins.  gw int32, nodata -2147483647.  id_table: int32 array (k, 2) of the `-id` file's lines (id, iddown)
+        for the k placed outlets in input order; iddown is -1 where the gauge's downstream neighbour is off the raster or unlabelled."""
+        ny, nx = p.shape
+        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32)).reshape(-1)
+        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32)).reshape(-1)
+        ids = np.arange(1, ox.size + 1, dtype=np.int32) if len(outlets) < 3 else np.ascontiguousarray(np.asarray(outlets[2], dtype=np.int32)).reshape(-1)
+        if ox.shape != oy.shape or ox.shape != ids.shape:
+            raise ValueError("outlets: need equal-length 1-D arrays (columns, rows[, ids])")
+        gw = self._out(p, np.int32, (ny, nx))
+        pp, dev = self._ptr(p, np.int16, name="p")
+        pg, _ = self._ptr(gw, np.int32, (ny, nx), "gw")
+        placed = np.zeros(ox.size + 1, np.int32)
+        iddown = np.zeros(ox.size + 1, np.int32)
+        st = TdxStats()
+        self._sync_torch(p)
+        check(self._pick(dev, "tdx_gagewatershed")(self._h, pp, nx, ny, int(nodata), C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data),
+                                                   C.c_void_p(ids.ctypes.data), int(ox.size), pg, C.c_void_p(placed.ctypes.data),
+                                                   C.c_void_p(iddown.ctypes.data), C.byref(st)), self._h)
+        keep = placed[:ox.size] > 0
+        table = np.stack([ids[keep], iddown[:ox.size][keep]], axis=1).astype(np.int32)
+        return (gw, table, st.as_dict()) if stats else (gw, table)
+
     def dinfdistup(self, ang, fel=None, *, stat="ave", kind="h", weights=None, weights_nodata=-9999.0, contcheck=True, thresh=0.0, dx=1.0, dy=1.0,
                    nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
         """du = dinfdistup(ang, fel, w)  (src/DinfDistUp.cpp:65): distance from each cell up to the ridge over the neighbours that drain into it.

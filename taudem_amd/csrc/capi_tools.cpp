@@ -12,6 +12,8 @@
 //   tdx_tool_dinftranslimaccum <- tlaccum()   src/DinfTransLimAccum.cpp:61-372
 //   tdx_tool_dinfdistdown    <- dinfdistdown()  src/DinfDistDown.cpp:66-1060
 //   tdx_tool_dinfdistup      <- dinfdistup()    src/DinfDistUp.cpp:65-1214
+//   tdx_tool_d8hdisttostrm   <- distgrid()      src/D8HDistToStrm.cpp:57-260
+//   tdx_tool_gagewatershed   <- gagewatershed() src/gagewatershed.cpp:56-360
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -157,7 +159,7 @@ struct CtxGuard {
 };
 
 // outlets: readoutlets + geoToGlobalXY (src/aread8.cpp:114-136,179-189)
-int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, std::vector<int32_t>& ox, std::vector<int32_t>& oy) {
+int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, std::vector<int32_t>& ox, std::vector<int32_t>& oy, std::vector<int32_t>* ids = nullptr) {
     std::vector<double> x, y; std::vector<int> id; std::string err;
     if (!tdx::read_outlets(datasrc, x, y, id, err)) {
         printf("Error Opening OGR Data Source .\n");
@@ -173,6 +175,7 @@ int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, std::vector<int
         tdx::geo_to_global_xy(x[i], y[i], ri.xleftedge, ri.ytopedge, ri.dlon, ri.dlat, gx, gy);
         ox[i] = gx; oy[i] = gy;
     }
+    if (ids) ids->assign(id.begin(), id.end());
     return TDX_OK;
 }
 
@@ -654,6 +657,111 @@ int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* /*
     printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
            writet - begint);
     print_gpu_stats("dinfdistup", st, ang.info.nx * ang.info.ny);
+    return 0;
+}
+
+// distgrid() (src/D8HDistToStrm.cpp:57-260): p, then src read as LONG (File sizes do not match + MPI_Abort(MCW, 5))
+int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh) {
+    printf("D8HDistToStrm version %s\n", TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    Raster p, src;
+    int rc = load_raster(pfile, tdx::DType::I16, p);
+    if (rc != TDX_OK) return rc;
+    rc = load_raster(srcfile, tdx::DType::I32, src);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(p.info, pfile, src.info, srcfile)) { printf("File sizes do not match\n%s\n", srcfile); fflush(stdout); return TDX_ERR_OUTLETS; }
+    const double readt = now_s();
+    std::vector<float> dist(p.s.size());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t s_nd = (int32_t)src.info.nodata;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.strip<int16_t>(p.s.data());
+            int32_t* d_src = j.strip<int32_t>(src.l.data());
+            float* d_dist = j.strip<float>(nullptr);
+            if (!d_p || !d_src || !d_dist) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(p.info.dxc), dys = j.rows_of(p.info.dyc);
+            const int e = tdx_d8hdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_src, s_nd, thresh, dxs.data(), dys.data(), d_dist, s);
+            return e != TDX_OK ? e : (j.fetch(dist.data(), d_dist) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_d8hdisttostrm(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, src.l.data(), s_nd, thresh, p.info.dxc.data(), p.info.dyc.data(), dist.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(distfile, tdx::DType::F32, dist.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8HDistToStrm.cpp:223-225)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("d8hdisttostrm", st, p.info.nx * p.info.ny);
+    return 0;
+}
+
+// gagewatershed() (src/gagewatershed.cpp:56-360).  -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  -upid is
+// refused: the reference appends a line per visit of a nodata neighbour in queue order (:246-253), which depends on the schedule.
+int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/,
+                           const char* idfile, int writeid, int writeupid, const char* /*upidfile*/) {
+    printf("Gage Watershed version %s\n", TDVERSION);
+    fflush(stdout);
+    if (writeupid == 1) {
+        fprintf(stderr, "taudem_amd: gagewatershed -upid is not supported (the reference's upstream-id file depends on its queue order)\n");
+        g_tdx_thread_error = "gagewatershed: -upid is not supported";
+        return TDX_ERR_ARG;
+    }
+    const double begint = now_s();
+    Raster p;
+    int rc = load_raster(pfile, tdx::DType::I16, p);
+    if (rc != TDX_OK) return rc;
+    std::vector<int32_t> ox, oy, ids;
+    rc = load_outlets(datasrc, p.info, ox, oy, &ids);
+    if (rc != TDX_OK) return rc;
+    const int64_t nout = int64_t(ox.size());
+    const double readt = now_s();
+    std::vector<int32_t> gw(p.s.size()), placed(size_t(nout) + 1), iddown(size_t(nout) + 1);
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.strip<int16_t>(p.s.data());
+            int32_t* d_gw = j.strip<int32_t>(nullptr);
+            if (!d_p || !d_gw) return TDX_ERR_NOMEM;
+            const std::vector<int32_t> rows = j.local_rows(oy);
+            std::vector<int32_t> pl(size_t(nout) + 1), dn(size_t(nout) + 1);   // (every rank gets the reduced table)
+            const int e = tdx_gagewatershed_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, ox.data(), rows.data(), ids.data(), nout, d_gw, pl.data(), dn.data(), s);
+            if (e != TDX_OK) return e;
+            if (j.rank == 0) { placed = pl; iddown = dn; }
+            return j.fetch(gw.data(), d_gw) ? TDX_OK : TDX_ERR_HIP;
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_gagewatershed(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, ox.data(), oy.data(), ids.data(), nout, gw.data(), placed.data(), iddown.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    if (writeid == 1) {   // src/gagewatershed.cpp:327-341
+        FILE* f = fopen(idfile, "w");
+        if (!f) { printf("Error opening file %s.\n", idfile); fflush(stdout); return TDX_ERR_FILE; }
+        fprintf(f, "id iddown\n");
+        for (int64_t i = 0; i < nout; i++)
+            if (placed[size_t(i)] > 0) fprintf(f, "%d %d\n", ids[size_t(i)], iddown[size_t(i)]);
+        fclose(f);
+    }
+    rc = save_raster(wfile, tdx::DType::I32, gw.data(), p.info, -2147483647.0);   // MISSINGLONG (src/gagewatershed.cpp:346-348)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Size: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("gagewatershed", st, p.info.nx * p.info.ny);
     return 0;
 }
 

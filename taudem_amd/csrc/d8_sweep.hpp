@@ -517,8 +517,8 @@ __device__ __forceinline__ int sweep_tile_rev(const Alg& alg, const tilek::TileG
             const int gyc = gy >= g.ny ? g.ny - 1 : gy;
             const size_t idx = size_t(gyc) * size_t(g.nx) + size_t(gx >= g.nx ? g.nx - 1 : gx);
             si[r] = A.info[idx];
-            sa[r] = A.aux[idx];
-            srow[r] = A.rows[gyc];
+            if constexpr (Alg::HAS_AUX) sa[r] = A.aux[idx]; else sa[r] = Aux{};      // (the D8 reverse policies: d8rev.hip)
+            if constexpr (Alg::HAS_ROWS) srow[r] = A.rows[gyc]; else srow[r] = 0.;
         }
 #pragma unroll
         for (int i = 0; i < NSTAGE; i++) {

@@ -466,6 +466,37 @@ class StripPipeline:
                                                  sm, tm, int(bool(contcheck)), float(thresh), _tptr(du, torch.float32, self.shape, "du"), C.byref(st)), self.ctx._h)
         return du, st.as_dict()
 
+    def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=-32768, src_nodata=-2147483647):
+        """dist = distgrid(p, src) on this strip (src/D8HDistToStrm.cpp:57): src int32, dist float32 (nodata -FLT_MAX)."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        dist = self.empty(torch.float32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_d8hdisttostrm_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                    _tptr(src, torch.int32, self.shape, "src"), int(src_nodata), int(thresh), C.c_void_p(dxc.ctypes.data),
+                                                    C.c_void_p(dyc.ctypes.data), _tptr(dist, torch.float32, self.shape, "dist"), C.byref(st)), self.ctx._h)
+        return dist, st.as_dict()
+
+    def gagewatershed(self, p, outlets, *, nodata=-32768):
+        """gw, id_table = gagewatershed(p, outlets) on this strip (src/gagewatershed.cpp:56).  outlets: (columns, STRIP-ARRAY rows, ids) of ALL
+        outlets (local_outlets(); those outside the owned rows are other ranks'); id_table as Context.gagewatershed's, the same on every rank."""
+        torch = self.torch
+        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32)).reshape(-1)
+        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32)).reshape(-1)
+        ids = np.ascontiguousarray(np.asarray(outlets[2], dtype=np.int32)).reshape(-1)
+        gw = self.empty(torch.int32)
+        placed = np.zeros(ox.size + 1, np.int32)
+        iddown = np.zeros(ox.size + 1, np.int32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_gagewatershed_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                    C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data), C.c_void_p(ids.ctypes.data), int(ox.size),
+                                                    _tptr(gw, torch.int32, self.shape, "gw"), C.c_void_p(placed.ctypes.data), C.c_void_p(iddown.ctypes.data),
+                                                    C.byref(st)), self.ctx._h)
+        keep = placed[:ox.size] > 0
+        return gw, np.stack([ids[keep], iddown[:ox.size][keep]], axis=1).astype(np.int32), st.as_dict()
+
     def dinfdecayaccum(self, ang, dm, nodata=-3.402823466e38, dm_nodata=-9999.0, dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
         torch = self.torch
         dxc, dyc = self._cells(dx, dy)

@@ -92,6 +92,20 @@ def dinfdistup(angfile, felfile, slpfile, wfile, rtrfile, statmethod=0, typemeth
                                            int(concheck), float(thresh))
 
 
+def distgrid(pfile, srcfile, distfile, thresh=1):
+    """src/D8HDistToStrm.cpp:57 (D8HDistToStrm)"""
+    return _lib.load().tdx_tool_d8hdisttostrm(_b(pfile), _b(srcfile), _b(distfile), int(thresh))
+
+
+d8hdisttostrm = distgrid
+
+
+def gagewatershed(pfile, wfile, datasrc, lyrname="", uselyrname=0, lyrno=0, idfile="", writeid=0, writeupid=0, upidfile=""):
+    """src/gagewatershed.cpp:56 (writeupid = 1 is refused)"""
+    return _lib.load().tdx_tool_gagewatershed(_b(pfile), _b(wfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(idfile), int(writeid),
+                                              int(writeupid), _b(upidfile))
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
