@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Benchmark of the PitRemove -> D8FlowDir -> AreaD8 pipeline (BASELINE.json metric: Mcells/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size n | --nx X --ny Y] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size n | --nx X --ny Y] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs when `--dump-outputs` is given and prints its line; what
+takes runs of its own (the roofline pass, the CPU baseline, the other configurations' legs below) comes with `--full` only.
 
 One "step" = one pass of the three-stage pipeline over one synthetic fractal DEM that is already
 resident in HBM (generated on the device by tdx_synth_dem_dev).
@@ -16,7 +19,9 @@ resident in HBM (generated on the device by tdx_synth_dem_dev).
           functional check only).
 --nx/--ny set the TOTAL raster explicitly (ny rows are split over the ranks).  Rank 0 prints ONE JSON line.
 
-Beside the pipeline, the N = 1 line carries (outside the timed region, one step each, `--no-extras` skips them)
+With `--full`, after the timed steps: one more step with every launch of the dominant kernel timed (the `roofline` object, all N), the
+reference's own tools on a `--cpu-sample` edge sample (`cpu_baseline`, N = 1), and in the N = 1 line at the default size (outside the
+timed region, one step each, `--no-extras` skips them)
   config3        BASELINE.json configs[2]: DinfFlowDir + AreaDinf on a 32768 x 32768 DEM (ms, Mcells/s, the accumulation sweeps' roofline)
   config4_strip  BASELINE.json configs[3] as ONE GPU sees it: the pipeline on a 65536 x 8192 strip (no neighbours)
   config5_strip  BASELINE.json configs[4] as ONE GPU sees it: DinfDecayAccum with weights, decay multipliers and 64 outlets on a
@@ -88,9 +93,11 @@ def parse():
     ap.add_argument("--nx", type=int, default=0, help="columns of the whole raster")
     ap.add_argument("--ny", type=int, default=0, help="rows of the whole raster (split over the ranks)")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="edge length of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also: the roofline pass, the CPU baseline and (N = 1, default size) "
+                    "the other configurations' legs")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="--full: edge length of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--workload", choices=("d8", "decay"), default="d8", help="d8: PitRemove->D8FlowDir->AreaD8 (the metric); decay: DinfDecayAccum -wg -o on strips")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the config3 / config5_strip legs after the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N = 1: skip the config3 / config5_strip legs after the timed region")
     ap.add_argument("--in-process", action="store_true", help="N > 1: rank threads of this process (tdx_group) instead of one process per rank")
     ap.add_argument("--segments", type=int, default=0, choices=(0, 1, 2), help="--in-process: segment trace of the timed steps (2: one rank on the device at a "
                     "time) -> projected_ngpu_ms in the line (taudem_amd.distributed.project_critical_path)")
@@ -728,13 +735,15 @@ def main():
     if args.dump_outputs:   # before the pass below writes the same buffers again
         own = slice(None) if comm is None else slice(1, nyl + 1)
         dump_outputs(torch, args.dump_outputs, {"fel": fel[own], "p": p[own], "sd8": sd8[own], "ad8": ad8[own]}, rank, world)
-    # One more pass of the same step, outside the timed region, with every launch of the tile-relaxation kernel
+    # --full: one more pass of the same step, outside the timed region, with every launch of the tile-relaxation kernel
     # bracketed by HIP events on the library's stream (two event records per launch would cost ~5 % inside it):
     # the dominant kernel's average launch duration for the roofline object.
-    ctx.set_option("kernel_timing", 1)
-    prof = step()
-    ctx.set_option("kernel_timing", 0)
-    barrier()
+    prof = None
+    if args.full:
+        ctx.set_option("kernel_timing", 1)
+        prof = step()
+        ctx.set_option("kernel_timing", 0)
+        barrier()
     if dist.is_initialized():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -753,22 +762,28 @@ def main():
             for name in ("stencil", "relax", "bfs", "flatdir", "accum", "misc"):
                 klass[name] = klass.get(name, 0.0) + a["ms_" + name]
                 klass["n_" + name] = klass.get("n_" + name, 0) + a["launches_" + name]
-        # per-stage view of the dominant kernel class: the tile-relaxation kernel of pitremove ("relax") and of
-        # flat resolution ("bfs") are the same kernel template (tilek::relax_kernel) with different operators
-        per_stage = {"pitremove/relax_kernel<PitOp>": (prof[0]["ms_tilek"], prof[0]["launches_tilek"], "pitremove"),
-                     "d8flowdir/relax_kernel<LevelOp>": (prof[1]["ms_tilek"], prof[1]["launches_tilek"], "d8flowdir"),
-                     "aread8/tile kernels": (prof[2]["ms_stencil"], prof[2]["launches_stencil"], "aread8"),
-                     "aread8/big-cell evaluation": (prof[2]["ms_misc"], prof[2]["launches_misc"], "aread8")}
-        dom = max(per_stage, key=lambda k: per_stage[k][0])
-        dms, dlaunch, stage = per_stage[dom]
-        launches = max(1, dlaunch)
-        avg_ms = dms / launches
-        bytes_per_launch = BYTES_PER_CELL[stage] * cells / launches
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        roofline = {}
+        if prof is not None:
+            # per-stage view of the dominant kernel class: the tile-relaxation kernel of pitremove ("relax") and of
+            # flat resolution ("bfs") are the same kernel template (tilek::relax_kernel) with different operators
+            per_stage = {"pitremove/relax_kernel<PitOp>": (prof[0]["ms_tilek"], prof[0]["launches_tilek"], "pitremove"),
+                         "d8flowdir/relax_kernel<LevelOp>": (prof[1]["ms_tilek"], prof[1]["launches_tilek"], "d8flowdir"),
+                         "aread8/tile kernels": (prof[2]["ms_stencil"], prof[2]["launches_stencil"], "aread8"),
+                         "aread8/big-cell evaluation": (prof[2]["ms_misc"], prof[2]["launches_misc"], "aread8")}
+            dom = max(per_stage, key=lambda k: per_stage[k][0])
+            dms, dlaunch, stage = per_stage[dom]
+            launches = max(1, dlaunch)
+            avg_ms = dms / launches
+            bytes_per_launch = BYTES_PER_CELL[stage] * cells / launches
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            traffic, traffic_note = pmc_traffic("LevelOp" if "LevelOp" in dom else ("PitOp" if "PitOp" in dom else "ad8_tile"))
+            roofline["roofline"] = {"bound": "hbm", "kernel": dom, "stage": stage, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note, "avg_launch_ms": avg_ms,
+                                    "launches_per_step": launches, "algorithmic_bytes_per_launch": bytes_per_launch,
+                                    "note": "dependency-driven sweep: bound by (critical path in tiles) x launch, not by bandwidth (SURVEY.md 8d)"}
         # the streaming 3x3 stencil that the 40 %-of-HBM target of BASELINE.json is about: D8 slope pass
         slope_ms = acc[1]["ms_stencil"] / max(1, acc[1]["launches_stencil"])
         slope_gbs = 10.0 * cells / (slope_ms * 1e-3) / 1e9 if slope_ms > 0 else 0.0
-        traffic, traffic_note = pmc_traffic("LevelOp" if "LevelOp" in dom else ("PitOp" if "PitOp" in dom else "ad8_tile"))
         out = {
             "metric": "Mcells/s (PitRemove->D8FlowDir->AreaD8 pipeline)",
             "value": value,
@@ -792,10 +807,7 @@ def main():
             "stage_mcells_per_s": {k: total_cells / (v / args.steps) / 1e3 for k, v in stage_ms.items() if v > 0},
             "kernel_class_ms_per_step": {k: klass[k] / args.steps for k in ("stencil", "relax", "bfs", "flatdir", "accum", "misc")},
             "kernel_class_launches_per_step": {k: klass["n_" + k] / args.steps for k in ("stencil", "relax", "bfs", "flatdir", "accum", "misc")},
-            "roofline": {"bound": "hbm", "kernel": dom, "stage": stage, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note, "avg_launch_ms": avg_ms, "launches_per_step": launches,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "note": "dependency-driven sweep: bound by (critical path in tiles) x launch, not by bandwidth (SURVEY.md 8d)"},
+            **roofline,
             "roofline_streaming_stencil": {"kernel": "d8_slope_kernel", "algorithmic_bytes_per_cell": 10, "avg_launch_ms": slope_ms,
                                            "achieved": slope_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": slope_gbs / HBM_PEAK_GBS},
             "flats": {"initial": acc[1]["flats_initial"], "left": acc[1]["flats_left"], "iterations": acc[1]["flat_iterations"],
@@ -807,9 +819,9 @@ def main():
             out["comm"] = {"transport": getattr(comm, "backend", backend),
                            "exchanges_per_step": {"pitremove": last[0][0], "d8flowdir": last[1][0], "aread8": last[2][0]},
                            "allreduces_per_step": {"pitremove": last[0][1], "d8flowdir": last[1][1], "aread8": last[2][1]}}
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.seed)
-        if world == 1 and comm is None and not args.no_extras and not (args.size or args.nx or args.ny):
+        if args.full and world == 1 and comm is None and not args.no_extras and not (args.size or args.nx or args.ny):
             # the other single-GPU configurations of BASELINE.json, one step each, outside the timed region (an error in one of them must
             # not cost the line of record)
             del dem, fel, p, sd8, ad8
