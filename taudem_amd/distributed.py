@@ -511,3 +511,72 @@ class StripPipeline:
                                                      _tptr(dsca, torch.float32, self.shape, "dsca"), C.byref(st)), self.ctx._h)
         del keep
         return dsca, st.as_dict()
+
+    def d8flowpathextremeup(self, p, sa, nodata=-32768, usemax=True, contcheck=True, outlets=None):
+        """ssa = d8flowpathextremeup(p, sa) on this strip (src/D8flowpathextremeup.cpp:58): sa float32, ssa float32 (nodata -FLT_MAX).
+        outlets: (columns, STRIP-ARRAY rows) as for aread8."""
+        torch = self.torch
+        ssa = self.empty(torch.float32)
+        ox, oy, no, keep = self._outlets(outlets)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_d8flowpathextremeup_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                          _tptr(sa, torch.float32, self.shape, "sa"), int(bool(usemax)), int(bool(contcheck)), ox, oy, no,
+                                                          _tptr(ssa, torch.float32, self.shape, "ssa"), C.byref(st)), self.ctx._h)
+        del keep
+        return ssa, st.as_dict()
+
+    def gridnet(self, p, nodata=-32768, dx=1.0, dy=1.0, mask=None, thresh=0, outlets=None):
+        """plen, tlen, gord = gridnet(p) on this strip (src/gridnet.cpp:54): mask an optional int32 strip array (the library fills its halo
+        rows); outlets: (columns, STRIP-ARRAY rows) as for aread8."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        plen, tlen, gord = self.empty(torch.float32), self.empty(torch.float32), self.empty(torch.int16)
+        pm = _tptr(mask, torch.int32, self.shape, "mask") if mask is not None else None
+        ox, oy, no, keep = self._outlets(outlets)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_gridnet_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                              C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pm, int(thresh), ox, oy, no,
+                                              _tptr(plen, torch.float32, self.shape, "plen"), _tptr(tlen, torch.float32, self.shape, "tlen"),
+                                              _tptr(gord, torch.int16, self.shape, "gord"), C.byref(st)), self.ctx._h)
+        del keep
+        return plen, tlen, gord, st.as_dict()
+
+    def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=-3.402823466e38, dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
+                         outlets=None):
+        """ctpt = dsllArea(ang, dm, dg, q) on this strip (src/DinfConcLimAccum.cpp:61): dg int16, ctpt float32 (nodata -FLT_MAX)."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        ctpt = self.empty(torch.float32)
+        ox, oy, no, keep = self._outlets(outlets)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_dinfconclimaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
+                                                       C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(dm, torch.float32, self.shape, "dm"),
+                                                       float(dm_nodata), _tptr(dg, torch.int16, self.shape, "dg"), _tptr(q, torch.float32, self.shape, "q"),
+                                                       float(q_nodata), float(csol), int(bool(contcheck)), ox, oy, no,
+                                                       _tptr(ctpt, torch.float32, self.shape, "ctpt"), C.byref(st)), self.ctx._h)
+        del keep
+        return ctpt, st.as_dict()
+
+    def dinftranslimaccum(self, ang, tsup, tc, cs=None, nodata=-3.402823466e38, tsup_nodata=-9999.0, tc_nodata=-9999.0, cs_nodata=-9999.0, dx=1.0, dy=1.0,
+                          contcheck=True, outlets=None):
+        """tla, tdep, ctpt = tlaccum(ang, tsup, tc[, cs]) on this strip (src/DinfTransLimAccum.cpp:61): float32, nodata -FLT_MAX; ctpt is None
+        without cs."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        tla, tdep = self.empty(torch.float32), self.empty(torch.float32)
+        ctpt = self.empty(torch.float32) if cs is not None else None
+        pc = _tptr(cs, torch.float32, self.shape, "cs") if cs is not None else None
+        po = _tptr(ctpt, torch.float32, self.shape, "ctpt") if cs is not None else None
+        ox, oy, no, keep = self._outlets(outlets)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_dinftranslimaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
+                                                        C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(tsup, torch.float32, self.shape, "tsup"),
+                                                        float(tsup_nodata), _tptr(tc, torch.float32, self.shape, "tc"), float(tc_nodata), pc, float(cs_nodata),
+                                                        int(bool(contcheck)), ox, oy, no, _tptr(tla, torch.float32, self.shape, "tla"),
+                                                        _tptr(tdep, torch.float32, self.shape, "tdep"), po, C.byref(st)), self.ctx._h)
+        del keep
+        return tla, tdep, ctpt, st.as_dict()

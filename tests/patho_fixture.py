@@ -1,0 +1,44 @@
+"""tests/golden/patho_<case>.npz (tests/golden/make_golden_pathological.py) as the inputs and expected rasters of tests/downstream.py."""
+import os
+
+import numpy as np
+
+import downstream as D
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DX = DY = 30.0
+UPSTREAM = ("fel", "p", "sd8", "ang", "slp", "ad8", "ad8_nc", "sca", "sca_nc")
+
+
+def names():
+    return sorted(f[len("patho_"):-len(".npz")] for f in os.listdir(os.path.join(HERE, "golden")) if f.startswith("patho_") and f.endswith(".npz"))
+
+
+def load(name):
+    g = np.load(os.path.join(HERE, "golden", f"patho_{name}.npz"), allow_pickle=False)
+    return {k: g[k] for k in g.files}
+
+
+def inputs(g):
+    """The downstream tools' inputs of the fixture: the reference's directions and the recorded extra inputs."""
+    inp = {k: g[k] for k in ("fel", "p", "sd8", "ang", "slp")}
+    inp["ad8"], inp["sca"] = g["ad8_nc"], g["sca_nc"]
+    inp.update({k[3:]: g[k] for k in g if k.startswith("in_") and k not in ("in_outlets", "in_gauges")})
+    inp["outlets"] = tuple(g["in_outlets"])
+    inp["gauges"] = tuple(g["in_gauges"])
+    return inp
+
+
+def expected(g):
+    """{key: raster} of the reference in the keys of downstream.reference (the -id text under gw_id)."""
+    out = {k: g[k] for k in g if not k.startswith("in_") and k not in UPSTREAM and k not in ("dem", "index", "gw_id")}
+    out["gw_id"] = str(g["gw_id"])
+    return out
+
+
+def restated(R, g):
+    return D.reference(R, inputs(g), DX, DY, int(g["index"]))
+
+
+def gpu(ctx, g):
+    return D.single(ctx, inputs(g), DX, DY, int(g["index"]))

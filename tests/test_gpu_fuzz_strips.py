@@ -112,3 +112,58 @@ def _fuzz(seed, oracle, monkeypatch, case, dx, dy, label):
                      ("dsca_o", d_o), ("dep", dep_o), ("racc", racc_o), ("dmax", dmax_o)):
         got = np.concatenate([r[key] for r in res], axis=0)
         assert bits_equal(got, ref), describe_diff(got, ref, f"{what}: {key}")
+
+
+# Every tool downstream of the directions under the random cut (tests/downstream.py: the strip entry points of DinfUpDependence,
+# DinfRevAccum, DinfDecayAccum, DinfConcLimAccum, DinfTransLimAccum, DinfDistDown, DinfDistUp, D8HDistToStrm, GageWatershed, GridNet and
+# D8FlowPathExtremeUp, plus the upstream strip tools), fed the oracle's directions of the global raster and held to the restatements of the
+# global rasters and global per-row sizes; gauges and outlets on the cut rows, every rank's -id table equal to the restatement's -id text.
+# Seeds 200 + i: other shapes and cuts than the seeds above; the distance modes rotate with i, every (stat, kind) within 12 seeds; cell
+# sizes rotate through constant, `wild` and geographic `band` rows.
+@pytest.fixture(scope="module")
+def restate_downstream(tmp_path_factory, oracle):
+    import downstream as D
+
+    return D.Restate(tmp_path_factory.mktemp("downstream"), oracle)
+
+
+@pytest.mark.parametrize("seed", range(int(os.environ.get("TDX_FUZZ_SEEDS", "32"))))
+def test_random_cut_downstream_tools(seed, oracle, restate_downstream, monkeypatch):
+    import torch
+
+    import downstream as D
+    from cellsizes import rows
+    from taudem_amd.distributed import StripGroup, StripPipeline, partition_rows, strip_rows
+
+    ny, nx, world, holes, thr, eager, rng = _case(200 + seed)
+    dx, dy = [(30.0, 25.0), rows("wild", ny, seed=seed), rows("band", ny)][seed % 3]
+    dem = oracle.synth_dem((ny, nx), 500 + 200 + seed)
+    for _ in range(holes):
+        y0, x0 = int(rng.integers(0, ny - 5)), int(rng.integers(0, nx - 5))
+        dem[y0:y0 + int(rng.integers(2, ny // 3 + 3)), x0:x0 + int(rng.integers(2, nx // 3 + 3))] = -9999.0
+    parts = partition_rows(ny, world)
+    cut = sorted({y for y0, y1 in parts for y in (y0 - 1, y0, y1 - 1, y1) if 0 <= y < ny})
+    inp = D.derive(oracle, dem, dx, dy, 3000 + seed, cut_rows=cut)
+    ref = D.reference(restate_downstream, inp, dx, dy, seed)
+    monkeypatch.setenv("TDX_AD8_BIG_THRESHOLD", str(thr))
+    monkeypatch.setenv("TDX_SWEEP_EAGER_ROUNDS", str(eager))
+    monkeypatch.setenv("TDX_REACH_EAGER_ROUNDS", str(eager))
+    monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
+    with StripGroup(world, nx, [0] * world) as grp:
+        def rank_main(r, c, comm):
+            y0, y1 = parts[r]
+            nyl = y1 - y0
+            pipe = StripPipeline(c, comm, nx, nyl)
+
+            def put(a):
+                t = pipe.empty(getattr(torch, np.asarray(a).dtype.name))
+                t[1:nyl + 1] = torch.from_numpy(np.ascontiguousarray(a[y0:y1])).cuda()
+                return t
+            return D.strip(pipe, put, inp, strip_rows(dx, y0, y1), strip_rows(dy, y0, y1), y0, y1, seed)
+        res = grp.run(rank_main)
+    what = (f"seed {200 + seed}: {ny} x {nx} in {world} strips, {holes} holes, big-cell threshold {thr}, {eager} rounds between exchanges, "
+            f"{['constant', 'wild', 'band'][seed % 3]} cell sizes")
+    got = {k: np.concatenate([r[k] for r in res], axis=0) for k in res[0] if k != "gw_id"}
+    bad = D.compare(got, {k: v for k, v in ref.items() if k != "gw_id"}, what)
+    bad += [f"{what}: rank {r} -id table {res[r]['gw_id']!r} vs {ref['gw_id']!r}" for r in range(world) if res[r]["gw_id"] != ref["gw_id"]]
+    assert not bad, "\n".join(bad)
