@@ -430,8 +430,14 @@ struct LevelOpT {
         const size_t pitch = size_t(g.nx);
         int* const h = lds; int* const pre = h + MACRO_LMAX; int* const suf = pre + MACRO_LMAX; int* const pm = suf + MACRO_LMAX; int* const sp = pm + MACRO_LMAX;
         int* const acc = sp + MACRO_LMAX;                  // [4][MACRO_LMAX - 2]: rim edges top, bottom, left, right
-        int* const moved = acc + 4 * (MACRO_LMAX - 2);     // [4]: per rim edge, bit s = a cell of its s-th 64-cell segment moved
+        int* const moved = acc + 4 * (MACRO_LMAX - 2);     // [8]: see below
         constexpr int AW = MACRO_LMAX - 2;
+        // [0 .. 4): per ring edge, bit p + 1 = the tile outside at position p (-1 .. k) can be improved; [4 .. 8): the ring edge holds a level at all.  Zeroed by
+        // wave 0 BEFORE the barrier: lane 0 of every wave raises moved[4 + E] below, and a zero landing after another wave's flag would drop the edge's offers
+        // for this activation (the gain filter then withholds the wake-up that could repair it).  (The previous activation's last read of moved[] is
+        // behind the barrier that ends it; this one comes before any global load is issued.)
+        if (tid < 8) moved[tid] = 0;
+        __syncthreads();
         // rim cell i of edge e (0 top, 1 bottom, 2 left, 3 right)
         auto rim_idx = [&](int e, int i) -> size_t {
             const int x = e == 2 ? 0 : (e == 3 ? W - 1 : i), y = e == 0 ? 0 : (e == 1 ? W - 1 : i);
@@ -474,7 +480,6 @@ struct LevelOpT {
                 old[e][u] = i < W ? decode(raw_rim[e][u]) : MACRO_INF;
                 best[e][u] = old[e][u];
             }
-        if (tid < 8) moved[tid] = 0;   // [0 .. 4): per ring edge, bit p + 1 = the tile outside at position p (-1 .. k) can be improved; [4 .. 8): the ring edge holds a level at all
 #pragma unroll
         for (int E = 0; E < 4; E++) {
             bool fin = false;

@@ -44,6 +44,10 @@ constexpr int NTHR = NWAVE * 64;
 constexpr int COUNT_RING = 1024;
 constexpr int MAX_SWEEPS = 8;
 constexpr int PULL_MAX = 64;    // tiles a workgroup takes from the round's list per cursor atomic (large rounds)
+// macro_role deals the blocks of a round of up to MACRO_DEAL_MAX entries out by their number, and one workgroup keeps at most PULL_MAX of them: with at least
+// MACRO_WGS_MIN block workgroups (the host's launch makes sure) no workgroup is dealt more, even when every entry of the round is a block
+constexpr unsigned MACRO_DEAL_MAX = 4096;
+constexpr unsigned MACRO_WGS_MIN = MACRO_DEAL_MAX / PULL_MAX;
 
 struct TileGeom {
     int nx, ny;             // raster (strip incl. halo rows) size
@@ -985,8 +989,9 @@ __device__ __forceinline__ void macro_role(const Op& op, const TileGeom& g, cons
     // A round of up to 4096 entries - every round but the first few: EVERY block workgroup numbers the round's blocks in list order (16 entries per thread, one
     // workgroup-wide prefix count) and serves the blocks whose number is its own modulo the number of block workgroups: no workgroup serves two blocks while
     // another idles (with list entries dealt out by index, 150 blocks on 1 024 workgroups met two to four at a time in one of them: rounds of 35 - 76 us).
-    if (nact <= 4096u) {
+    if (nact <= MACRO_DEAL_MAX) {
         constexpr int PER = 16;
+        static_assert(PER * NTHR == MACRO_DEAL_MAX, "every entry of a dealt round is looked at");
         uint32_t ent[PER];
         unsigned kk[PER];
         const unsigned first = threadIdx.x * PER;
@@ -1010,12 +1015,12 @@ __device__ __forceinline__ void macro_role(const Op& op, const TileGeom& g, cons
 #pragma unroll
         for (int j = 0; j < PER; j++)
             if (kk[j] != 0u) {
-                if (before % nblocks == bid) { const unsigned slot = atomicAdd(&L.next, 1u); if (slot < unsigned(PULL_MAX)) L.pulled[slot] = ent[j]; }
+                if (before % nblocks == bid) { const unsigned slot = atomicAdd(&L.next, 1u); if (slot < unsigned(PULL_MAX)) L.pulled[slot] = ent[j]; }   // (always: nblocks >= MACRO_WGS_MIN)
                 before++;
             }
         __syncthreads();
         if (dbg && threadIdx.x == 0 && L.next) atomicMax(dbg + 15, (unsigned long long)L.next);
-        serve(L.next < unsigned(PULL_MAX) ? L.next : unsigned(PULL_MAX));   // (at most 4096 / 4 blocks over >= 256 workgroups: never more than 4 each)
+        serve(L.next < unsigned(PULL_MAX) ? L.next : unsigned(PULL_MAX));   // (at most MACRO_DEAL_MAX blocks - every entry may be one - over nblocks >= MACRO_WGS_MIN workgroups: at most PULL_MAX each)
         return;
     }
     // 64 list entries per look (at most PULL_MAX = 64 blocks to remember), STRIDED over the list: neighbouring entries - blocks activated by the same front - go
@@ -1432,7 +1437,8 @@ struct RoundRunner {
             else {
                 // with macro blocks (TileGeom::blk_k): four more workgroups per CU in the same launch serve the blocks of the round (1 / 2 / 4 / 8 / 16 per CU: 22.07 / 21.97 / 21.86 / 21.81 / 21.87 ms per 16384^2 step, profiles/r06g_macro_wgs.txt)
                 static const int macro_wgs = getenv("TDX_MACRO_WGS") ? std::max(1, atoi(getenv("TDX_MACRO_WGS"))) : 4;   // (A/B hook: block workgroups per CU)
-                const unsigned gm = (has_macro<Op>::value && g.blk_k != nullptr) ? unsigned(macro_wgs * ctx->num_cus) : 0u;
+                // (at least MACRO_WGS_MIN of them, whatever the number of CUs: macro_role keeps at most PULL_MAX blocks per workgroup)
+                const unsigned gm = (has_macro<Op>::value && g.blk_k != nullptr) ? std::max(unsigned(macro_wgs * ctx->num_cus), MACRO_WGS_MIN) : 0u;
                 hipLaunchKernelGGL((relax_kernel<Op, true>), dim3(grid + gm), dim3(NTHR), 0, s, op, g, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1),
                                    list_of(p ^ 1), pull_max, dbg, gm ? grid : 0u);
             }
