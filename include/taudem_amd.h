@@ -272,6 +272,31 @@ int tdx_dinfdistup_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t
 int tdx_dinfdistup(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
                    const double* dxc, const double* dyc, const float* fel, float fel_nodata, const float* w, float w_nodata,
                    int statmethod, int typemethod, int contcheck, float thresh, float* du, tdx_stats* stats);
+/* retlimro() src/RetlimFlow.cpp:53-240: retention limited runoff.  For a cell whose wg and rc are data, qrl = max(0, sum over the
+ * neighbours that drain into it of p * qrl + wg - rc), p a float, float arithmetic in k = 1..8 order.  A cell whose wg or rc is nodata
+ * gets no value and neither does anything downstream of it (the reference never releases its receivers).  No outlets, no
+ * contamination check.  Result float, nodata -FLT_MAX. */
+int tdx_retlimflow_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
+                       const double* dxc, const double* dyc, const float* d_wg, float wg_nodata, const float* d_rc, float rc_nodata,
+                       float* d_qrl, tdx_stats* stats);
+int tdx_retlimflow(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
+                   const double* dxc, const double* dyc, const float* wg, float wg_nodata, const float* rc, float rc_nodata,
+                   float* qrl, tdx_stats* stats);
+/* avalancherunoutgrd() src/DinfAvalanche.cpp:62-420: avalanche runout.  A cell with ass > 0 (int16 source grid) and an elevation is a
+ * source; every cell takes, over the neighbours that drain into it with a proportion p >= thresh and a runout angle rz >= alpha, the
+ * source with the largest angle beta = atan((source elevation - fel) / d) in degrees, if beta >= alpha.  path != 0: d is measured
+ * along the flow path; path == 0 (-direct): d is the straight line from the source cell, from the raster's coordinates - geo =
+ * {xleftedge, ytopedge, dlon, dlat} of the whole raster (NULL: 0, ny * dyc[0], dxc[0], dyc[0]; required when geographic != 0, where
+ * dlon / dlat are degrees) - and rasters wider or taller than 65536 are refused with TDX_ERR_ARG.  rz (runout angle) and dfs
+ * (distance from the source) float, nodata -FLT_MAX.  rz is within a few float ulps of the reference's. */
+int tdx_dinfavalanche_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
+                          const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const int16_t* d_ass,
+                          int16_t ass_nodata, float thresh, float alpha, int path, const double* geo, int geographic,
+                          float* d_rz, float* d_dfs, tdx_stats* stats);
+int tdx_dinfavalanche(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
+                      const double* dxc, const double* dyc, const float* fel, float fel_nodata, const int16_t* ass,
+                      int16_t ass_nodata, float thresh, float alpha, int path, const double* geo, int geographic,
+                      float* rz, float* dfs, tdx_stats* stats);
 /* dsllArea() src/DinfConcLimAccum.cpp:61-326: concentration limited accumulation.  ctpt = csol where the indicator dg (int16,
  * a SHORT grid in the reference) is > 0, else sum over the contributing cells of p * ctpt * q * dm divided by the cell's own q;
  * cells with q <= 0 get no value.  Result float, nodata -FLT_MAX.  Outlets as for tdx_areadinf. */
@@ -404,6 +429,15 @@ int tdx_dinfdistdown_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang,
 int tdx_dinfdistup_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                          const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const float* d_w, float w_nodata,
                          int statmethod, int typemethod, int contcheck, float thresh, float* d_du, tdx_stats* stats);
+/* RetLimFlow and DinfAvalanche on strips (row0: global row of the strip's first owned row, ny_total: rows of the whole raster; geo
+ * describes the whole raster) */
+int tdx_retlimflow_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
+                         const double* dxc, const double* dyc, const float* d_wg, float wg_nodata, const float* d_rc, float rc_nodata,
+                         float* d_qrl, tdx_stats* stats);
+int tdx_dinfavalanche_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
+                            const double* dxc, const double* dyc, const float* d_fel, float fel_nodata, const int16_t* d_ass,
+                            int16_t ass_nodata, float thresh, float alpha, int path, const double* geo, int geographic,
+                            int64_t row0, int64_t ny_total, float* d_rz, float* d_dfs, tdx_stats* stats);
 /* the reverse D8 tools on strips (dxc / dyc: per-row cell sizes of the ny_local + 2 strip rows; outlet_row: array row of the strip,
  * outside the owned rows = on another rank).  placed / iddown come back reduced over the ranks: the same on every rank. */
 int tdx_d8hdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata,
@@ -504,6 +538,12 @@ int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* 
  *                int concheck, float thresh)                                  src/DinfDistUp.cpp:65-66 (slpfile is never read) */
 int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* slpfile, const char* wfile, const char* rtrfile,
                         int statmethod, int typemethod, int usew, int concheck, float thresh);
+/* int retlimro(char* angfile, char* wgfile, char* rcfile, char* qrlfile)         src/RetlimFlow.cpp:53 */
+int tdx_tool_retlimflow(const char* angfile, const char* wgfile, const char* rcfile, const char* qrlfile);
+/* int avalancherunoutgrd(char* angfile, char* felfile, char* assfile, char* rzfile, char* dmfile, float thresh, float alpha,
+ *                        int path)                                             src/DinfAvalanche.cpp:62-63 */
+int tdx_tool_dinfavalanche(const char* angfile, const char* felfile, const char* assfile, const char* rzfile, const char* dmfile,
+                           float thresh, float alpha, int path);
 /* int distgrid(char* pfile, char* srcfile, char* distfile, int thresh)          src/D8HDistToStrm.cpp:57 */
 int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh);
 /* int gagewatershed(char* pfile, char* wfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* idfile, int writeid,

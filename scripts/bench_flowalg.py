@@ -1,7 +1,7 @@
 """The accumulation tools beside the headline path (SURVEY.md 8f ranks 2 and 4, config 5's kernel) on one MI355X, HBM-resident inputs:
 weighted AreaD8, D8FlowPathExtremeUp, GridNet, DinfDecayAccum with weights and outlets, DinfUpDependence, DinfRevAccum,
 DinfConcLimAccum, DinfTransLimAccum, DinfDistDown (ave v = HAND, ave h; streams = D-infinity area above the 98th percentile),
-DinfDistUp (ave h, ave v, ave p).  One JSON line with the ms of each (library-side HIP-event time of the call).
+DinfDistUp (ave h, ave v, ave p), RetLimFlow, DinfAvalanche (path; sources = 1 % of the cells).  One JSON line with the ms of each (library-side HIP-event time of the call).
 usage: python scripts/bench_flowalg.py [--size 16384]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -66,5 +66,7 @@ timed("d8hdisttostrm", lambda: ctx.d8hdisttostrm(p, src8, dx=30.0, dy=30.0, stat
 timed("gagewatershed", lambda: ctx.gagewatershed(p, gauges, stats=True))
 timed("dinfconclimaccum", lambda: ctx.dinfconclimaccum(ang, w2, dg16, w + 0.5, dx=30.0, dy=30.0, stats=True))
 timed("dinftranslimaccum_cs", lambda: ctx.dinftranslimaccum(ang, w, 50.0 * w2, cs=w2, dx=30.0, dy=30.0, stats=True))
+timed("retlimflow", lambda: ctx.retlimflow(ang, w, 0.5 * w2, dx=30.0, dy=30.0, stats=True))
+timed("dinfavalanche", lambda: ctx.dinfavalanche(ang, fel, dg16, dx=30.0, dy=30.0, stats=True))
 print(json.dumps({"metric": "ms per call", "size": n, "n_gpus": 1, "ms": res,
                   "config": {"workload": f"{n}x{n} synthetic fractal DEM (pit-filled): D8 / D-infinity directions from the library, random weight / multiplier / indicator grids in HBM"}}))

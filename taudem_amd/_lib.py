@@ -171,6 +171,16 @@ _SIGNATURES = {
     "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_tool_dinfdistup": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, wg, wg_nodata, rc, rc_nodata, qrl, stats
+    "tdx_retlimflow": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
+    "tdx_retlimflow_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
+    "tdx_retlimflow_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
+    "tdx_tool_retlimflow": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, ass, ass_nodata, thresh, alpha, path, geo, geographic, [row0, ny_total,] rz, dfs, stats
+    "tdx_dinfavalanche": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "tdx_dinfavalanche_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "tdx_dinfavalanche_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _I64, _I64, _P, _P, _P]),
+    "tdx_tool_dinfavalanche": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _F, _F, C.c_int]),
     "tdx_tool_dinfupdependence": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     "tdx_tool_dinfrevaccum": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, dg, q, q_nodata, csol, contcheck, ox, oy, n_outlets, ctpt, stats

@@ -441,6 +441,49 @@ class Context:
                                                  C.byref(st)), self._h)
         return (du, st.as_dict()) if stats else du
 
+    def retlimflow(self, ang, wg, rc, *, dx=1.0, dy=1.0, nodata=float(ANG_NODATA), wg_nodata=-9999.0, rc_nodata=-9999.0, stats=False):
+        """qrl = retlimro(ang, wg, rc)  (src/RetlimFlow.cpp:53): retention limited runoff, max(0, inflow + wg - rc) accumulated along the
+        D-infinity flow.  A cell whose wg or rc is nodata has no value, and neither has anything downstream of it.  qrl float32, nodata -FLT_MAX."""
+        ny, nx = ang.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        qrl = self._out(ang, np.float32, (ny, nx))
+        pa, dev = self._ptr(ang, np.float32, name="ang")
+        pw, wdev = self._ptr(wg, np.float32, (ny, nx), "wg")
+        pr, rdev = self._ptr(rc, np.float32, (ny, nx), "rc")
+        po, _ = self._ptr(qrl, np.float32, (ny, nx), "qrl")
+        if wdev != dev or rdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(ang, wg, rc)
+        check(self._pick(dev, "tdx_retlimflow")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw, float(wg_nodata), pr,
+                                                 float(rc_nodata), po, C.byref(st)), self._h)
+        return (qrl, st.as_dict()) if stats else qrl
+
+    def dinfavalanche(self, ang, fel, ass, *, thresh=0.2, alpha=18.0, direct=False, dx=1.0, dy=1.0, geo=None, geographic=False, nodata=float(ANG_NODATA),
+                      fel_nodata=float(FEL_NODATA), ass_nodata=-32768, stats=False):
+        """rz, dfs = avalancherunoutgrd(ang, fel, ass)  (src/DinfAvalanche.cpp:62): the runout zone below the source cells (ass > 0, int16) as the
+        angle to the source in degrees, and the distance from the source - along the flow path, or with direct=True as a straight line in
+        the raster's coordinates: geo = (xleftedge, ytopedge, dlon, dlat), by default (0, ny * dy[0], dx[0], dy[0]); needed when
+        geographic, where dlon / dlat are degrees.  float32, nodata -FLT_MAX."""
+        ny, nx = ang.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        rz = self._out(ang, np.float32, (ny, nx))
+        dfs = self._out(ang, np.float32, (ny, nx))
+        pa, dev = self._ptr(ang, np.float32, name="ang")
+        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
+        ps, sdev = self._ptr(ass, np.int16, (ny, nx), "ass")
+        pz, _ = self._ptr(rz, np.float32, (ny, nx), "rz")
+        pd, _ = self._ptr(dfs, np.float32, (ny, nx), "dfs")
+        if fdev != dev or sdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        g4 = None if geo is None else np.ascontiguousarray(np.asarray(geo, dtype=np.float64).reshape(4))
+        st = TdxStats()
+        self._sync_torch(ang, fel, ass)
+        check(self._pick(dev, "tdx_dinfavalanche")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf, float(fel_nodata),
+                                                    ps, int(ass_nodata), float(thresh), float(alpha), 0 if direct else 1,
+                                                    None if g4 is None else C.c_void_p(g4.ctypes.data), int(bool(geographic)), pz, pd, C.byref(st)), self._h)
+        return (rz, dfs, st.as_dict()) if stats else (rz, dfs)
+
     def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=float(ANG_NODATA), dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
                          outlets=None, stats=False):
         """ctpt = dsllArea(ang, dm, dg, q)  (src/DinfConcLimAccum.cpp:61): dg int16, ctpt float32 (nodata -FLT_MAX)."""

@@ -660,6 +660,105 @@ int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* /*
     return 0;
 }
 
+// retlimro() (src/RetlimFlow.cpp:53-240): ang, wg, rc, each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); the output header is rc's
+int tdx_tool_retlimflow(const char* angfile, const char* wgfile, const char* rcfile, const char* qrlfile) {
+    printf("Retention limited flow accumulation version %s\n", TDVERSION);
+    fflush(stdout);
+    Raster ang, wg, rcg;
+    int rc = load_raster(angfile, tdx::DType::F32, ang);
+    if (rc != TDX_OK) return rc;
+    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
+    rc = load_raster(wgfile, tdx::DType::F32, wg);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(ang.info, angfile, wg.info, wgfile)) return mismatch(wgfile);
+    rc = load_raster(rcfile, tdx::DType::F32, rcg);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(ang.info, angfile, rcg.info, rcfile)) return mismatch(rcfile);
+    std::vector<float> qrl(ang.f.size());
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            float* d_ang = j.strip<float>(ang.f.data());
+            float* d_wg = j.strip<float>(wg.f.data());
+            float* d_rc = j.strip<float>(rcg.f.data());
+            float* d_q = j.strip<float>(nullptr);
+            if (!d_ang || !d_wg || !d_rc || !d_q) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
+            const int e = tdx_retlimflow_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_wg, (float)wg.info.nodata, d_rc,
+                                               (float)rcg.info.nodata, d_q, s);
+            return e != TDX_OK ? e : (j.fetch(qrl.data(), d_q) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_retlimflow(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), wg.f.data(),
+                            (float)wg.info.nodata, rcg.f.data(), (float)rcg.info.nodata, qrl.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    rc = save_raster(qrlfile, tdx::DType::F32, qrl.data(), rcg.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of rc (src/RetlimFlow.cpp:233-235)
+    if (rc != TDX_OK) return rc;
+    printf("Processors: %d\n", nproc);   // (the reference prints no times for this tool; the count that ran, as the other tools say it)
+    print_gpu_stats("retlimflow", st, ang.info.nx * ang.info.ny);
+    return 0;
+}
+
+// avalancherunoutgrd() (src/DinfAvalanche.cpp:62-420): ang, fel, ass (SHORT), each compared with ang; a mismatch RETURNS 1 here (the MPI_Abort is
+// commented out in the reference).  -direct reads the file's coordinates: the geotransform goes to the library.
+int tdx_tool_dinfavalanche(const char* angfile, const char* felfile, const char* assfile, const char* rzfile, const char* dmfile, float thresh, float alpha, int path) {
+    printf("DinfAvalanche version %s\n", TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    Raster ang, fel, ass;
+    int rc = load_raster(angfile, tdx::DType::F32, ang);
+    if (rc != TDX_OK) return rc;
+    rc = load_raster(felfile, tdx::DType::F32, fel);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(ang.info, angfile, fel.info, felfile)) { printf("File sizes do not match\n%s\n%s\n", felfile, angfile); fflush(stdout); return 1; }
+    rc = load_raster(assfile, tdx::DType::I16, ass);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(ang.info, angfile, ass.info, assfile)) { printf("File sizes do not match\n%s\n%s\n", assfile, angfile); fflush(stdout); return 1; }
+    const double readt = now_s();
+    std::vector<float> rz(ang.f.size()), dfs(ang.f.size());
+    const double geo[4] = {ang.info.xleftedge, ang.info.ytopedge, ang.info.dlon, ang.info.dlat};
+    const int geographic = ang.info.geographic ? 1 : 0;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            float* d_ang = j.strip<float>(ang.f.data());
+            float* d_fel = j.strip<float>(fel.f.data());
+            int16_t* d_ass = j.strip<int16_t>(ass.s.data());
+            float* d_rz = j.strip<float>(nullptr);
+            float* d_dfs = j.strip<float>(nullptr);
+            if (!d_ang || !d_fel || !d_ass || !d_rz || !d_dfs) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
+            const int e = tdx_dinfavalanche_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, (float)fel.info.nodata, d_ass,
+                                                  (int16_t)ass.info.nodata, thresh, alpha, path, geo, geographic, j.y0, j.ny, d_rz, d_dfs, s);
+            if (e != TDX_OK) return e;
+            return j.fetch(rz.data(), d_rz) && j.fetch(dfs.data(), d_dfs) ? TDX_OK : TDX_ERR_HIP;
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_dinfavalanche(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), fel.f.data(),
+                               (float)fel.info.nodata, ass.s.data(), (int16_t)ass.info.nodata, thresh, alpha, path, geo, geographic, rz.data(), dfs.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(rzfile, tdx::DType::F32, rz.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of ang (src/DinfAvalanche.cpp:384-389)
+    if (rc != TDX_OK) return rc;
+    rc = save_raster(dmfile, tdx::DType::F32, dfs.data(), ang.info, (double)TDX_ANG_NODATA);
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("dinfavalanche", st, ang.info.nx * ang.info.ny);
+    return 0;
+}
+
 // distgrid() (src/D8HDistToStrm.cpp:57-260): p, then src read as LONG (File sizes do not match + MPI_Abort(MCW, 5))
 int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh) {
     printf("D8HDistToStrm version %s\n", TDVERSION);

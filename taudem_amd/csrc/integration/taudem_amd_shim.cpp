@@ -6,7 +6,7 @@
 // mains call (prototypes: src/flood.h:1-2, src/d8.h:5, src/aread8.h:3, src/tardemlib.h:70, src/areadinf.h:2,
 // src/dinfdecayaccum.cpp:61-62, src/gridnet.cpp:54-55, src/Threshold.cpp:49, src/D8flowpathextremeup.cpp:58,
 // src/DinfUpDependence.cpp:52, src/DinfRevAccum.cpp:51, src/DinfDistDown.cpp:66-67, src/DinfDistUp.cpp:65-66,
-// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56) forwards to the
+// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56, src/retlimro.h, src/DinfAvalanche.cpp:62-63) forwards to the
 // file-level C ABI, and nameadd() (src/commonLib.cpp:53-73, the only other symbol the mains use) is provided here.  No MPI and
 // no GDAL at link time (their headers are only needed to COMPILE the mains, which include commonLib.h).
 // oracle/Makefile builds oracle/_ref/shim_<tool> this way; tests/test_gpu_cli.py runs them against the reference's rasters.
@@ -38,6 +38,10 @@ int dinfdistdown(char* angfile, char* felfile, char* slpfile, char* wfile, char*
 { return tdx_tool_dinfdistdown(angfile, felfile, slpfile, wfile, srcfile, dtsfile, statmethod, typemethod, usew, concheck); }
 int dinfdistup(char* angfile, char* felfile, char* slpfile, char* wfile, char* rtrfile, int statmethod, int typemethod, int usew, int concheck, float thresh)
 { return tdx_tool_dinfdistup(angfile, felfile, slpfile, wfile, rtrfile, statmethod, typemethod, usew, concheck, thresh); }
+int retlimro(char* angfile, char* wgfile, char* rcfile, char* qrlfile)
+{ return tdx_tool_retlimflow(angfile, wgfile, rcfile, qrlfile); }
+int avalancherunoutgrd(char* angfile, char* felfile, char* assfile, char* rzfile, char* dmfile, float thresh, float alpha, int path)
+{ return tdx_tool_dinfavalanche(angfile, felfile, assfile, rzfile, dmfile, thresh, alpha, path); }
 int distgrid(char* pfile, char* srcfile, char* distfile, int thresh)
 { return tdx_tool_d8hdisttostrm(pfile, srcfile, distfile, thresh); }
 int gagewatershed(char* pfile, char* wfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* idfile, int writeid, int writeupid, char* upidfile)

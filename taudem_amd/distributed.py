@@ -466,6 +466,37 @@ class StripPipeline:
                                                  sm, tm, int(bool(contcheck)), float(thresh), _tptr(du, torch.float32, self.shape, "du"), C.byref(st)), self.ctx._h)
         return du, st.as_dict()
 
+    def retlimflow(self, ang, wg, rc, *, dx=1.0, dy=1.0, nodata=-3.402823466e38, wg_nodata=-9999.0, rc_nodata=-9999.0):
+        """qrl = retlimro(ang, wg, rc) on this strip (src/RetlimFlow.cpp:53): qrl float32 (nodata -FLT_MAX)."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        qrl = self.empty(torch.float32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_retlimflow_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
+                                                 C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(wg, torch.float32, self.shape, "wg"), float(wg_nodata),
+                                                 _tptr(rc, torch.float32, self.shape, "rc"), float(rc_nodata), _tptr(qrl, torch.float32, self.shape, "qrl"), C.byref(st)),
+              self.ctx._h)
+        return qrl, st.as_dict()
+
+    def dinfavalanche(self, ang, fel, ass, *, row0, ny_total, thresh=0.2, alpha=18.0, direct=False, dx=1.0, dy=1.0, geo=None, geographic=False,
+                      nodata=-3.402823466e38, fel_nodata=-3.0e38, ass_nodata=-32768):
+        """rz, dfs = avalancherunoutgrd(ang, fel, ass) on this strip (src/DinfAvalanche.cpp:62).  row0: global row of the strip's first owned row,
+        ny_total: rows of the whole raster; geo = (xleftedge, ytopedge, dlon, dlat) of the WHOLE raster (direct mode)."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        rz, dfs = self.empty(torch.float32), self.empty(torch.float32)
+        g4 = None if geo is None else np.ascontiguousarray(np.asarray(geo, dtype=np.float64).reshape(4))
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_dinfavalanche_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
+                                                    C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(fel, torch.float32, self.shape, "fel"),
+                                                    float(fel_nodata), _tptr(ass, torch.int16, self.shape, "ass"), int(ass_nodata), float(thresh), float(alpha),
+                                                    0 if direct else 1, None if g4 is None else C.c_void_p(g4.ctypes.data), int(bool(geographic)), int(row0),
+                                                    int(ny_total), _tptr(rz, torch.float32, self.shape, "rz"), _tptr(dfs, torch.float32, self.shape, "dfs"),
+                                                    C.byref(st)), self.ctx._h)
+        return rz, dfs, st.as_dict()
+
     def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=-32768, src_nodata=-2147483647):
         """dist = distgrid(p, src) on this strip (src/D8HDistToStrm.cpp:57): src int32, dist float32 (nodata -FLT_MAX)."""
         torch = self.torch

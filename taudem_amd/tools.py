@@ -92,6 +92,16 @@ def dinfdistup(angfile, felfile, slpfile, wfile, rtrfile, statmethod=0, typemeth
                                            int(concheck), float(thresh))
 
 
+def retlimro(angfile, wgfile, rcfile, qrlfile):
+    """src/RetlimFlow.cpp:53 (RetLimFlow)"""
+    return _lib.load().tdx_tool_retlimflow(_b(angfile), _b(wgfile), _b(rcfile), _b(qrlfile))
+
+
+def avalancherunoutgrd(angfile, felfile, assfile, rzfile, dmfile, thresh=0.2, alpha=18.0, path=1):
+    """src/DinfAvalanche.cpp:62 (DinfAvalanche)"""
+    return _lib.load().tdx_tool_dinfavalanche(_b(angfile), _b(felfile), _b(assfile), _b(rzfile), _b(dmfile), float(thresh), float(alpha), int(path))
+
+
 def distgrid(pfile, srcfile, distfile, thresh=1):
     """src/D8HDistToStrm.cpp:57 (D8HDistToStrm)"""
     return _lib.load().tdx_tool_d8hdisttostrm(_b(pfile), _b(srcfile), _b(distfile), int(thresh))
