@@ -257,6 +257,31 @@ int tdx_gagewatershed_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int6
 int tdx_gagewatershed(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* outlet_x,
                       const int32_t* outlet_y, const int32_t* ids, int64_t n_outlets, int32_t* gw, int32_t* placed, int32_t* iddown,
                       tdx_stats* stats);
+/* d8vdistdown() src/D8VDistToStrm.cpp:58-276 (D8VDistToStrm): vertical drop along the D8 flow path down to the stream.  Sources, participation
+ * and release are tdx_d8hdisttostrm's; a cell that is not a stream cell gets (fel - fel(receiver)) + dist(receiver) in float, nodata
+ * (-FLT_MAX) where the receiver has no value.  fel is read with no nodata test, as in the reference. */
+int tdx_d8vdisttostrm_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_fel, const int32_t* d_src,
+                          int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats);
+int tdx_d8vdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* fel, const int32_t* src,
+                      int32_t src_nodata, int32_t thresh, float* dist, tdx_stats* stats);
+/* flowdircond() src/flowdircond.cpp:54-252 (FlowDirCond): z conditioned along the D8 directions.  From the ridges downstream every cell the
+ * queue of initNeighborD8up reaches and whose z is not nodata becomes the minimum of its own z and the conditioned z of every neighbour
+ * that has a code 1..8, drains into it and is not nodata.  Every other cell keeps its input value; the result carries z's nodata value.
+ * zfdc must not alias z. */
+int tdx_flowdircond_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_z, float z_nodata,
+                        float* d_zfdc, tdx_stats* stats);
+int tdx_flowdircond(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* z, float z_nodata, float* zfdc,
+                    tdx_stats* stats);
+/* sloped() src/SlopeAveDown.cpp:59-330 (SlopeAveDown): the slope from each cell to the cell the distance dn down its D8 flow path, after
+ * niter synchronous one-step pulls along the D8 pointer (the reference's niter Kahn passes).  niter <= 0: int(dn / min(dxA, dyA)) + 1 with
+ * the cell sizes of the raster's middle row, as the reference (tdx_slopeavedown_niter; the strip form needs it given).  niter is not
+ * capped; dn that is negative or not finite is refused with TDX_ERR_ARG.  slpd float32, nodata -FLT_MAX.  ms_kernel[TDX_K_ACCUM] is the
+ * sweep that finds the cells the passes visit, ms_kernel[TDX_K_MISC] the niter passes. */
+int64_t tdx_slopeavedown_niter(double dn, const double* dxc, const double* dyc, int64_t ny);
+int tdx_slopeavedown_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_fel, float fel_nodata,
+                         const double* dxc, const double* dyc, double dn, int64_t niter, float* d_slpd, tdx_stats* stats);
+int tdx_slopeavedown(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* fel, float fel_nodata,
+                     const double* dxc, const double* dyc, double dn, int64_t niter, float* slpd, tdx_stats* stats);
 /* dinfdistup() src/DinfDistUp.cpp:65-1214: distance from each cell up to the ridge along the D-infinity flow, over the neighbours that
  * drain into it (AreaDinf's dependency graph, no outlets).  typemethod 0 h (horizontal, hdisttoridgegrd :94), 1 v (vertical rise,
  * vrisetoridgegrd :356), 2 p (Pythagorean, sqrt(h^2 + v^2), pdisttoridgegrd :599), 3 s (surface: sqrt(dz^2 + dh^2) per step,
@@ -446,6 +471,14 @@ int tdx_d8hdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p
 int tdx_gagewatershed_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata,
                             const int32_t* outlet_x, const int32_t* outlet_row, const int32_t* ids, int64_t n_outlets, int32_t* d_gw,
                             int32_t* placed, int32_t* iddown, tdx_stats* stats);
+/* the last three D8 tools on strips.  d_fel of tdx_d8vdisttostrm_strip is written: its halo rows are exchanged before the set-up.
+ * tdx_slopeavedown_strip: dxc / dyc of the ny_local + 2 strip rows, niter > 0 from the WHOLE raster (tdx_slopeavedown_niter). */
+int tdx_d8vdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, float* d_fel,
+                            const int32_t* d_src, int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats);
+int tdx_flowdircond_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const float* d_z,
+                          float z_nodata, float* d_zfdc, tdx_stats* stats);
+int tdx_slopeavedown_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const float* d_fel,
+                           float fel_nodata, const double* dxc, const double* dyc, double dn, int64_t niter, float* d_slpd, tdx_stats* stats);
 /* the limited D-infinity accumulations on strips (outlet_row: array row of the strip, as for tdx_areadinf_strip) */
 int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg,
@@ -550,6 +583,12 @@ int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* d
  *                   int writeupid, char* upidfile)                            src/gagewatershed.cpp:56 (writeupid = 1 is refused) */
 int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* datasrc, const char* lyrname, int uselyrname, int lyrno,
                            const char* idfile, int writeid, int writeupid, const char* upidfile);
+/* int flowdircond(char* pfile, char* zfile, char* zfdcfile)                      src/flowdircond.cpp:54 */
+int tdx_tool_flowdircond(const char* pfile, const char* zfile, const char* zfdcfile);
+/* int d8vdistdown(char* pfile, char* felfile, char* srcfile, char* distfile, int thresh)   src/D8VDistToStrm.cpp:58 */
+int tdx_tool_d8vdisttostrm(const char* pfile, const char* felfile, const char* srcfile, const char* distfile, int thresh);
+/* int sloped(char* pfile, char* felfile, char* slpdfile, double dn)               src/SlopeAveDown.cpp:59 */
+int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* slpdfile, double dn);
 /* int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile,
  *              char* dgfile, int useOutlets, int contcheck, float cSol)          src/DinfConcLimAccum.cpp:61-62 */
 int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* lyrname,

@@ -167,6 +167,22 @@ _SIGNATURES = {
     "tdx_gagewatershed": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "tdx_gagewatershed_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "tdx_tool_gagewatershed": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
+    # ctx, p, nx, ny, p_nodata, fel, src, src_nodata, thresh, dist, stats
+    "tdx_d8vdisttostrm_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tdx_d8vdisttostrm": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tdx_d8vdisttostrm_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tdx_tool_d8vdisttostrm": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
+    # ctx, p, nx, ny, p_nodata, z, z_nodata, zfdc, stats
+    "tdx_flowdircond_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
+    "tdx_flowdircond": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
+    "tdx_flowdircond_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
+    "tdx_tool_flowdircond": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
+    # ctx, p, nx, ny, p_nodata, fel, fel_nodata, dxc, dyc, dn, niter, slpd, stats
+    "tdx_slopeavedown_niter": (_I64, [C.c_double, _P, _P, _I64]),
+    "tdx_slopeavedown_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
+    "tdx_slopeavedown": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
+    "tdx_slopeavedown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
+    "tdx_tool_slopeavedown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_double]),
     "tdx_dinfdistup_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),

@@ -387,6 +387,61 @@ class Context:
                                                    C.c_void_p(dyc.ctypes.data), po, C.byref(st)), self._h)
         return (dist, st.as_dict()) if stats else dist
 
+    def d8vdisttostrm(self, p, fel, src, thresh=1, *, nodata=int(P_NODATA), src_nodata=-2147483647, stats=False):
+        """dist = d8vdistdown(p, fel, src)  (src/D8VDistToStrm.cpp:58): vertical drop along the D8 flow path down to the stream.
+
+        Stream cells as for d8hdisttostrm; every other cell gets (fel - fel(receiver)) + dist(receiver) in float32.  fel is read with no
+        nodata test, as in the reference.  dist float32, nodata -FLT_MAX."""
+        ny, nx = p.shape
+        dist = self._out(p, np.float32, (ny, nx))
+        pp, dev = self._ptr(p, np.int16, name="p")
+        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
+        ps, sdev = self._ptr(src, np.int32, (ny, nx), "src")
+        po, _ = self._ptr(dist, np.float32, (ny, nx), "dist")
+        if sdev != dev or fdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(p, fel, src)
+        check(self._pick(dev, "tdx_d8vdisttostrm")(self._h, pp, nx, ny, int(nodata), pf, ps, int(src_nodata), int(thresh), po, C.byref(st)), self._h)
+        return (dist, st.as_dict()) if stats else dist
+
+    def flowdircond(self, p, z, *, nodata=int(P_NODATA), z_nodata=float(FEL_NODATA), stats=False):
+        """zfdc = flowdircond(p, z)  (src/flowdircond.cpp:54): z conditioned along the D8 directions - from the ridges downstream every
+        cell becomes the minimum of its own z and the conditioned z of the cells that drain into it.
+
+        Cells the reference's queue never reaches (no valid direction, below a p == 0 cell, on or below a cycle) and cells with nodata z
+        keep their input value; the result carries z's nodata value."""
+        ny, nx = p.shape
+        out = self._out(p, np.float32, (ny, nx))
+        pp, dev = self._ptr(p, np.int16, name="p")
+        pz, zdev = self._ptr(z, np.float32, (ny, nx), "z")
+        po, _ = self._ptr(out, np.float32, (ny, nx), "zfdc")
+        if zdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(p, z)
+        check(self._pick(dev, "tdx_flowdircond")(self._h, pp, nx, ny, int(nodata), pz, float(z_nodata), po, C.byref(st)), self._h)
+        return (out, st.as_dict()) if stats else out
+
+    def slopeavedown(self, p, fel, dn=50.0, *, dx=1.0, dy=1.0, niter=None, nodata=int(P_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
+        """slpd = sloped(p, fel, dn)  (src/SlopeAveDown.cpp:59): the slope from each cell to the cell the distance dn down its D8 flow path.
+
+        niter (default int(dn / min(dx, dy) of the middle row) + 1, the reference's count; not capped) synchronous one-step pulls along
+        the D8 pointer.  dn must be finite and not negative.  slpd float32, nodata -FLT_MAX."""
+        ny, nx = p.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        out = self._out(p, np.float32, (ny, nx))
+        pp, dev = self._ptr(p, np.int16, name="p")
+        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
+        po, _ = self._ptr(out, np.float32, (ny, nx), "slpd")
+        if fdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        st = TdxStats()
+        self._sync_torch(p, fel)
+        check(self._pick(dev, "tdx_slopeavedown")(self._h, pp, nx, ny, int(nodata), pf, float(fel_nodata), C.c_void_p(dxc.ctypes.data),
+                                                  C.c_void_p(dyc.ctypes.data), float(dn), int(niter) if niter else 0, po, C.byref(st)), self._h)
+        return (out, st.as_dict()) if stats else out
+
     def gagewatershed(self, p, outlets, *, nodata=int(P_NODATA), stats=False):
         """gw, id_table = gagewatershed(p, outlets)  (src/gagewatershed.cpp:56): every cell gets the id of the first gauge downstream of it.
 

@@ -14,6 +14,9 @@
 //   tdx_tool_dinfdistup      <- dinfdistup()    src/DinfDistUp.cpp:65-1214
 //   tdx_tool_d8hdisttostrm   <- distgrid()      src/D8HDistToStrm.cpp:57-260
 //   tdx_tool_gagewatershed   <- gagewatershed() src/gagewatershed.cpp:56-360
+//   tdx_tool_flowdircond     <- flowdircond()   src/flowdircond.cpp:54-252
+//   tdx_tool_d8vdisttostrm   <- d8vdistdown()   src/D8VDistToStrm.cpp:58-276
+//   tdx_tool_slopeavedown    <- sloped()        src/SlopeAveDown.cpp:59-330
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -861,6 +864,150 @@ int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* dat
     printf("Size: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
            writet - begint);
     print_gpu_stats("gagewatershed", st, p.info.nx * p.info.ny);
+    return 0;
+}
+
+// flowdircond() (src/flowdircond.cpp:54-252): p, then z (File sizes do not match + MPI_Abort(MCW, 5)); the output carries z's nodata value
+int tdx_tool_flowdircond(const char* pfile, const char* zfile, const char* zfdcfile) {
+    printf("FlowDirCond version %s\n", TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    Raster p, z;
+    int rc = load_raster(pfile, tdx::DType::I16, p);
+    if (rc != TDX_OK) return rc;
+    rc = load_raster(zfile, tdx::DType::F32, z);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(p.info, pfile, z.info, zfile)) { printf("File sizes do not match\n%s\n", zfile); fflush(stdout); return TDX_ERR_OUTLETS; }
+    const double readt = now_s();
+    std::vector<float> out(p.s.size());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float z_nd = (float)z.info.nodata;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.strip<int16_t>(p.s.data());
+            float* d_z = j.strip<float>(z.f.data());
+            float* d_o = j.strip<float>(nullptr);
+            if (!d_p || !d_z || !d_o) return TDX_ERR_NOMEM;
+            const int e = tdx_flowdircond_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_z, z_nd, d_o, s);
+            return e != TDX_OK ? e : (j.fetch(out.data(), d_o) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_flowdircond(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, z.f.data(), z_nd, out.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(zfdcfile, tdx::DType::F32, out.data(), z.info, z.info.nodata);   // zIO's nodata, like zIO (src/flowdircond.cpp:224)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("flowdircond", st, p.info.nx * p.info.ny);
+    return 0;
+}
+
+// d8vdistdown() (src/D8VDistToStrm.cpp:58-276): p, fel, then src read as LONG (File sizes do not match + MPI_Abort(MCW, 5))
+int tdx_tool_d8vdisttostrm(const char* pfile, const char* felfile, const char* srcfile, const char* distfile, int thresh) {
+    printf("D8VDistToStrm version %s\n", TDVERSION);
+    fflush(stdout);
+    const double begint = now_s();
+    Raster p, fel, src;
+    int rc = load_raster(pfile, tdx::DType::I16, p);
+    if (rc != TDX_OK) return rc;
+    rc = load_raster(felfile, tdx::DType::F32, fel);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(p.info, pfile, fel.info, felfile)) { printf("File sizes do not match\n%s\n", felfile); fflush(stdout); return TDX_ERR_OUTLETS; }
+    rc = load_raster(srcfile, tdx::DType::I32, src);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(p.info, pfile, src.info, srcfile)) { printf("File sizes do not match\n%s\n", srcfile); fflush(stdout); return TDX_ERR_OUTLETS; }
+    const double readt = now_s();
+    std::vector<float> dist(p.s.size());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t s_nd = (int32_t)src.info.nodata;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.strip<int16_t>(p.s.data());
+            float* d_fel = j.strip<float>(fel.f.data());
+            int32_t* d_src = j.strip<int32_t>(src.l.data());
+            float* d_dist = j.strip<float>(nullptr);
+            if (!d_p || !d_fel || !d_src || !d_dist) return TDX_ERR_NOMEM;
+            const int e = tdx_d8vdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, d_src, s_nd, thresh, d_dist, s);
+            return e != TDX_OK ? e : (j.fetch(dist.data(), d_dist) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_d8vdisttostrm(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), src.l.data(), s_nd, thresh, dist.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(distfile, tdx::DType::F32, dist.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8VDistToStrm.cpp:250-252)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("d8vdisttostrm", st, p.info.nx * p.info.ny);
+    return 0;
+}
+
+// sloped() (src/SlopeAveDown.cpp:59-330): fel, then p (File sizes do not match + MPI_Abort(MCW, 5)); the cell sizes are fel's, the output is
+// written like p.  niter = int(dn / min(dxA, dyA)) + 1 (:172) is not capped; a dn that is negative or not finite is refused.
+int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* slpdfile, double dn) {
+    printf("SlopeAveDown version %s\n", TDVERSION);
+    fflush(stdout);
+    if (!std::isfinite(dn) || dn < 0.0) {
+        fprintf(stderr, "taudem_amd: slopeavedown: dn must be finite and not negative\n");
+        g_tdx_thread_error = "slopeavedown: dn must be finite and not negative";
+        return TDX_ERR_ARG;
+    }
+    const double begint = now_s();
+    Raster p, fel;
+    int rc = load_raster(felfile, tdx::DType::F32, fel);
+    if (rc != TDX_OK) return rc;
+    rc = load_raster(pfile, tdx::DType::I16, p);
+    if (rc != TDX_OK) return rc;
+    if (!compare_rasters(fel.info, felfile, p.info, pfile)) { printf("File sizes do not match\n%s\n", pfile); fflush(stdout); return TDX_ERR_OUTLETS; }
+    const double readt = now_s();
+    const int64_t niter = tdx_slopeavedown_niter(dn, fel.info.dxc.data(), fel.info.dyc.data(), fel.info.ny);
+    if (niter <= 0) { g_tdx_thread_error = "slopeavedown: the cell sizes give no iteration count"; return TDX_ERR_ARG; }
+    fprintf(stderr, "Number of slope down interations to do %lld\n", (long long)niter);
+    fflush(stderr);
+    std::vector<float> sd(p.s.size());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float f_nd = (float)fel.info.nodata;
+    tdx_stats st;
+    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
+    if (nproc > 1) {
+        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.strip<int16_t>(p.s.data());
+            float* d_fel = j.strip<float>(fel.f.data());
+            float* d_sd = j.strip<float>(nullptr);
+            if (!d_p || !d_fel || !d_sd) return TDX_ERR_NOMEM;
+            const std::vector<double> dxs = j.rows_of(fel.info.dxc), dys = j.rows_of(fel.info.dyc);
+            const int e = tdx_slopeavedown_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, f_nd, dxs.data(), dys.data(), dn, niter, d_sd, s);
+            return e != TDX_OK ? e : (j.fetch(sd.data(), d_sd) ? TDX_OK : TDX_ERR_HIP);
+        });
+        if (rc != TDX_OK) return rc;
+    } else {
+        CtxGuard g;
+        if (g.rc != TDX_OK) return g.rc;
+        rc = tdx_slopeavedown(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), f_nd, fel.info.dxc.data(), fel.info.dyc.data(), dn, niter, sd.data(), &st);
+        if (rc != TDX_OK) { report(g.c); return rc; }
+    }
+    const double computet = now_s();
+    rc = save_raster(slpdfile, tdx::DType::F32, sd.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, like pIO (src/SlopeAveDown.cpp:302-304)
+    if (rc != TDX_OK) return rc;
+    const double writet = now_s();
+    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
+           writet - begint);
+    print_gpu_stats("slopeavedown", st, p.info.nx * p.info.ny);
     return 0;
 }
 

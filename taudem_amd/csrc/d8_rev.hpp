@@ -1,4 +1,4 @@
-// The set-up of the REVERSE D8 sweeps (d8rev.hip: D8HDistToStrm, GageWatershed), the counterpart of dinf_rev.hpp: one streaming pass
+// The set-up of the REVERSE D8 sweeps (d8rev.hip: D8HDistToStrm, D8VDistToStrm, GageWatershed), the counterpart of dinf_rev.hpp: one streaming pass
 // over the direction grid writes the info word of the dependency graph.  A cell's value comes from the ONE cell it drains to (its
 // receiver); the sweep runs upstream from the sources (stream cells / gauges) and a finished cell releases the neighbours that drain
 // into it.
@@ -11,8 +11,11 @@
 //              p is 1..8 (p == 0 reads the cell's own, still unset, distance: nodata).
 //   MODE_GAGE  p(n) > 0 first (src/gagewatershed.cpp:257-259).  Cells with p 1..8 take part and depend on their receiver; the gauges are
 //              seeded by the caller, which clears their info word.
+//   MODE_VDIST sources, participation and release of MODE_DIST (src/D8VDistToStrm.cpp:153-165, 201-219).
 // MODE_DIST also writes each cell's own step into `step` (dist[j][p], float, of the cell's row j; 0 on stream cells; nodata where there
-// is no receiver), so that the sweep's evaluation is one float add.
+// is no receiver), so that the sweep's evaluation is one float add.  MODE_VDIST's step is the drop to the receiver, fel - fel(receiver) in
+// float with no nodata test on either (src/D8VDistToStrm.cpp:191-198); a cell whose receiver lies off the array is never released, its
+// step is nodata.
 #pragma once
 #include <vector>
 
@@ -23,13 +26,13 @@
 namespace d8rev {
 using namespace tdxk;
 
-enum { MODE_DIST = 0, MODE_GAGE = 1 };
+enum { MODE_DIST = 0, MODE_GAGE = 1, MODE_VDIST = 2 };
 constexpr int32_t GW_NODATA = -2147483647;   // MISSINGLONG (src/commonLib.h:79)
 
 // src / step are only read / written on the owned rows [y_own0, y_own1) (the halo rows of a strip hold no src values); `dist` is [row][9]
 static __global__ __launch_bounds__(256) void setup_kernel(const int16_t* __restrict__ P, int nx, int ny, int16_t nodata, int mode, const int32_t* __restrict__ src,
-                                                           int32_t src_nodata, int32_t thresh, const float* __restrict__ dist, int y_own0, int y_own1,
-                                                           uint32_t* __restrict__ info, float* __restrict__ step) {
+                                                           int32_t src_nodata, int32_t thresh, const float* __restrict__ dist, const float* __restrict__ fel, int y_own0,
+                                                           int y_own1, uint32_t* __restrict__ info, float* __restrict__ step) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= nx || y >= ny) return;
@@ -46,11 +49,21 @@ static __global__ __launch_bounds__(256) void setup_kernel(const int16_t* __rest
         if (pn - k == 4 || pn - k == -4) inf |= 1u << (16 + k - 1);
     }
     const bool recv = !pnd && p >= 1 && p <= 8;
-    if (mode == MODE_DIST) {
+    if (mode != MODE_GAGE) {
         const bool stream = own && src[idx] != src_nodata && src[idx] >= thresh;   // !src->isNodata(i, j) && src >= thresh (src/D8HDistToStrm.cpp:171)
         if (stream || !pnd) inf |= d8sweep::INFO_PART;
         if (!stream && recv) inf |= 1u << (p - 1);
-        if (own) step[idx] = stream ? 0.0f : (recv ? dist[size_t(y) * 9 + size_t(p)] : TDX_ANG_NODATA);
+        if (own) {
+            float stp = stream ? 0.0f : TDX_ANG_NODATA;
+            if (!stream && recv) {
+                if (mode == MODE_DIST) stp = dist[size_t(y) * 9 + size_t(p)];
+                else {
+                    const int xn = x + d1(p), yn = y + d2(p);
+                    if (xn >= 0 && xn < nx && yn >= 0 && yn < ny) stp = fel[idx] - fel[size_t(yn) * size_t(nx) + size_t(xn)];
+                }
+            }
+            step[idx] = stp;
+        }
     } else if (recv) {
         inf |= d8sweep::INFO_PART | (1u << (p - 1));
     }
@@ -62,9 +75,9 @@ struct RevSetup {
     uint32_t* flags = nullptr;
     unsigned long long* counts = nullptr;
 };
-// common front part: halo rows of the direction grid, info words (and MODE_DIST's steps)
+// common front part: halo rows of the direction grid (and of MODE_VDIST's elevations), info words (and the distance modes' steps)
 static int rev_prepare(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, int mode, const int32_t* d_src, int32_t src_nodata, int32_t thresh,
-                       const double* dxc, const double* dyc, float* d_step, RevSetup& R, tdx_stats* stats, const char* stage) {
+                       const double* dxc, const double* dyc, float* d_step, RevSetup& R, tdx_stats* stats, const char* stage, float* d_fel = nullptr) {
     hipStream_t s = ctx->stream;
     const int inx = st.nx, iny = st.ny_arr;
     const size_t n = size_t(inx) * size_t(iny);
@@ -91,9 +104,13 @@ static int rev_prepare(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t 
     strip_mark(ctx, st, stage);
     int rc = strip_exchange<int16_t>(ctx, st, d_p, p_nodata);   // p->share()
     if (rc != TDX_OK) return rc;
+    if (mode == MODE_VDIST) {
+        rc = strip_exchange<float>(ctx, st, d_fel, TDX_ANG_NODATA);   // fel->share(): the receiver of a boundary cell lies in the halo row
+        if (rc != TDX_OK) return rc;
+    }
     TdxSpan sp(ctx, TDX_K_STENCIL);
-    hipLaunchKernelGGL(setup_kernel, dim3((inx + 63) / 64, (iny + 3) / 4), dim3(256), 0, s, d_p, inx, iny, p_nodata, mode, d_src, src_nodata, thresh, d_dist, st.y0,
-                       st.y1, R.info, d_step);
+    hipLaunchKernelGGL(setup_kernel, dim3((inx + 63) / 64, (iny + 3) / 4), dim3(256), 0, s, d_p, inx, iny, p_nodata, mode, d_src, src_nodata, thresh, d_dist, d_fel,
+                       st.y0, st.y1, R.info, d_step);
     if (stats) stats->launches[TDX_K_STENCIL]++;
     return TDX_OK;
 }

@@ -1,4 +1,4 @@
-// D8HDistToStrm (distgrid, src/D8HDistToStrm.cpp:57-260) and GageWatershed (gagewatershed, src/gagewatershed.cpp:56-360) on gfx950: the
+// D8HDistToStrm (distgrid, src/D8HDistToStrm.cpp:57-260), D8VDistToStrm (d8vdistdown, src/D8VDistToStrm.cpp:58-276) and GageWatershed (gagewatershed, src/gagewatershed.cpp:56-360) on gfx950: the
 // D8 tools that sweep the D8 dependency graph in REVERSE.
 //
 // Both are a Kahn queue in the reference that starts at the sources (stream cells / gauges) and walks upstream: a cell's value comes
@@ -7,7 +7,8 @@
 // Only one receiver slot is ever on and no proportion is used.
 //   D8DistAlg: a float record.  Stream cells evaluate to 0; any other cell to (float)(dist[j][p] + its receiver's distance), nodata
 //     where the receiver's is (src/D8HDistToStrm.cpp:171-180).  The step dist[j][p] is the cell's own input record (made by the set-up),
-//     so an evaluation is one float add.  Cells never released - draining off the raster, into a nodata cell that is not a stream
+//     so an evaluation is one float add.  D8VDistToStrm is the same policy with the step fel - fel(receiver) (float, no nodata test:
+//     src/D8VDistToStrm.cpp:191-198).  Cells never released - draining off the raster, into a nodata cell that is not a stream
 //     cell, around a cycle - finish as nodata, as in the reference.
 //   GageAlg: an int32 record that carries the INDEX of the outlet (0 .. n - 1) whose gauge labels the cell, mapped to the user's id
 //     when the result is unpacked (an arbitrary id could collide with the pending pattern).  Gauges are seeded and never evaluated; a
@@ -132,8 +133,9 @@ __global__ __launch_bounds__(256) void gw_unpack_kernel(int32_t* __restrict__ re
     rec[i] = (!d8sweep::pending(__int_as_float(v)) && v >= 0 && v < nout) ? ids[v] : GW_NODATA;
 }
 
+// d_fel != nullptr: D8VDistToStrm (the step is the drop to the receiver; dxc / dyc are not used), else D8HDistToStrm
 int d8dist_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, const int32_t* d_src, int32_t src_nodata, int32_t thresh, const double* dxc,
-                const double* dyc, float* d_dist, tdx_stats* stats) {
+                const double* dyc, float* d_dist, tdx_stats* stats, float* d_fel = nullptr) {
     TDX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t n = size_t(st.nx) * size_t(st.ny_arr);
@@ -141,7 +143,8 @@ int d8dist_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodat
     float* step = static_cast<float*>(ctx->scratch(TDX_S_B, n * 4));
     if (!step) return TDX_ERR_NOMEM;
     RevSetup R;
-    int rc = rev_prepare(ctx, st, d_p, p_nodata, MODE_DIST, d_src, src_nodata, thresh, dxc, dyc, step, R, stats, "d8hdisttostrm");
+    int rc = rev_prepare(ctx, st, d_p, p_nodata, d_fel ? MODE_VDIST : MODE_DIST, d_src, src_nodata, thresh, dxc, dyc, step, R, stats,
+                         d_fel ? "d8vdisttostrm" : "d8hdisttostrm", d_fel);
     if (rc != TDX_OK) return rc;
     hipLaunchKernelGGL(d8sweep::init_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, R.info, d_dist, first, nown, TDX_ANG_NODATA);
     rc = strip_exchange<float>(ctx, st, d_dist, TDX_ANG_NODATA);
@@ -269,6 +272,40 @@ extern "C" int tdx_d8hdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx,
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, src, n * 4, hipMemcpyHostToDevice, ctx->stream));
     const int rc = tdx_d8hdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_s, src_nodata, thresh, dxc, dyc, d_o, stats);
+    if (rc != TDX_OK) return rc;
+    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dist, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDX_OK;
+}
+
+// D8VDistToStrm (d8vdistdown, src/D8VDistToStrm.cpp:58-276): the same sweep with the drop to the receiver as the step.  fel's halo rows are
+// exchanged by the set-up, so the strip form writes them.
+extern "C" int tdx_d8vdisttostrm_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_fel, const int32_t* d_src,
+                                     int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats) {
+    if (!ctx || !d_p || !d_fel || !d_src || !d_dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm_dev: bad argument");
+    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    return d8dist_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_src, src_nodata, thresh, nullptr, nullptr, d_dist, stats,
+                       const_cast<float*>(d_fel));   // (a single strip has no halo rows: nothing is written)
+}
+extern "C" int tdx_d8vdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, float* d_fel,
+                                       const int32_t* d_src, int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats) {
+    if (!ctx || !d_p || !d_fel || !d_src || !d_dist || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm_strip: bad argument");
+    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    return d8dist_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_src, src_nodata, thresh, nullptr, nullptr, d_dist, stats, d_fel);
+}
+extern "C" int tdx_d8vdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* fel, const int32_t* src,
+                                 int32_t src_nodata, int32_t thresh, float* dist, tdx_stats* stats) {
+    if (!ctx || !p || !fel || !src || !dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm: bad argument");
+    const size_t n = size_t(nx) * size_t(ny);
+    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
+    int32_t* d_s = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
+    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
+    float* d_f = static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4));
+    if (!d_p || !d_s || !d_o || !d_f) return TDX_ERR_NOMEM;
+    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
+    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, src, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_f, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = tdx_d8vdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_f, d_s, src_nodata, thresh, d_o, stats);
     if (rc != TDX_OK) return rc;
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(dist, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

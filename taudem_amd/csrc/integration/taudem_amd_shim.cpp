@@ -6,7 +6,7 @@
 // mains call (prototypes: src/flood.h:1-2, src/d8.h:5, src/aread8.h:3, src/tardemlib.h:70, src/areadinf.h:2,
 // src/dinfdecayaccum.cpp:61-62, src/gridnet.cpp:54-55, src/Threshold.cpp:49, src/D8flowpathextremeup.cpp:58,
 // src/DinfUpDependence.cpp:52, src/DinfRevAccum.cpp:51, src/DinfDistDown.cpp:66-67, src/DinfDistUp.cpp:65-66,
-// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56, src/retlimro.h, src/DinfAvalanche.cpp:62-63) forwards to the
+// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56, src/flowdircond.cpp:54, src/D8VDistToStrm.cpp:58, src/SlopeAveDown.cpp:59, src/retlimro.h, src/DinfAvalanche.cpp:62-63) forwards to the
 // file-level C ABI, and nameadd() (src/commonLib.cpp:53-73, the only other symbol the mains use) is provided here.  No MPI and
 // no GDAL at link time (their headers are only needed to COMPILE the mains, which include commonLib.h).
 // oracle/Makefile builds oracle/_ref/shim_<tool> this way; tests/test_gpu_cli.py runs them against the reference's rasters.
@@ -46,6 +46,12 @@ int distgrid(char* pfile, char* srcfile, char* distfile, int thresh)
 { return tdx_tool_d8hdisttostrm(pfile, srcfile, distfile, thresh); }
 int gagewatershed(char* pfile, char* wfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* idfile, int writeid, int writeupid, char* upidfile)
 { return tdx_tool_gagewatershed(pfile, wfile, datasrc, lyrname, uselyrname, lyrno, idfile, writeid, writeupid, upidfile); }
+int flowdircond(char* pfile, char* zfile, char* zfdcfile)
+{ return tdx_tool_flowdircond(pfile, zfile, zfdcfile); }
+int d8vdistdown(char* pfile, char* felfile, char* srcfile, char* distfile, int thresh)
+{ return tdx_tool_d8vdisttostrm(pfile, felfile, srcfile, distfile, thresh); }
+int sloped(char* pfile, char* felfile, char* slpdfile, double dn)
+{ return tdx_tool_slopeavedown(pfile, felfile, slpdfile, dn); }
 int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile, char* dgfile, int useOutlets, int contcheck, float cSol)
 { return tdx_tool_dinfconclimaccum(angfile, ctptfile, dmfile, datasrc, lyrname, uselyrname, lyrno, qfile, dgfile, useOutlets, contcheck, cSol); }
 int tlaccum(char* angfile, char* tsupfile, char* tcfile, char* tlafile, char* depfile, char* cinfile, char* coutfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, int useOutlets, int usec, int contcheck)

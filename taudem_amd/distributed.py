@@ -509,6 +509,42 @@ class StripPipeline:
                                                     C.c_void_p(dyc.ctypes.data), _tptr(dist, torch.float32, self.shape, "dist"), C.byref(st)), self.ctx._h)
         return dist, st.as_dict()
 
+    def d8vdisttostrm(self, p, fel, src, thresh=1, *, nodata=-32768, src_nodata=-2147483647):
+        """dist = d8vdistdown(p, fel, src) on this strip (src/D8VDistToStrm.cpp:58).  fel's halo rows are exchanged (written) by the call."""
+        torch = self.torch
+        dist = self.empty(torch.float32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_d8vdisttostrm_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                    _tptr(fel, torch.float32, self.shape, "fel"), _tptr(src, torch.int32, self.shape, "src"), int(src_nodata),
+                                                    int(thresh), _tptr(dist, torch.float32, self.shape, "dist"), C.byref(st)), self.ctx._h)
+        return dist, st.as_dict()
+
+    def flowdircond(self, p, z, *, nodata=-32768, z_nodata=-3.0e38):
+        """zfdc = flowdircond(p, z) on this strip (src/flowdircond.cpp:54)."""
+        torch = self.torch
+        out = self.empty(torch.float32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_flowdircond_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                  _tptr(z, torch.float32, self.shape, "z"), float(z_nodata), _tptr(out, torch.float32, self.shape, "zfdc"),
+                                                  C.byref(st)), self.ctx._h)
+        return out, st.as_dict()
+
+    def slopeavedown(self, p, fel, dn, niter, *, dx=1.0, dy=1.0, nodata=-32768, fel_nodata=-3.0e38):
+        """slpd = sloped(p, fel, dn) on this strip (src/SlopeAveDown.cpp:59).  niter: the pass count of the WHOLE raster
+        (int(dn / min(dx, dy) of its middle row) + 1); the record halo rows are exchanged after every pass."""
+        torch = self.torch
+        dxc, dyc = self._cells(dx, dy)
+        out = self.empty(torch.float32)
+        st = TdxStats()
+        torch.cuda.synchronize(self.ctx.device)
+        check(self.ctx._lib.tdx_slopeavedown_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
+                                                   _tptr(fel, torch.float32, self.shape, "fel"), float(fel_nodata), C.c_void_p(dxc.ctypes.data),
+                                                   C.c_void_p(dyc.ctypes.data), float(dn), int(niter), _tptr(out, torch.float32, self.shape, "slpd"), C.byref(st)),
+              self.ctx._h)
+        return out, st.as_dict()
+
     def gagewatershed(self, p, outlets, *, nodata=-32768):
         """gw, id_table = gagewatershed(p, outlets) on this strip (src/gagewatershed.cpp:56).  outlets: (columns, STRIP-ARRAY rows, ids) of ALL
         outlets (local_outlets(); those outside the owned rows are other ranks'); id_table as Context.gagewatershed's, the same on every rank."""

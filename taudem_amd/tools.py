@@ -116,6 +116,27 @@ def gagewatershed(pfile, wfile, datasrc, lyrname="", uselyrname=0, lyrno=0, idfi
                                               int(writeupid), _b(upidfile))
 
 
+def flowdircond(pfile, zfile, zfdcfile):
+    """src/flowdircond.cpp:54 (FlowDirCond)"""
+    return _lib.load().tdx_tool_flowdircond(_b(pfile), _b(zfile), _b(zfdcfile))
+
+
+def d8vdistdown(pfile, felfile, srcfile, distfile, thresh=1):
+    """src/D8VDistToStrm.cpp:58 (D8VDistToStrm)"""
+    return _lib.load().tdx_tool_d8vdisttostrm(_b(pfile), _b(felfile), _b(srcfile), _b(distfile), int(thresh))
+
+
+d8vdisttostrm = d8vdistdown
+
+
+def sloped(pfile, felfile, slpdfile, dn=50.0):
+    """src/SlopeAveDown.cpp:59 (SlopeAveDown; a dn that is negative or not finite is refused)"""
+    return _lib.load().tdx_tool_slopeavedown(_b(pfile), _b(felfile), _b(slpdfile), float(dn))
+
+
+slopeavedown = sloped
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
