@@ -2,28 +2,42 @@
 // reference's tool functions, with the compute part on the GPU.  `tool --gpus N` / TAUDEM_AMD_GPUS=N / tdx_tool_set_gpus(N)
 // partitions the raster into N row strips, one GPU (and one host thread) each, exchanging boundary rows over RCCL
 // (tool_strips.hpp, comm.cpp) - the place of `mpiexec -n N` in the reference.
-//   tdx_tool_pitremove       <- flood()     src/flood.cpp:50-526
-//   tdx_tool_d8flowdir       <- setdird8()  src/d8.cpp:181-355
-//   tdx_tool_aread8          <- aread8()    src/aread8.cpp:56-322
-//   tdx_tool_dinfflowdir     <- setdir()    src/dinf.cpp:109-284
-//   tdx_tool_areadinf        <- area()      src/areadinf.cpp:53-300
-//   tdx_tool_dinfdecayaccum  <- dmarea()    src/dinfdecayaccum.cpp:61-324
-//   tdx_tool_dinfconclimaccum  <- dsllArea()  src/DinfConcLimAccum.cpp:61-326
-//   tdx_tool_dinftranslimaccum <- tlaccum()   src/DinfTransLimAccum.cpp:61-372
-//   tdx_tool_dinfdistdown    <- dinfdistdown()  src/DinfDistDown.cpp:66-1060
-//   tdx_tool_dinfdistup      <- dinfdistup()    src/DinfDistUp.cpp:65-1214
-//   tdx_tool_d8hdisttostrm   <- distgrid()      src/D8HDistToStrm.cpp:57-260
-//   tdx_tool_gagewatershed   <- gagewatershed() src/gagewatershed.cpp:56-360
-//   tdx_tool_flowdircond     <- flowdircond()   src/flowdircond.cpp:54-252
-//   tdx_tool_d8vdisttostrm   <- d8vdistdown()   src/D8VDistToStrm.cpp:58-276
-//   tdx_tool_slopeavedown    <- sloped()        src/SlopeAveDown.cpp:59-330
+//
+// Every tool function runs on one frame, ToolRun: banner, input() per raster (compared with the first one, under the tool's mismatch
+// policy), outlets(), read_done(), compute(one GPU: tdx_x() on a context of its own; N GPUs: tdx_x_strip() on strip arrays),
+// output() per raster, finish(footer).  A tool function states what is its own: which rasters as which type and in which order,
+// the two library calls, which header and nodata value each output carries, and the footer's wording.
+//   tdx_tool_pitremove           <- flood()               src/flood.cpp:50-526
+//   tdx_tool_d8flowdir           <- setdird8()            src/d8.cpp:181-355
+//   tdx_tool_dinfflowdir         <- setdir()              src/dinf.cpp:109-284
+//   tdx_tool_aread8              <- aread8()              src/aread8.cpp:56-322
+//   tdx_tool_areadinf            <- area()                src/areadinf.cpp:53-300
+//   tdx_tool_dinfdecayaccum      <- dmarea()              src/dinfdecayaccum.cpp:61-324
+//   tdx_tool_gridnet             <- gridnet()             src/gridnet.cpp:54-510
+//   tdx_tool_d8flowpathextremeup <- d8flowpathextremeup() src/D8flowpathextremeup.cpp:58-285
+//   tdx_tool_threshold           <- threshold()           src/Threshold.cpp:49-161
+//   tdx_tool_dinfupdependence    <- depgrd()              src/DinfUpDependence.cpp:52-272
+//   tdx_tool_dinfrevaccum        <- dsaccum()             src/DinfRevAccum.cpp:51-290
+//   tdx_tool_dinfconclimaccum    <- dsllArea()            src/DinfConcLimAccum.cpp:61-326
+//   tdx_tool_dinftranslimaccum   <- tlaccum()             src/DinfTransLimAccum.cpp:61-372
+//   tdx_tool_dinfdistdown        <- dinfdistdown()        src/DinfDistDown.cpp:66-1060
+//   tdx_tool_dinfdistup          <- dinfdistup()          src/DinfDistUp.cpp:65-1214
+//   tdx_tool_retlimflow          <- retlimro()            src/RetlimFlow.cpp:53-240
+//   tdx_tool_dinfavalanche       <- avalancherunoutgrd()  src/DinfAvalanche.cpp:62-420
+//   tdx_tool_d8hdisttostrm       <- distgrid()            src/D8HDistToStrm.cpp:57-260
+//   tdx_tool_gagewatershed       <- gagewatershed()       src/gagewatershed.cpp:56-360
+//   tdx_tool_flowdircond         <- flowdircond()         src/flowdircond.cpp:54-252
+//   tdx_tool_d8vdisttostrm       <- d8vdistdown()         src/D8VDistToStrm.cpp:58-276
+//   tdx_tool_slopeavedown        <- sloped()              src/SlopeAveDown.cpp:59-330
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "context.hpp"
@@ -34,6 +48,9 @@
 #define TDVERSION "5.4.0"   /* src/commonLib.h:63 */
 
 namespace {
+
+using toolstrips::Outlets;
+using toolstrips::RankJob;
 
 int g_tool_device = -1;
 int g_tool_gpus = -1;
@@ -58,6 +75,7 @@ bool want_lzw() {
 }
 
 struct Raster {
+    std::string path;
     tdx::RasterInfo info;
     std::vector<float> f;
     std::vector<int16_t> s;
@@ -162,7 +180,7 @@ struct CtxGuard {
 };
 
 // outlets: readoutlets + geoToGlobalXY (src/aread8.cpp:114-136,179-189)
-int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, std::vector<int32_t>& ox, std::vector<int32_t>& oy, std::vector<int32_t>* ids = nullptr) {
+int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, Outlets& o) {
     std::vector<double> x, y; std::vector<int> id; std::string err;
     if (!tdx::read_outlets(datasrc, x, y, id, err)) {
         printf("Error Opening OGR Data Source .\n");
@@ -172,13 +190,13 @@ int load_outlets(const char* datasrc, const tdx::RasterInfo& ri, std::vector<int
         return TDX_ERR_OUTLETS;
     }
     printf("Warning: Spatial References of Outlet feature and Raster data are missing.\n");
-    ox.resize(x.size()); oy.resize(x.size());
+    o.x.resize(x.size()); o.y.resize(x.size());
     for (size_t i = 0; i < x.size(); i++) {
         int gx, gy;
         tdx::geo_to_global_xy(x[i], y[i], ri.xleftedge, ri.ytopedge, ri.dlon, ri.dlat, gx, gy);
-        ox[i] = gx; oy[i] = gy;
+        o.x[i] = gx; o.y[i] = gy;
     }
-    if (ids) ids->assign(id.begin(), id.end());
+    o.ids.assign(id.begin(), id.end());
     return TDX_OK;
 }
 
@@ -190,933 +208,204 @@ void print_gpu_stats(const char* tool, const tdx_stats& st, int64_t cells) {
             (long long)st.flats_initial, (long long)st.levels_fall, (long long)st.levels_rise);
 }
 
+// What a tool does with a raster that does not match its first one (tiffIO::compareTiff returned false)
+enum class Mismatch {
+    Sizes,       // "File sizes do not match" + the file + MPI_Abort(MCW, 5): most tools (e.g. src/gridnet.cpp:147-152)
+    Silent,      // return 1 without a word (src/Threshold.cpp:90, src/DinfUpDependence.cpp:103, src/areadinf.cpp:134)
+    PitRemove,   // flood()'s own sentence, return 1
+    Avalanche    // both file names, return 1: the MPI_Abort is commented out in the reference (src/DinfAvalanche.cpp)
+};
+
+// The timing blocks the reference's tools end with
+enum class Footer {
+    Times,         // <label>: N + read / compute / write / total
+    HeaderTimes,   // PitRemove: a header read time of its own (src/flood.cpp:517-519)
+    FlowDir,       // D8FlowDir / DinfFlowDir: slopes and flats apart, the slope raster written in between (src/d8.cpp, src/dinf.cpp)
+    CountOnly      // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
+};
+
+template <class T> constexpr tdx::DType dtype_of();
+template <> constexpr tdx::DType dtype_of<float>() { return tdx::DType::F32; }
+template <> constexpr tdx::DType dtype_of<int16_t>() { return tdx::DType::I16; }
+template <> constexpr tdx::DType dtype_of<int32_t>() { return tdx::DType::I32; }
+
+// One call of a tool function: banner, read, compute, write, footer.  A step that fails leaves its code in `rc`, and every later
+// input() / outlets() / output() does nothing, so that a tool checks once per phase: read_done(), compute(), finish().
+struct ToolRun {
+    double begint, readt = 0, computet = 0;
+    const Raster* grid = nullptr;   // the first raster read: every other one is compared with it, and it gives the strips their rows
+    int nproc = 1;                  // GPUs (row strips) of the compute step: the count that is printed is the count that ran
+    tdx_stats st{};
+    int rc = TDX_OK;
+    std::optional<CtxGuard> ctx;    // the one-GPU context: it lives until the tool function returns, after the footer's times are taken
+
+    explicit ToolRun(const std::string& name) {
+        printf("%s version %s\n", name.c_str(), TDVERSION);
+        fflush(stdout);
+        begint = now_s();
+    }
+    size_t cells() const { return size_t(grid->info.nx) * size_t(grid->info.ny); }
+
+    void input(const char* path, tdx::DType type, Raster& r, Mismatch policy = Mismatch::Sizes) {
+        if (rc != TDX_OK) return;
+        r.path = path;
+        rc = load_raster(path, type, r);
+        if (rc != TDX_OK) return;
+        if (!grid) { grid = &r; return; }
+        if (compare_rasters(grid->info, grid->path.c_str(), r.info, path)) return;
+        switch (policy) {
+        case Mismatch::Sizes: printf("File sizes do not match\n%s\n", path); rc = TDX_ERR_OUTLETS; break;
+        case Mismatch::Silent: rc = TDX_ERR_MISMATCH; break;
+        case Mismatch::PitRemove:
+            printf("Error: depression mask and input DEM are not similar. Files must have the same number of rows/columns.\n");
+            rc = TDX_ERR_MISMATCH;
+            break;
+        case Mismatch::Avalanche: printf("File sizes do not match\n%s\n%s\n", path, grid->path.c_str()); rc = 1; break;
+        }
+        fflush(stdout);
+    }
+    // use == 1: read the outlet file; the library is given outlets whenever use is not 0
+    void outlets(const char* datasrc, int use, Outlets& o) {
+        if (rc != TDX_OK) return;
+        o.use = use != 0;
+        if (use == 1) rc = load_outlets(datasrc, grid->info, o);
+    }
+    bool read_done() { readt = now_s(); return rc == TDX_OK; }
+
+    // one(ctx, stats): the host form tdx_x() on a context of its own, for one GPU.  strip(job, stats): tdx_x_strip() on the job's strip
+    // arrays, for N GPUs; nullptr for a tool that has no strip form.
+    template <class One, class Strip>
+    bool compute(One one, Strip strip) {
+        if constexpr (!std::is_same<Strip, std::nullptr_t>::value) {
+            nproc = int(std::min<int64_t>(tool_gpus(), grid->info.ny));   // at least one row per rank
+            if (nproc > 1) {
+                rc = toolstrips::run(nproc, tool_device(), grid->info.nx, grid->info.ny, grid->info.dxc, grid->info.dyc, &st, strip);
+                computet = now_s();
+                return rc == TDX_OK;
+            }
+        }
+        ctx.emplace();
+        if (ctx->rc != TDX_OK) { rc = ctx->rc; return false; }
+        rc = one(ctx->c, &st);
+        if (rc != TDX_OK) { report(ctx->c); return false; }
+        computet = now_s();
+        return true;
+    }
+
+    template <class T>
+    void output(const char* path, const std::vector<T>& data, const Raster& like, double nodata) {
+        if (rc == TDX_OK) rc = save_raster(path, dtype_of<T>(), data.data(), like.info, nodata);
+    }
+    // midt: FlowDir only, the time at which the slope raster had been written.  stats_name == nullptr: no statistics line.
+    int finish(const char* label, const char* stats_name, Footer footer = Footer::Times, double midt = 0.0) {
+        if (rc != TDX_OK) return rc;
+        const double writet = now_s(), slope_s = st.ms_kernel[TDX_K_STENCIL] / 1000.0;
+        switch (footer) {
+        case Footer::Times:
+            printf("%s: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", label, nproc, readt - begint, computet - readt, writet - computet,
+                   writet - begint);
+            break;
+        case Footer::HeaderTimes:
+            printf("%s: %d\nHeader read time: %f\nData read time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", label, nproc, 0.0, readt - begint,
+                   computet - readt, writet - computet, writet - begint);
+            break;
+        case Footer::FlowDir:
+            printf("%s: %d\nHeader read time: %f\nData read time: %f\nCompute Slope time: %f\nWrite Slope time: %f\nResolve Flat time: %f\nWrite Flat time: %f\nTotal time: %f\n",
+                   label, nproc, 0.0, readt - begint, slope_s, midt - computet, (computet - readt) - slope_s, writet - midt, writet - begint);
+            break;
+        case Footer::CountOnly: printf("%s: %d\n", label, nproc); break;
+        }
+        if (stats_name) print_gpu_stats(stats_name, st, grid->info.nx * grid->info.ny);
+        return 0;
+    }
+};
+
+constexpr tdx::DType F32 = tdx::DType::F32, I16 = tdx::DType::I16, I32 = tdx::DType::I32;
+
 }  // namespace
 
 extern "C" {
-
-int tdx_tool_gridnet(const char* pfile, const char* plenfile, const char* tlenfile, const char* gordfile, const char* maskfile, const char* datasrc,
-                     const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/, int useMask, int useOutlets, int thresh) {
-    printf("GridNet version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster p, mask;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, p.info, ox, oy); if (rc != TDX_OK) return rc; }   // src/gridnet.cpp:78-120
-    if (useMask == 1) {
-        rc = load_raster(maskfile, tdx::DType::I32, mask);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(p.info, pfile, mask.info, maskfile)) { printf("File sizes do not match\n%s\n", maskfile); fflush(stdout); return TDX_ERR_OUTLETS; }   // src/gridnet.cpp:147-152
-    }
-    const double readt = now_s();
-    const size_t n = p.s.size();
-    std::vector<float> plen(n), tlen(n);
-    std::vector<int16_t> gord(n);
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            int32_t* d_m = useMask ? j.strip<int32_t>(mask.l.data()) : nullptr;
-            float* d_pl = j.strip<float>(nullptr);
-            float* d_tl = j.strip<float>(nullptr);
-            int16_t* d_go = j.strip<int16_t>(nullptr);
-            if (!d_p || !d_pl || !d_tl || !d_go || (useMask && !d_m)) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(p.info.dxc), dys = j.rows_of(p.info.dyc);
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_gridnet_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, (int16_t)p.info.nodata, dxs.data(), dys.data(), d_m, thresh, useOutlets ? ox.data() : nullptr,
-                                            useOutlets ? lrow.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, d_pl, d_tl, d_go, s);
-            if (e != TDX_OK) return e;
-            return (j.fetch(plen.data(), d_pl) && j.fetch(tlen.data(), d_tl) && j.fetch(gord.data(), d_go)) ? TDX_OK : TDX_ERR_HIP;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_gridnet(g.c, p.s.data(), p.info.nx, p.info.ny, (int16_t)p.info.nodata, p.info.dxc.data(), p.info.dyc.data(), useMask ? mask.l.data() : nullptr, thresh,
-                         useOutlets ? ox.data() : nullptr, useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, plen.data(), tlen.data(),
-                         gord.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(gordfile, tdx::DType::I16, gord.data(), p.info, -1.0);   // src/gridnet.cpp:474-481
-    if (rc != TDX_OK) return rc;
-    rc = save_raster(plenfile, tdx::DType::F32, plen.data(), p.info, -1.0);
-    if (rc != TDX_OK) return rc;
-    rc = save_raster(tlenfile, tdx::DType::F32, tlen.data(), p.info, -1.0);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    print_gpu_stats("gridnet", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-int tdx_tool_d8flowpathextremeup(const char* pfile, const char* safile, const char* ssafile, int usemax, const char* datasrc, const char* /*lyrname*/,
-                                 int /*uselyrname*/, int /*lyrno*/, int useOutlets, int contcheck) {
-    printf("D8FlowPathExtremeUp version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster p, sa;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, p.info, ox, oy); if (rc != TDX_OK) return rc; }
-    rc = load_raster(safile, tdx::DType::F32, sa);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(p.info, pfile, sa.info, safile)) { printf("File sizes do not match\n%s\n", safile); fflush(stdout); return TDX_ERR_OUTLETS; }   // src/D8flowpathextremeup.cpp:120-125
-    const double readt = now_s();
-    std::vector<float> ssa(p.s.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            float* d_sa = j.strip<float>(sa.f.data());
-            float* d_out = j.strip<float>(nullptr);
-            if (!d_p || !d_sa || !d_out) return TDX_ERR_NOMEM;
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_d8flowpathextremeup_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, (int16_t)p.info.nodata, d_sa, usemax, contcheck, useOutlets ? ox.data() : nullptr,
-                                                        useOutlets ? lrow.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, d_out, s);
-            return e != TDX_OK ? e : (j.fetch(ssa.data(), d_out) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_d8flowpathextremeup(g.c, p.s.data(), p.info.nx, p.info.ny, (int16_t)p.info.nodata, sa.f.data(), usemax, contcheck,
-                                     useOutlets ? ox.data() : nullptr, useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, ssa.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(ssafile, tdx::DType::F32, ssa.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT = -FLT_MAX (src/commonLib.h:80)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    print_gpu_stats("d8flowpathextremeup", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-int tdx_tool_threshold(const char* ssafile, const char* srcfile, const char* maskfile, float thresh, int usemask) {
-    printf("Threshold version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster ssa, mask;
-    int rc = load_raster(ssafile, tdx::DType::F32, ssa);
-    if (rc != TDX_OK) return rc;
-    if (usemask == 1) {
-        rc = load_raster(maskfile, tdx::DType::F32, mask);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ssa.info, ssafile, mask.info, maskfile)) return TDX_ERR_MISMATCH;   // src/Threshold.cpp:90
-    }
-    const double readt = now_s();
-    CtxGuard g;
-    if (g.rc != TDX_OK) return g.rc;
-    std::vector<int16_t> src(ssa.f.size());
-    tdx_stats st;
-    rc = tdx_threshold(g.c, ssa.f.data(), ssa.info.nx, ssa.info.ny, (float)ssa.info.nodata, usemask ? mask.f.data() : nullptr, thresh, src.data(), &st);
-    if (rc != TDX_OK) { fprintf(stderr, "taudem_amd: %s\n", tdx_last_error(g.c)); return rc; }
-    const double computet = now_s();
-    rc = save_raster(srcfile, tdx::DType::I16, src.data(), ssa.info, -32768.0);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", 1, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    return 0;
-}
-
-int tdx_tool_dinfupdependence(const char* angfile, const char* dgfile, const char* depfile) {
-    printf("DinfUpDependence version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster ang, dg;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(dgfile, tdx::DType::I32, dg);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, dg.info, dgfile)) return TDX_ERR_MISMATCH;   // src/DinfUpDependence.cpp:103
-    const double readt = now_s();
-    std::vector<float> dep(ang.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            int32_t* d_dg = j.strip<int32_t>(dg.l.data());
-            float* d_dep = j.strip<float>(nullptr);
-            if (!d_ang || !d_dg || !d_dep) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_dinfupdependence_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_dg, d_dep, s);
-            return e != TDX_OK ? e : (j.fetch(dep.data(), d_dep) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfupdependence(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), dg.l.data(), dep.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(depfile, tdx::DType::F32, dep.data(), ang.info, -1.0);   // depNodata = -1 (src/DinfUpDependence.cpp:113)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfupdependence", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/,
-                              int /*lyrno*/, const char* qfile, const char* dgfile, int useOutlets, int contcheck, float cSol) {
-    printf("DinfConcLimAccum version %s\n", TDVERSION);
-    const double begint = now_s();
-    Raster ang, dm, dg, q;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, ang.info, ox, oy); if (rc != TDX_OK) return rc; }
-    rc = load_raster(dmfile, tdx::DType::F32, dm);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, dm.info, dmfile)) { printf("File sizes do not match\n%s\n", dmfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    rc = load_raster(dgfile, tdx::DType::I16, dg);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, dg.info, dgfile)) { printf("File sizes do not match\n%s\n", dgfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    rc = load_raster(qfile, tdx::DType::F32, q);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, q.info, qfile)) { printf("File sizes do not match\n%s\n", qfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    const double readt = now_s();
-    std::vector<float> out(ang.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_dm = j.strip<float>(dm.f.data());
-            float* d_q = j.strip<float>(q.f.data());
-            int16_t* d_dg = j.strip<int16_t>(dg.s.data());
-            float* d_out = j.strip<float>(nullptr);
-            if (!d_ang || !d_dm || !d_q || !d_dg || !d_out) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_dinfconclimaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_dm, (float)dm.info.nodata, d_dg,
-                                                     d_q, (float)q.info.nodata, cSol, contcheck, useOutlets ? ox.data() : nullptr, useOutlets ? lrow.data() : nullptr,
-                                                     useOutlets ? int64_t(ox.size()) : -1, d_out, s);
-            return e != TDX_OK ? e : (j.fetch(out.data(), d_out) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfconclimaccum(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), dm.f.data(),
-                                  (float)dm.info.nodata, dg.s.data(), q.f.data(), (float)q.info.nodata, cSol, contcheck, useOutlets ? ox.data() : nullptr,
-                                  useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, out.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(ctptfile, tdx::DType::F32, out.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfconclimaccum", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-int tdx_tool_dinftranslimaccum(const char* angfile, const char* tsupfile, const char* tcfile, const char* tlafile, const char* depfile, const char* cinfile,
-                               const char* coutfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/, int useOutlets, int usec,
-                               int contcheck) {
-    printf("DinfTransLimAccum version %s\n", TDVERSION);
-    const double begint = now_s();
-    Raster ang, tsup, tc, cin;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, ang.info, ox, oy); if (rc != TDX_OK) return rc; }
-    rc = load_raster(tsupfile, tdx::DType::F32, tsup);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, tsup.info, tsupfile)) { printf("File sizes do not match\n%s\n", tsupfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    rc = load_raster(tcfile, tdx::DType::F32, tc);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, tc.info, tcfile)) { printf("File sizes do not match\n%s\n", tcfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    if (usec == 1) {
-        rc = load_raster(cinfile, tdx::DType::F32, cin);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, cin.info, cinfile)) { printf("File sizes do not match\n%s\n", cinfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    }
-    const double readt = now_s();
-    std::vector<float> tla(ang.f.size()), dep(ang.f.size()), cso(usec ? ang.f.size() : 0);
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_ts = j.strip<float>(tsup.f.data());
-            float* d_tc = j.strip<float>(tc.f.data());
-            float* d_ci = usec ? j.strip<float>(cin.f.data()) : nullptr;
-            float* d_tla = j.strip<float>(nullptr);
-            float* d_dep = j.strip<float>(nullptr);
-            float* d_co = usec ? j.strip<float>(nullptr) : nullptr;
-            if (!d_ang || !d_ts || !d_tc || !d_tla || !d_dep || (usec && (!d_ci || !d_co))) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_dinftranslimaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_ts, (float)tsup.info.nodata, d_tc,
-                                                      (float)tc.info.nodata, d_ci, usec ? (float)cin.info.nodata : 0.f, contcheck, useOutlets ? ox.data() : nullptr,
-                                                      useOutlets ? lrow.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, d_tla, d_dep, d_co, s);
-            if (e != TDX_OK) return e;
-            if (!j.fetch(tla.data(), d_tla) || !j.fetch(dep.data(), d_dep) || (usec && !j.fetch(cso.data(), d_co))) return TDX_ERR_HIP;
-            return TDX_OK;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinftranslimaccum(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), tsup.f.data(),
-                                   (float)tsup.info.nodata, tc.f.data(), (float)tc.info.nodata, usec ? cin.f.data() : nullptr, usec ? (float)cin.info.nodata : 0.f,
-                                   contcheck, useOutlets ? ox.data() : nullptr, useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, tla.data(),
-                                   dep.data(), usec ? cso.data() : nullptr, &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(tlafile, tdx::DType::F32, tla.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    rc = save_raster(depfile, tdx::DType::F32, dep.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    if (usec == 1) {
-        rc = save_raster(coutfile, tdx::DType::F32, cso.data(), ang.info, (double)TDX_ANG_NODATA);
-        if (rc != TDX_OK) return rc;
-    }
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinftranslimaccum", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-int tdx_tool_dinfrevaccum(const char* angfile, const char* wgfile, const char* raccfile, const char* dmaxfile) {
-    printf("DinfRevAccum version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster ang, w;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(wgfile, tdx::DType::F32, w);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, w.info, wgfile)) { printf("File sizes do not match\n%s\n", wgfile); fflush(stdout); return TDX_ERR_OUTLETS; }   // src/DinfRevAccum.cpp:94-99
-    const double readt = now_s();
-    const size_t n = ang.f.size();
-    std::vector<float> racc(n), dmax(n);
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_w = j.strip<float>(w.f.data());
-            float* d_r = j.strip<float>(nullptr);
-            float* d_m = j.strip<float>(nullptr);
-            if (!d_ang || !d_w || !d_r || !d_m) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_dinfrevaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_w, (float)w.info.nodata, d_r, d_m, s);
-            if (e != TDX_OK) return e;
-            return (j.fetch(racc.data(), d_r) && j.fetch(dmax.data(), d_m)) ? TDX_OK : TDX_ERR_HIP;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfrevaccum(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), w.f.data(),
-                              (float)w.info.nodata, racc.data(), dmax.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(raccfile, tdx::DType::F32, racc.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfRevAccum.cpp:253-258)
-    if (rc != TDX_OK) return rc;
-    rc = save_raster(dmaxfile, tdx::DType::F32, dmax.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfrevaccum", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-// dinfdistdown() (src/DinfDistDown.cpp:66-91) and its four tool functions: files in the reference's order (ang, then fel for v / p / s, w
-// for h / p / s when used, src), each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); slpfile is never read
-int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* srcfile, const char* dtsfile,
-                          int statmethod, int typemethod, int usew, int concheck) {
-    static const char* const banner[4] = {"-h", "-v", "-p", "-s"};
-    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
-    printf("DinfDistDown %s version %s\n", banner[typemethod], TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;   // (v: the weight code is commented out in the reference)
-    Raster ang, fel, w, src;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
-    if (use_fel) {
-        rc = load_raster(felfile, tdx::DType::F32, fel);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, fel.info, felfile)) return mismatch(felfile);
-    }
-    if (use_w) {
-        rc = load_raster(wfile, tdx::DType::F32, w);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, w.info, wfile)) return mismatch(wfile);
-    }
-    rc = load_raster(srcfile, tdx::DType::I16, src);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, src.info, srcfile)) return mismatch(srcfile);
-    const double readt = now_s();
-    std::vector<float> dd(ang.f.size());
-    const float fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_fel = use_fel ? j.strip<float>(fel.f.data()) : nullptr;
-            float* d_w = use_w ? j.strip<float>(w.f.data()) : nullptr;
-            int16_t* d_src = j.strip<int16_t>(src.s.data());
-            float* d_dd = j.strip<float>(nullptr);
-            if (!d_ang || (use_fel && !d_fel) || (use_w && !d_w) || !d_src || !d_dd) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_dinfdistdown_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, fel_nd, d_src, d_w, w_nd,
-                                                 statmethod, typemethod, concheck, d_dd, s);
-            return e != TDX_OK ? e : (j.fetch(dd.data(), d_dd) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfdistdown(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(),
-                              use_fel ? fel.f.data() : nullptr, fel_nd, src.s.data(), use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, dd.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(dtsfile, tdx::DType::F32, dd.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistDown.cpp:363-365)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfdistdown", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-// dinfdistup() (src/DinfDistUp.cpp:65-90) and its four tool functions: files in the reference's order (ang, then fel for v / p / s, w for
-// h / p / s when used), each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); slpfile is never read
-int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* rtrfile, int statmethod,
-                        int typemethod, int usew, int concheck, float thresh) {
-    static const char* const banner[4] = {"-h", "-v", "-p", "-s"};
-    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
-    printf("DinfDistUp %s version %s\n", banner[typemethod], TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;   // (v: the weight code is commented out in the reference)
-    Raster ang, fel, w;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
-    if (use_fel) {
-        rc = load_raster(felfile, tdx::DType::F32, fel);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, fel.info, felfile)) return mismatch(felfile);
-    }
-    if (use_w) {
-        rc = load_raster(wfile, tdx::DType::F32, w);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, w.info, wfile)) return mismatch(wfile);
-    }
-    const double readt = now_s();
-    std::vector<float> du(ang.f.size());
-    const float fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_fel = use_fel ? j.strip<float>(fel.f.data()) : nullptr;
-            float* d_w = use_w ? j.strip<float>(w.f.data()) : nullptr;
-            float* d_du = j.strip<float>(nullptr);
-            if (!d_ang || (use_fel && !d_fel) || (use_w && !d_w) || !d_du) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_dinfdistup_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, fel_nd, d_w, w_nd, statmethod,
-                                               typemethod, concheck, thresh, d_du, s);
-            return e != TDX_OK ? e : (j.fetch(du.data(), d_du) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfdistup(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), use_fel ? fel.f.data() : nullptr,
-                            fel_nd, use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, thresh, du.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(rtrfile, tdx::DType::F32, du.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistUp.cpp:321-322)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfdistup", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-// retlimro() (src/RetlimFlow.cpp:53-240): ang, wg, rc, each compared with ang (File sizes do not match + MPI_Abort(MCW, 5)); the output header is rc's
-int tdx_tool_retlimflow(const char* angfile, const char* wgfile, const char* rcfile, const char* qrlfile) {
-    printf("Retention limited flow accumulation version %s\n", TDVERSION);
-    fflush(stdout);
-    Raster ang, wg, rcg;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    auto mismatch = [](const char* f) { printf("File sizes do not match\n%s\n", f); fflush(stdout); return TDX_ERR_OUTLETS; };
-    rc = load_raster(wgfile, tdx::DType::F32, wg);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, wg.info, wgfile)) return mismatch(wgfile);
-    rc = load_raster(rcfile, tdx::DType::F32, rcg);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, rcg.info, rcfile)) return mismatch(rcfile);
-    std::vector<float> qrl(ang.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_wg = j.strip<float>(wg.f.data());
-            float* d_rc = j.strip<float>(rcg.f.data());
-            float* d_q = j.strip<float>(nullptr);
-            if (!d_ang || !d_wg || !d_rc || !d_q) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_retlimflow_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_wg, (float)wg.info.nodata, d_rc,
-                                               (float)rcg.info.nodata, d_q, s);
-            return e != TDX_OK ? e : (j.fetch(qrl.data(), d_q) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_retlimflow(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), wg.f.data(),
-                            (float)wg.info.nodata, rcg.f.data(), (float)rcg.info.nodata, qrl.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    rc = save_raster(qrlfile, tdx::DType::F32, qrl.data(), rcg.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of rc (src/RetlimFlow.cpp:233-235)
-    if (rc != TDX_OK) return rc;
-    printf("Processors: %d\n", nproc);   // (the reference prints no times for this tool; the count that ran, as the other tools say it)
-    print_gpu_stats("retlimflow", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-// avalancherunoutgrd() (src/DinfAvalanche.cpp:62-420): ang, fel, ass (SHORT), each compared with ang; a mismatch RETURNS 1 here (the MPI_Abort is
-// commented out in the reference).  -direct reads the file's coordinates: the geotransform goes to the library.
-int tdx_tool_dinfavalanche(const char* angfile, const char* felfile, const char* assfile, const char* rzfile, const char* dmfile, float thresh, float alpha, int path) {
-    printf("DinfAvalanche version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster ang, fel, ass;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(felfile, tdx::DType::F32, fel);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, fel.info, felfile)) { printf("File sizes do not match\n%s\n%s\n", felfile, angfile); fflush(stdout); return 1; }
-    rc = load_raster(assfile, tdx::DType::I16, ass);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, ass.info, assfile)) { printf("File sizes do not match\n%s\n%s\n", assfile, angfile); fflush(stdout); return 1; }
-    const double readt = now_s();
-    std::vector<float> rz(ang.f.size()), dfs(ang.f.size());
-    const double geo[4] = {ang.info.xleftedge, ang.info.ytopedge, ang.info.dlon, ang.info.dlat};
-    const int geographic = ang.info.geographic ? 1 : 0;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_fel = j.strip<float>(fel.f.data());
-            int16_t* d_ass = j.strip<int16_t>(ass.s.data());
-            float* d_rz = j.strip<float>(nullptr);
-            float* d_dfs = j.strip<float>(nullptr);
-            if (!d_ang || !d_fel || !d_ass || !d_rz || !d_dfs) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const int e = tdx_dinfavalanche_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_fel, (float)fel.info.nodata, d_ass,
-                                                  (int16_t)ass.info.nodata, thresh, alpha, path, geo, geographic, j.y0, j.ny, d_rz, d_dfs, s);
-            if (e != TDX_OK) return e;
-            return j.fetch(rz.data(), d_rz) && j.fetch(dfs.data(), d_dfs) ? TDX_OK : TDX_ERR_HIP;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfavalanche(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(), fel.f.data(),
-                               (float)fel.info.nodata, ass.s.data(), (int16_t)ass.info.nodata, thresh, alpha, path, geo, geographic, rz.data(), dfs.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(rzfile, tdx::DType::F32, rz.data(), ang.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of ang (src/DinfAvalanche.cpp:384-389)
-    if (rc != TDX_OK) return rc;
-    rc = save_raster(dmfile, tdx::DType::F32, dfs.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("dinfavalanche", st, ang.info.nx * ang.info.ny);
-    return 0;
-}
-
-// distgrid() (src/D8HDistToStrm.cpp:57-260): p, then src read as LONG (File sizes do not match + MPI_Abort(MCW, 5))
-int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh) {
-    printf("D8HDistToStrm version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster p, src;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(srcfile, tdx::DType::I32, src);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(p.info, pfile, src.info, srcfile)) { printf("File sizes do not match\n%s\n", srcfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    const double readt = now_s();
-    std::vector<float> dist(p.s.size());
-    const int16_t p_nd = (int16_t)p.info.nodata;
-    const int32_t s_nd = (int32_t)src.info.nodata;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            int32_t* d_src = j.strip<int32_t>(src.l.data());
-            float* d_dist = j.strip<float>(nullptr);
-            if (!d_p || !d_src || !d_dist) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(p.info.dxc), dys = j.rows_of(p.info.dyc);
-            const int e = tdx_d8hdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_src, s_nd, thresh, dxs.data(), dys.data(), d_dist, s);
-            return e != TDX_OK ? e : (j.fetch(dist.data(), d_dist) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_d8hdisttostrm(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, src.l.data(), s_nd, thresh, p.info.dxc.data(), p.info.dyc.data(), dist.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(distfile, tdx::DType::F32, dist.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8HDistToStrm.cpp:223-225)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("d8hdisttostrm", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-// gagewatershed() (src/gagewatershed.cpp:56-360).  -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  -upid is
-// refused: the reference appends a line per visit of a nodata neighbour in queue order (:246-253), which depends on the schedule.
-int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/,
-                           const char* idfile, int writeid, int writeupid, const char* /*upidfile*/) {
-    printf("Gage Watershed version %s\n", TDVERSION);
-    fflush(stdout);
-    if (writeupid == 1) {
-        fprintf(stderr, "taudem_amd: gagewatershed -upid is not supported (the reference's upstream-id file depends on its queue order)\n");
-        g_tdx_thread_error = "gagewatershed: -upid is not supported";
-        return TDX_ERR_ARG;
-    }
-    const double begint = now_s();
-    Raster p;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy, ids;
-    rc = load_outlets(datasrc, p.info, ox, oy, &ids);
-    if (rc != TDX_OK) return rc;
-    const int64_t nout = int64_t(ox.size());
-    const double readt = now_s();
-    std::vector<int32_t> gw(p.s.size()), placed(size_t(nout) + 1), iddown(size_t(nout) + 1);
-    const int16_t p_nd = (int16_t)p.info.nodata;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            int32_t* d_gw = j.strip<int32_t>(nullptr);
-            if (!d_p || !d_gw) return TDX_ERR_NOMEM;
-            const std::vector<int32_t> rows = j.local_rows(oy);
-            std::vector<int32_t> pl(size_t(nout) + 1), dn(size_t(nout) + 1);   // (every rank gets the reduced table)
-            const int e = tdx_gagewatershed_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, ox.data(), rows.data(), ids.data(), nout, d_gw, pl.data(), dn.data(), s);
-            if (e != TDX_OK) return e;
-            if (j.rank == 0) { placed = pl; iddown = dn; }
-            return j.fetch(gw.data(), d_gw) ? TDX_OK : TDX_ERR_HIP;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_gagewatershed(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, ox.data(), oy.data(), ids.data(), nout, gw.data(), placed.data(), iddown.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    if (writeid == 1) {   // src/gagewatershed.cpp:327-341
-        FILE* f = fopen(idfile, "w");
-        if (!f) { printf("Error opening file %s.\n", idfile); fflush(stdout); return TDX_ERR_FILE; }
-        fprintf(f, "id iddown\n");
-        for (int64_t i = 0; i < nout; i++)
-            if (placed[size_t(i)] > 0) fprintf(f, "%d %d\n", ids[size_t(i)], iddown[size_t(i)]);
-        fclose(f);
-    }
-    rc = save_raster(wfile, tdx::DType::I32, gw.data(), p.info, -2147483647.0);   // MISSINGLONG (src/gagewatershed.cpp:346-348)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Size: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("gagewatershed", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-// flowdircond() (src/flowdircond.cpp:54-252): p, then z (File sizes do not match + MPI_Abort(MCW, 5)); the output carries z's nodata value
-int tdx_tool_flowdircond(const char* pfile, const char* zfile, const char* zfdcfile) {
-    printf("FlowDirCond version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster p, z;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(zfile, tdx::DType::F32, z);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(p.info, pfile, z.info, zfile)) { printf("File sizes do not match\n%s\n", zfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    const double readt = now_s();
-    std::vector<float> out(p.s.size());
-    const int16_t p_nd = (int16_t)p.info.nodata;
-    const float z_nd = (float)z.info.nodata;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            float* d_z = j.strip<float>(z.f.data());
-            float* d_o = j.strip<float>(nullptr);
-            if (!d_p || !d_z || !d_o) return TDX_ERR_NOMEM;
-            const int e = tdx_flowdircond_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_z, z_nd, d_o, s);
-            return e != TDX_OK ? e : (j.fetch(out.data(), d_o) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_flowdircond(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, z.f.data(), z_nd, out.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(zfdcfile, tdx::DType::F32, out.data(), z.info, z.info.nodata);   // zIO's nodata, like zIO (src/flowdircond.cpp:224)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("flowdircond", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-// d8vdistdown() (src/D8VDistToStrm.cpp:58-276): p, fel, then src read as LONG (File sizes do not match + MPI_Abort(MCW, 5))
-int tdx_tool_d8vdisttostrm(const char* pfile, const char* felfile, const char* srcfile, const char* distfile, int thresh) {
-    printf("D8VDistToStrm version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster p, fel, src;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(felfile, tdx::DType::F32, fel);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(p.info, pfile, fel.info, felfile)) { printf("File sizes do not match\n%s\n", felfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    rc = load_raster(srcfile, tdx::DType::I32, src);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(p.info, pfile, src.info, srcfile)) { printf("File sizes do not match\n%s\n", srcfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    const double readt = now_s();
-    std::vector<float> dist(p.s.size());
-    const int16_t p_nd = (int16_t)p.info.nodata;
-    const int32_t s_nd = (int32_t)src.info.nodata;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            float* d_fel = j.strip<float>(fel.f.data());
-            int32_t* d_src = j.strip<int32_t>(src.l.data());
-            float* d_dist = j.strip<float>(nullptr);
-            if (!d_p || !d_fel || !d_src || !d_dist) return TDX_ERR_NOMEM;
-            const int e = tdx_d8vdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, d_src, s_nd, thresh, d_dist, s);
-            return e != TDX_OK ? e : (j.fetch(dist.data(), d_dist) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_d8vdisttostrm(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), src.l.data(), s_nd, thresh, dist.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(distfile, tdx::DType::F32, dist.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8VDistToStrm.cpp:250-252)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("d8vdisttostrm", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-// sloped() (src/SlopeAveDown.cpp:59-330): fel, then p (File sizes do not match + MPI_Abort(MCW, 5)); the cell sizes are fel's, the output is
-// written like p.  niter = int(dn / min(dxA, dyA)) + 1 (:172) is not capped; a dn that is negative or not finite is refused.
-int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* slpdfile, double dn) {
-    printf("SlopeAveDown version %s\n", TDVERSION);
-    fflush(stdout);
-    if (!std::isfinite(dn) || dn < 0.0) {
-        fprintf(stderr, "taudem_amd: slopeavedown: dn must be finite and not negative\n");
-        g_tdx_thread_error = "slopeavedown: dn must be finite and not negative";
-        return TDX_ERR_ARG;
-    }
-    const double begint = now_s();
-    Raster p, fel;
-    int rc = load_raster(felfile, tdx::DType::F32, fel);
-    if (rc != TDX_OK) return rc;
-    rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(fel.info, felfile, p.info, pfile)) { printf("File sizes do not match\n%s\n", pfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    const double readt = now_s();
-    const int64_t niter = tdx_slopeavedown_niter(dn, fel.info.dxc.data(), fel.info.dyc.data(), fel.info.ny);
-    if (niter <= 0) { g_tdx_thread_error = "slopeavedown: the cell sizes give no iteration count"; return TDX_ERR_ARG; }
-    fprintf(stderr, "Number of slope down interations to do %lld\n", (long long)niter);
-    fflush(stderr);
-    std::vector<float> sd(p.s.size());
-    const int16_t p_nd = (int16_t)p.info.nodata;
-    const float f_nd = (float)fel.info.nodata;
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            float* d_fel = j.strip<float>(fel.f.data());
-            float* d_sd = j.strip<float>(nullptr);
-            if (!d_p || !d_fel || !d_sd) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(fel.info.dxc), dys = j.rows_of(fel.info.dyc);
-            const int e = tdx_slopeavedown_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, f_nd, dxs.data(), dys.data(), dn, niter, d_sd, s);
-            return e != TDX_OK ? e : (j.fetch(sd.data(), d_sd) ? TDX_OK : TDX_ERR_HIP);
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_slopeavedown(g.c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), f_nd, fel.info.dxc.data(), fel.info.dyc.data(), dn, niter, sd.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(slpdfile, tdx::DType::F32, sd.data(), p.info, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, like pIO (src/SlopeAveDown.cpp:302-304)
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt, writet - computet,
-           writet - begint);
-    print_gpu_stats("slopeavedown", st, p.info.nx * p.info.ny);
-    return 0;
-}
 
 int tdx_tool_set_device(int device) { g_tool_device = device; return TDX_OK; }
 int tdx_tool_set_gpus(int ngpus) { g_tool_gpus = ngpus; return TDX_OK; }
 
 int tdx_tool_pitremove(const char* demfile, const char* felfile, const char* /*sfdrfile*/, int /*usesfdr*/,
                        int verbose, int is_4Point, int use_mask, const char* maskfile) {
-    printf("PitRemove version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
+    ToolRun t("PitRemove");
     Raster dem, mask;
-    int rc = load_raster(demfile, tdx::DType::F32, dem);
-    if (rc != TDX_OK) return rc;
-    if (use_mask) {
-        rc = load_raster(maskfile, tdx::DType::I16, mask);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(dem.info, demfile, mask.info, maskfile)) {
-            printf("Error: depression mask and input DEM are not similar. Files must have the same number of rows/columns.\n");
-            fflush(stdout);
-            return TDX_ERR_MISMATCH;
-        }
-    }
-    const double readt = now_s();
+    t.input(demfile, F32, dem);
+    if (use_mask) t.input(maskfile, I16, mask, Mismatch::PitRemove);
+    if (!t.read_done()) return t.rc;
     if (verbose) { printf("Header read\nData read\n"); if (use_mask) printf("Process: 0, Using depression mask data...\n"); fflush(stdout); }
-    std::vector<float> fel(dem.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), dem.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), dem.info.nx, dem.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_dem = j.strip<float>(dem.f.data());
-            int16_t* d_mask = use_mask ? j.strip<int16_t>(mask.s.data()) : nullptr;
-            float* d_fel = j.strip<float>(nullptr);
-            if (!d_dem || !d_fel || (use_mask && !d_mask)) return TDX_ERR_NOMEM;
-            const int e = tdx_pitremove_strip(j.ctx, j.comm, d_dem, j.nx, j.nyl, (float)dem.info.nodata, d_mask, is_4Point, d_fel, s);
-            return e != TDX_OK ? e : (j.fetch(fel.data(), d_fel) ? TDX_OK : TDX_ERR_HIP);
+    std::vector<float> fel(t.cells());
+    const float nd = (float)dem.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_pitremove(c, dem.f.data(), dem.info.nx, dem.info.ny, nd, use_mask ? mask.s.data() : nullptr, is_4Point, fel.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_dem = j.in(dem.f);
+            int16_t* d_mask = use_mask ? j.in(mask.s) : nullptr;
+            float* d_fel = j.out(fel);
+            if (j.error) return j.error;
+            return tdx_pitremove_strip(j.ctx, j.comm, d_dem, j.nx, j.nyl, nd, d_mask, is_4Point, d_fel, s);
         });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_pitremove(g.c, dem.f.data(), dem.info.nx, dem.info.ny, (float)dem.info.nodata, use_mask ? mask.s.data() : nullptr,
-                           is_4Point, fel.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    if (verbose) printf("Process: 0, Pass: %lld, Remaining: 0\n", (long long)st.rounds);
-    const double computet = now_s();
-    const float felNodata = -3.0e38f;
-    rc = save_raster(felfile, tdx::DType::F32, fel.data(), dem.info, (double)felNodata);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processes: %d\nHeader read time: %f\nData read time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n",
-           nproc, 0.0, readt - begint, computet - readt, writet - computet, writet - begint);
-    print_gpu_stats("pitremove", st, dem.info.nx * dem.info.ny);
-    return 0;
+    if (!ok) return t.rc;
+    if (verbose) printf("Process: 0, Pass: %lld, Remaining: 0\n", (long long)t.st.rounds);
+    t.output(felfile, fel, dem, (double)-3.0e38f);   // felNodata
+    return t.finish("Processes", "pitremove", Footer::HeaderTimes);
 }
 
 int tdx_tool_d8flowdir(const char* demfile, const char* pointfile, const char* slopefile, const char* /*flowfile*/, int useflowfile) {
-    printf("D8FlowDir version %s\n", TDVERSION);
-    fflush(stdout);
+    ToolRun t("D8FlowDir");
     if (useflowfile == 1) {
         // the reference's -sfdr branch reads an int32 partition through the int16 accessor and aborts
         // (src/d8.cpp:119,239-241 -> src/partition.h:100-107): treated as unsupported, same exit code
         printf("Attempt to access short grid with incorrect data type\n");
         return 41;
     }
-    const double begint = now_s();
     Raster dem;
-    int rc = load_raster(demfile, tdx::DType::F32, dem);
-    if (rc != TDX_OK) return rc;
-    const double readt = now_s();
-    const size_t n = dem.f.size();
-    std::vector<int16_t> p(n);
-    std::vector<float> sd8(n);
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), dem.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), dem.info.nx, dem.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_fel = j.strip<float>(dem.f.data());
-            int16_t* d_p = j.strip<int16_t>(nullptr);
-            float* d_sd8 = j.strip<float>(nullptr);
-            if (!d_fel || !d_p || !d_sd8) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(dem.info.dxc), dys = j.rows_of(dem.info.dyc);
-            const int e = tdx_d8flowdir_strip(j.ctx, j.comm, d_fel, j.nx, j.nyl, (float)dem.info.nodata, dxs.data(), dys.data(), d_p, d_sd8, s);
-            if (e != TDX_OK) return e;
-            return (j.fetch(p.data(), d_p) && j.fetch(sd8.data(), d_sd8)) ? TDX_OK : TDX_ERR_HIP;
+    t.input(demfile, F32, dem);
+    if (!t.read_done()) return t.rc;
+    std::vector<int16_t> p(t.cells());
+    std::vector<float> sd8(t.cells());
+    const float nd = (float)dem.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_d8flowdir(c, dem.f.data(), dem.info.nx, dem.info.ny, nd, dem.info.dxc.data(), dem.info.dyc.data(), p.data(), sd8.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_fel = j.in(dem.f);
+            int16_t* d_p = j.out(p);
+            float* d_sd8 = j.out(sd8);
+            if (j.error) return j.error;
+            return tdx_d8flowdir_strip(j.ctx, j.comm, d_fel, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_p, d_sd8, s);
         });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_d8flowdir(g.c, dem.f.data(), dem.info.nx, dem.info.ny, (float)dem.info.nodata, dem.info.dxc.data(), dem.info.dyc.data(),
-                           p.data(), sd8.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    fprintf(stderr, "All slopes evaluated. %ld flats to resolve.\n", (long)st.flats_initial);
-    if (st.flat_iterations > 0 && st.flats_left > 0) fprintf(stderr, "Iteration complete. Number of flats remaining: %ld\n", (long)st.flats_left);
-    rc = save_raster(slopefile, tdx::DType::F32, sd8.data(), dem.info, -1.0);
-    if (rc != TDX_OK) return rc;
+    if (!ok) return t.rc;
+    fprintf(stderr, "All slopes evaluated. %ld flats to resolve.\n", (long)t.st.flats_initial);
+    if (t.st.flat_iterations > 0 && t.st.flats_left > 0) fprintf(stderr, "Iteration complete. Number of flats remaining: %ld\n", (long)t.st.flats_left);
+    t.output(slopefile, sd8, dem, -1.0);
     const double writeSlopet = now_s();
-    rc = save_raster(pointfile, tdx::DType::I16, p.data(), dem.info, -32768.0);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    const double slope_s = st.ms_kernel[TDX_K_STENCIL] / 1000.0;
-    printf("Processors: %d\nHeader read time: %f\nData read time: %f\nCompute Slope time: %f\nWrite Slope time: %f\nResolve Flat time: %f\nWrite Flat time: %f\nTotal time: %f\n",
-           nproc, 0.0, readt - begint, slope_s, writeSlopet - computet, (computet - readt) - slope_s, writet - writeSlopet, writet - begint);
-    print_gpu_stats("d8flowdir", st, dem.info.nx * dem.info.ny);
-    return 0;
+    t.output(pointfile, p, dem, -32768.0);
+    return t.finish("Processors", "d8flowdir", Footer::FlowDir, writeSlopet);
+}
+
+int tdx_tool_dinfflowdir(const char* demfile, const char* angfile, const char* slopefile, const char* /*flowfile*/, int /*useflowfile*/) {
+    ToolRun t("DinfFlowDir");
+    Raster dem;
+    t.input(demfile, F32, dem);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> ang(t.cells()), slp(t.cells());
+    const float nd = (float)dem.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_dinfflowdir(c, dem.f.data(), dem.info.nx, dem.info.ny, nd, dem.info.dxc.data(), dem.info.dyc.data(), ang.data(), slp.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_fel = j.in(dem.f), *d_ang = j.out(ang), *d_slp = j.out(slp);
+            if (j.error) return j.error;
+            return tdx_dinfflowdir_strip(j.ctx, j.comm, d_fel, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_ang, d_slp, s);
+        });
+    if (!ok) return t.rc;
+    fprintf(stderr, "All slopes evaluated. %ld flats to resolve.\n", (long)t.st.flats_initial);
+    t.output(slopefile, slp, dem, -1.0);
+    const double writeSlopet = now_s();
+    t.output(angfile, ang, dem, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinfflowdir", Footer::FlowDir, writeSlopet);
 }
 
 int tdx_tool_aread8(const char* pfile, const char* afile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/,
@@ -1126,198 +415,560 @@ int tdx_tool_aread8(const char* pfile, const char* afile, const char* datasrc, c
         if (!fp) { fprintf(stderr, "Error: Input file %s does not exist.\n", pfile); return TDX_ERR_FILE; }
         fclose(fp);
     }
-    printf("AreaD8 version %s\n", TDVERSION);
-    const double begint = now_s();
+    ToolRun t("AreaD8");
     Raster p, w;
-    int rc = load_raster(pfile, tdx::DType::I16, p);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, p.info, ox, oy); if (rc != TDX_OK) return rc; }
-    if (usew == 1) {
-        rc = load_raster(wfile, tdx::DType::F32, w);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(p.info, pfile, w.info, wfile)) { printf("File sizes do not match\n%s\n", wfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    }
-    const double readt = now_s();
-    std::vector<float> a(p.s.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), p.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), p.info.nx, p.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            int16_t* d_p = j.strip<int16_t>(p.s.data());
-            float* d_w = usew ? j.strip<float>(w.f.data()) : nullptr;
-            float* d_a = j.strip<float>(nullptr);
-            if (!d_p || !d_a || (usew && !d_w)) return TDX_ERR_NOMEM;
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_aread8_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, (int16_t)p.info.nodata, d_w, usew ? (float)w.info.nodata : 0.f, contcheck,
-                                           useOutlets ? ox.data() : nullptr, useOutlets ? lrow.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, d_a, s);
-            return e != TDX_OK ? e : (j.fetch(a.data(), d_a) ? TDX_OK : TDX_ERR_HIP);
+    Outlets o;
+    t.input(pfile, I16, p);
+    t.outlets(datasrc, useOutlets, o);
+    if (usew == 1) t.input(wfile, F32, w);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> a(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float w_nd = usew ? (float)w.info.nodata : 0.f;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_aread8(c, p.s.data(), p.info.nx, p.info.ny, p_nd, usew ? w.f.data() : nullptr, w_nd, contcheck, o.xs(), o.ys(), o.n(), a.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            float* d_w = usew ? j.in(w.f) : nullptr;
+            float* d_a = j.out(a);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_aread8_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_w, w_nd, contcheck, lo.xs(), lo.ys(), lo.n(), d_a, s);
         });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_aread8(g.c, p.s.data(), p.info.nx, p.info.ny, (int16_t)p.info.nodata, usew ? w.f.data() : nullptr, usew ? (float)w.info.nodata : 0.f,
-                        contcheck, useOutlets ? ox.data() : nullptr, useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, a.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(afile, tdx::DType::F32, a.data(), p.info, -1.0);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Number of Processes: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    print_gpu_stats("aread8", st, p.info.nx * p.info.ny);
-    return 0;
-}
-
-int tdx_tool_dinfflowdir(const char* demfile, const char* angfile, const char* slopefile, const char* /*flowfile*/, int /*useflowfile*/) {
-    printf("DinfFlowDir version %s\n", TDVERSION);
-    fflush(stdout);
-    const double begint = now_s();
-    Raster dem;
-    int rc = load_raster(demfile, tdx::DType::F32, dem);
-    if (rc != TDX_OK) return rc;
-    const double readt = now_s();
-    const size_t n = dem.f.size();
-    std::vector<float> ang(n), slp(n);
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), dem.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), dem.info.nx, dem.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_fel = j.strip<float>(dem.f.data());
-            float* d_ang = j.strip<float>(nullptr);
-            float* d_slp = j.strip<float>(nullptr);
-            if (!d_fel || !d_ang || !d_slp) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(dem.info.dxc), dys = j.rows_of(dem.info.dyc);
-            const int e = tdx_dinfflowdir_strip(j.ctx, j.comm, d_fel, j.nx, j.nyl, (float)dem.info.nodata, dxs.data(), dys.data(), d_ang, d_slp, s);
-            if (e != TDX_OK) return e;
-            return (j.fetch(ang.data(), d_ang) && j.fetch(slp.data(), d_slp)) ? TDX_OK : TDX_ERR_HIP;
-        });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfflowdir(g.c, dem.f.data(), dem.info.nx, dem.info.ny, (float)dem.info.nodata, dem.info.dxc.data(), dem.info.dyc.data(),
-                             ang.data(), slp.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    fprintf(stderr, "All slopes evaluated. %ld flats to resolve.\n", (long)st.flats_initial);
-    rc = save_raster(slopefile, tdx::DType::F32, slp.data(), dem.info, -1.0);
-    if (rc != TDX_OK) return rc;
-    const double writeSlopet = now_s();
-    rc = save_raster(angfile, tdx::DType::F32, ang.data(), dem.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    const double slope_s = st.ms_kernel[TDX_K_STENCIL] / 1000.0;
-    printf("Processors: %d\nHeader read time: %f\nData read time: %f\nCompute Slope time: %f\nWrite Slope time: %f\nResolve Flat time: %f\nWrite Flat time: %f\nTotal time: %f\n",
-           nproc, 0.0, readt - begint, slope_s, writeSlopet - computet, (computet - readt) - slope_s, writet - writeSlopet, writet - begint);
-    print_gpu_stats("dinfflowdir", st, dem.info.nx * dem.info.ny);
-    return 0;
+    if (!ok) return t.rc;
+    t.output(afile, a, p, -1.0);
+    return t.finish("Number of Processes", "aread8");
 }
 
 int tdx_tool_areadinf(const char* angfile, const char* scafile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/,
                       const char* wfile, int useOutlets, int usew, int contcheck) {
-    printf("AreaDinf version %s\n", TDVERSION);
-    const double begint = now_s();
+    ToolRun t("AreaDinf");
     Raster ang, w;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, ang.info, ox, oy); if (rc != TDX_OK) return rc; }
-    if (usew == 1) {
-        rc = load_raster(wfile, tdx::DType::F32, w);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, w.info, wfile)) return TDX_ERR_MISMATCH;   // src/areadinf.cpp:134
-    }
-    const double readt = now_s();
-    std::vector<float> sca(ang.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_w = usew ? j.strip<float>(w.f.data()) : nullptr;
-            float* d_out = j.strip<float>(nullptr);
-            if (!d_ang || !d_out || (usew && !d_w)) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_areadinf_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_w, contcheck,
-                                             useOutlets ? ox.data() : nullptr, useOutlets ? lrow.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, d_out, s);
-            return e != TDX_OK ? e : (j.fetch(sca.data(), d_out) ? TDX_OK : TDX_ERR_HIP);
+    Outlets o;
+    t.input(angfile, F32, ang);
+    t.outlets(datasrc, useOutlets, o);
+    if (usew == 1) t.input(wfile, F32, w, Mismatch::Silent);   // src/areadinf.cpp:134
+    if (!t.read_done()) return t.rc;
+    std::vector<float> sca(t.cells());
+    const float nd = (float)ang.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_areadinf(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), usew ? w.f.data() : nullptr, contcheck, o.xs(), o.ys(),
+                                o.n(), sca.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_ang = j.in(ang.f);
+            float* d_w = usew ? j.in(w.f) : nullptr;
+            float* d_out = j.out(sca);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_areadinf_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_w, contcheck, lo.xs(), lo.ys(), lo.n(), d_out, s);
         });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_areadinf(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(),
-                          usew ? w.f.data() : nullptr, contcheck, useOutlets ? ox.data() : nullptr, useOutlets ? oy.data() : nullptr,
-                          useOutlets ? int64_t(ox.size()) : -1, sca.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
-    }
-    const double computet = now_s();
-    rc = save_raster(scafile, tdx::DType::F32, sca.data(), ang.info, -1.0);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    print_gpu_stats("areadinf", st, ang.info.nx * ang.info.ny);
-    return 0;
+    if (!ok) return t.rc;
+    t.output(scafile, sca, ang, -1.0);
+    return t.finish("Processors", "areadinf");
 }
 
 int tdx_tool_dinfdecayaccum(const char* angfile, const char* adecfile, const char* dmfile, const char* datasrc, const char* /*lyrname*/,
                             int /*uselyrname*/, int /*lyrno*/, const char* wfile, int useOutlets, int usew, int contcheck) {
-    printf("DinfDecayAccum version %s\n", TDVERSION);
-    const double begint = now_s();
+    ToolRun t("DinfDecayAccum");
     Raster ang, dm, w;
-    int rc = load_raster(angfile, tdx::DType::F32, ang);
-    if (rc != TDX_OK) return rc;
-    std::vector<int32_t> ox, oy;
-    if (useOutlets == 1) { rc = load_outlets(datasrc, ang.info, ox, oy); if (rc != TDX_OK) return rc; }
-    rc = load_raster(dmfile, tdx::DType::F32, dm);
-    if (rc != TDX_OK) return rc;
-    if (!compare_rasters(ang.info, angfile, dm.info, dmfile)) { printf("File sizes do not match\n%s\n", dmfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    if (usew == 1) {
-        rc = load_raster(wfile, tdx::DType::F32, w);
-        if (rc != TDX_OK) return rc;
-        if (!compare_rasters(ang.info, angfile, w.info, wfile)) { printf("File sizes do not match\n%s\n", wfile); fflush(stdout); return TDX_ERR_OUTLETS; }
-    }
-    const double readt = now_s();
-    std::vector<float> out(ang.f.size());
-    tdx_stats st;
-    const int nproc = int(std::min<int64_t>(tool_gpus(), ang.info.ny));   // (at least one row per rank: the count that is printed is the count that ran)
-    if (nproc > 1) {
-        rc = toolstrips::run(nproc, tool_device(), ang.info.nx, ang.info.ny, &st, [&](toolstrips::RankJob& j, tdx_stats* s) {
-            float* d_ang = j.strip<float>(ang.f.data());
-            float* d_dm = j.strip<float>(dm.f.data());
-            float* d_w = usew ? j.strip<float>(w.f.data()) : nullptr;
-            float* d_out = j.strip<float>(nullptr);
-            if (!d_ang || !d_dm || !d_out || (usew && !d_w)) return TDX_ERR_NOMEM;
-            const std::vector<double> dxs = j.rows_of(ang.info.dxc), dys = j.rows_of(ang.info.dyc);
-            const std::vector<int32_t> lrow = j.local_rows(oy);
-            const int e = tdx_dinfdecayaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, (float)ang.info.nodata, dxs.data(), dys.data(), d_dm, (float)dm.info.nodata, d_w,
-                                                   contcheck, useOutlets ? ox.data() : nullptr, useOutlets ? lrow.data() : nullptr,
-                                                   useOutlets ? int64_t(ox.size()) : -1, d_out, s);
-            return e != TDX_OK ? e : (j.fetch(out.data(), d_out) ? TDX_OK : TDX_ERR_HIP);
+    Outlets o;
+    t.input(angfile, F32, ang);
+    t.outlets(datasrc, useOutlets, o);
+    t.input(dmfile, F32, dm);
+    if (usew == 1) t.input(wfile, F32, w);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> out(t.cells());
+    const float nd = (float)ang.info.nodata, dm_nd = (float)dm.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfdecayaccum(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), dm.f.data(), dm_nd, usew ? w.f.data() : nullptr,
+                                      contcheck, o.xs(), o.ys(), o.n(), out.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_dm = j.in(dm.f);
+            float* d_w = usew ? j.in(w.f) : nullptr;
+            float* d_out = j.out(out);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_dinfdecayaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_dm, dm_nd, d_w, contcheck, lo.xs(), lo.ys(), lo.n(), d_out, s);
         });
-        if (rc != TDX_OK) return rc;
-    } else {
-        CtxGuard g;
-        if (g.rc != TDX_OK) return g.rc;
-        rc = tdx_dinfdecayaccum(g.c, ang.f.data(), ang.info.nx, ang.info.ny, (float)ang.info.nodata, ang.info.dxc.data(), ang.info.dyc.data(),
-                                dm.f.data(), (float)dm.info.nodata, usew ? w.f.data() : nullptr, contcheck, useOutlets ? ox.data() : nullptr,
-                                useOutlets ? oy.data() : nullptr, useOutlets ? int64_t(ox.size()) : -1, out.data(), &st);
-        if (rc != TDX_OK) { report(g.c); return rc; }
+    if (!ok) return t.rc;
+    t.output(adecfile, out, ang, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinfdecayaccum");
+}
+
+int tdx_tool_gridnet(const char* pfile, const char* plenfile, const char* tlenfile, const char* gordfile, const char* maskfile, const char* datasrc,
+                     const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/, int useMask, int useOutlets, int thresh) {
+    ToolRun t("GridNet");
+    Raster p, mask;
+    Outlets o;
+    t.input(pfile, I16, p);
+    t.outlets(datasrc, useOutlets, o);   // src/gridnet.cpp:78-120
+    if (useMask == 1) t.input(maskfile, I32, mask);   // src/gridnet.cpp:147-152
+    if (!t.read_done()) return t.rc;
+    std::vector<float> plen(t.cells()), tlen(t.cells());
+    std::vector<int16_t> gord(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_gridnet(c, p.s.data(), p.info.nx, p.info.ny, p_nd, p.info.dxc.data(), p.info.dyc.data(), useMask ? mask.l.data() : nullptr, thresh, o.xs(), o.ys(), o.n(),
+                               plen.data(), tlen.data(), gord.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_m = useMask ? j.in(mask.l) : nullptr;
+            float *d_pl = j.out(plen), *d_tl = j.out(tlen);
+            int16_t* d_go = j.out(gord);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_gridnet_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, j.dxs.data(), j.dys.data(), d_m, thresh, lo.xs(), lo.ys(), lo.n(), d_pl, d_tl, d_go, s);
+        });
+    if (!ok) return t.rc;
+    t.output(gordfile, gord, p, -1.0);   // src/gridnet.cpp:474-481
+    t.output(plenfile, plen, p, -1.0);
+    t.output(tlenfile, tlen, p, -1.0);
+    return t.finish("Processors", "gridnet");
+}
+
+int tdx_tool_d8flowpathextremeup(const char* pfile, const char* safile, const char* ssafile, int usemax, const char* datasrc, const char* /*lyrname*/,
+                                 int /*uselyrname*/, int /*lyrno*/, int useOutlets, int contcheck) {
+    ToolRun t("D8FlowPathExtremeUp");
+    Raster p, sa;
+    Outlets o;
+    t.input(pfile, I16, p);
+    t.outlets(datasrc, useOutlets, o);
+    t.input(safile, F32, sa);   // src/D8flowpathextremeup.cpp:120-125
+    if (!t.read_done()) return t.rc;
+    std::vector<float> ssa(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_d8flowpathextremeup(c, p.s.data(), p.info.nx, p.info.ny, p_nd, sa.f.data(), usemax, contcheck, o.xs(), o.ys(), o.n(), ssa.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            float *d_sa = j.in(sa.f), *d_out = j.out(ssa);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_d8flowpathextremeup_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_sa, usemax, contcheck, lo.xs(), lo.ys(), lo.n(), d_out, s);
+        });
+    if (!ok) return t.rc;
+    t.output(ssafile, ssa, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT = -FLT_MAX (src/commonLib.h:80)
+    return t.finish("Processors", "d8flowpathextremeup");
+}
+
+// One GPU whatever --gpus says: the tool has no strip form, and its footer says 1 (no statistics line).
+int tdx_tool_threshold(const char* ssafile, const char* srcfile, const char* maskfile, float thresh, int usemask) {
+    ToolRun t("Threshold");
+    Raster ssa, mask;
+    t.input(ssafile, F32, ssa);
+    if (usemask == 1) t.input(maskfile, F32, mask, Mismatch::Silent);   // src/Threshold.cpp:90
+    if (!t.read_done()) return t.rc;
+    std::vector<int16_t> src(t.cells());
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_threshold(c, ssa.f.data(), ssa.info.nx, ssa.info.ny, (float)ssa.info.nodata, usemask ? mask.f.data() : nullptr, thresh, src.data(), s);
+        },
+        nullptr);
+    if (!ok) return t.rc;
+    t.output(srcfile, src, ssa, -32768.0);
+    return t.finish("Processors", nullptr);
+}
+
+int tdx_tool_dinfupdependence(const char* angfile, const char* dgfile, const char* depfile) {
+    ToolRun t("DinfUpDependence");
+    Raster ang, dg;
+    t.input(angfile, F32, ang);
+    t.input(dgfile, I32, dg, Mismatch::Silent);   // src/DinfUpDependence.cpp:103
+    if (!t.read_done()) return t.rc;
+    std::vector<float> dep(t.cells());
+    const float nd = (float)ang.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfupdependence(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), dg.l.data(), dep.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_ang = j.in(ang.f);
+            int32_t* d_dg = j.in(dg.l);
+            float* d_dep = j.out(dep);
+            if (j.error) return j.error;
+            return tdx_dinfupdependence_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_dg, d_dep, s);
+        });
+    if (!ok) return t.rc;
+    t.output(depfile, dep, ang, -1.0);   // depNodata = -1 (src/DinfUpDependence.cpp:113)
+    return t.finish("Processors", "dinfupdependence");
+}
+
+int tdx_tool_dinfrevaccum(const char* angfile, const char* wgfile, const char* raccfile, const char* dmaxfile) {
+    ToolRun t("DinfRevAccum");
+    Raster ang, w;
+    t.input(angfile, F32, ang);
+    t.input(wgfile, F32, w);   // src/DinfRevAccum.cpp:94-99
+    if (!t.read_done()) return t.rc;
+    std::vector<float> racc(t.cells()), dmax(t.cells());
+    const float nd = (float)ang.info.nodata, w_nd = (float)w.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfrevaccum(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), w.f.data(), w_nd, racc.data(), dmax.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_w = j.in(w.f), *d_r = j.out(racc), *d_m = j.out(dmax);
+            if (j.error) return j.error;
+            return tdx_dinfrevaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_w, w_nd, d_r, d_m, s);
+        });
+    if (!ok) return t.rc;
+    t.output(raccfile, racc, ang, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfRevAccum.cpp:253-258)
+    t.output(dmaxfile, dmax, ang, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinfrevaccum");
+}
+
+int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/,
+                              int /*lyrno*/, const char* qfile, const char* dgfile, int useOutlets, int contcheck, float cSol) {
+    ToolRun t("DinfConcLimAccum");
+    Raster ang, dm, dg, q;
+    Outlets o;
+    t.input(angfile, F32, ang);
+    t.outlets(datasrc, useOutlets, o);
+    t.input(dmfile, F32, dm);
+    t.input(dgfile, I16, dg);
+    t.input(qfile, F32, q);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> out(t.cells());
+    const float nd = (float)ang.info.nodata, dm_nd = (float)dm.info.nodata, q_nd = (float)q.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfconclimaccum(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), dm.f.data(), dm_nd, dg.s.data(), q.f.data(), q_nd,
+                                        cSol, contcheck, o.xs(), o.ys(), o.n(), out.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_dm = j.in(dm.f), *d_q = j.in(q.f);
+            int16_t* d_dg = j.in(dg.s);
+            float* d_out = j.out(out);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_dinfconclimaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_dm, dm_nd, d_dg, d_q, q_nd, cSol, contcheck, lo.xs(), lo.ys(),
+                                              lo.n(), d_out, s);
+        });
+    if (!ok) return t.rc;
+    t.output(ctptfile, out, ang, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinfconclimaccum");
+}
+
+int tdx_tool_dinftranslimaccum(const char* angfile, const char* tsupfile, const char* tcfile, const char* tlafile, const char* depfile, const char* cinfile,
+                               const char* coutfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/, int useOutlets, int usec,
+                               int contcheck) {
+    ToolRun t("DinfTransLimAccum");
+    Raster ang, tsup, tc, cin;
+    Outlets o;
+    t.input(angfile, F32, ang);
+    t.outlets(datasrc, useOutlets, o);
+    t.input(tsupfile, F32, tsup);
+    t.input(tcfile, F32, tc);
+    if (usec == 1) t.input(cinfile, F32, cin);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> tla(t.cells()), dep(t.cells()), cso(usec ? t.cells() : 0);
+    const float nd = (float)ang.info.nodata, ts_nd = (float)tsup.info.nodata, tc_nd = (float)tc.info.nodata, ci_nd = usec ? (float)cin.info.nodata : 0.f;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinftranslimaccum(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), tsup.f.data(), ts_nd, tc.f.data(), tc_nd,
+                                         usec ? cin.f.data() : nullptr, ci_nd, contcheck, o.xs(), o.ys(), o.n(), tla.data(), dep.data(), usec ? cso.data() : nullptr, s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_ts = j.in(tsup.f), *d_tc = j.in(tc.f);
+            float* d_ci = usec ? j.in(cin.f) : nullptr;
+            float *d_tla = j.out(tla), *d_dep = j.out(dep);
+            float* d_co = usec ? j.out(cso) : nullptr;
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            return tdx_dinftranslimaccum_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_ts, ts_nd, d_tc, tc_nd, d_ci, ci_nd, contcheck, lo.xs(), lo.ys(),
+                                               lo.n(), d_tla, d_dep, d_co, s);
+        });
+    if (!ok) return t.rc;
+    t.output(tlafile, tla, ang, (double)TDX_ANG_NODATA);
+    t.output(depfile, dep, ang, (double)TDX_ANG_NODATA);
+    if (usec == 1) t.output(coutfile, cso, ang, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinftranslimaccum");
+}
+
+// The four tool functions of each distance tool in one: files in the reference's order (ang, then fel for v / p / s, w for h / p / s when
+// used - for v the weight code is commented out in the reference -, then src), each compared with ang; slpfile is never read.
+static const char* const kDistType[4] = {"-h", "-v", "-p", "-s"};
+
+int tdx_tool_dinfdistdown(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* srcfile, const char* dtsfile,
+                          int statmethod, int typemethod, int usew, int concheck) {
+    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
+    ToolRun t(std::string("DinfDistDown ") + kDistType[typemethod]);
+    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;
+    Raster ang, fel, w, src;
+    t.input(angfile, F32, ang);
+    if (use_fel) t.input(felfile, F32, fel);
+    if (use_w) t.input(wfile, F32, w);
+    t.input(srcfile, I16, src);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> dd(t.cells());
+    const float nd = (float)ang.info.nodata, fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfdistdown(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), use_fel ? fel.f.data() : nullptr, fel_nd, src.s.data(),
+                                    use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, dd.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_ang = j.in(ang.f);
+            float* d_fel = use_fel ? j.in(fel.f) : nullptr;
+            float* d_w = use_w ? j.in(w.f) : nullptr;
+            int16_t* d_src = j.in(src.s);
+            float* d_dd = j.out(dd);
+            if (j.error) return j.error;
+            return tdx_dinfdistdown_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_fel, fel_nd, d_src, d_w, w_nd, statmethod, typemethod, concheck, d_dd, s);
+        });
+    if (!ok) return t.rc;
+    t.output(dtsfile, dd, ang, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistDown.cpp:363-365)
+    return t.finish("Processors", "dinfdistdown");
+}
+
+int tdx_tool_dinfdistup(const char* angfile, const char* felfile, const char* /*slpfile*/, const char* wfile, const char* rtrfile, int statmethod,
+                        int typemethod, int usew, int concheck, float thresh) {
+    if (typemethod < 0 || typemethod > 3) return 0;   // (the reference's switch has no default: nothing runs)
+    ToolRun t(std::string("DinfDistUp ") + kDistType[typemethod]);
+    const bool use_fel = typemethod != 0, use_w = usew == 1 && typemethod != 1;
+    Raster ang, fel, w;
+    t.input(angfile, F32, ang);
+    if (use_fel) t.input(felfile, F32, fel);
+    if (use_w) t.input(wfile, F32, w);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> du(t.cells());
+    const float nd = (float)ang.info.nodata, fel_nd = use_fel ? (float)fel.info.nodata : 0.f, w_nd = use_w ? (float)w.info.nodata : 0.f;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfdistup(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), use_fel ? fel.f.data() : nullptr, fel_nd,
+                                  use_w ? w.f.data() : nullptr, w_nd, statmethod, typemethod, concheck, thresh, du.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_ang = j.in(ang.f);
+            float* d_fel = use_fel ? j.in(fel.f) : nullptr;
+            float* d_w = use_w ? j.in(w.f) : nullptr;
+            float* d_du = j.out(du);
+            if (j.error) return j.error;
+            return tdx_dinfdistup_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_fel, fel_nd, d_w, w_nd, statmethod, typemethod, concheck, thresh, d_du, s);
+        });
+    if (!ok) return t.rc;
+    t.output(rtrfile, du, ang, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/DinfDistUp.cpp:321-322)
+    return t.finish("Processors", "dinfdistup");
+}
+
+// ang, wg, rc, each compared with ang; the output header is rc's
+int tdx_tool_retlimflow(const char* angfile, const char* wgfile, const char* rcfile, const char* qrlfile) {
+    ToolRun t("Retention limited flow accumulation");
+    Raster ang, wg, rcg;
+    t.input(angfile, F32, ang);
+    t.input(wgfile, F32, wg);
+    t.input(rcfile, F32, rcg);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> qrl(t.cells());
+    const float nd = (float)ang.info.nodata, wg_nd = (float)wg.info.nodata, rc_nd = (float)rcg.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_retlimflow(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), wg.f.data(), wg_nd, rcg.f.data(), rc_nd, qrl.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_wg = j.in(wg.f), *d_rc = j.in(rcg.f), *d_q = j.out(qrl);
+            if (j.error) return j.error;
+            return tdx_retlimflow_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_wg, wg_nd, d_rc, rc_nd, d_q, s);
+        });
+    if (!ok) return t.rc;
+    t.output(qrlfile, qrl, rcg, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of rc (src/RetlimFlow.cpp:233-235)
+    return t.finish("Processors", "retlimflow", Footer::CountOnly);
+}
+
+// ang, fel, ass (SHORT), each compared with ang.  -direct reads the file's coordinates: the geotransform goes to the library.
+int tdx_tool_dinfavalanche(const char* angfile, const char* felfile, const char* assfile, const char* rzfile, const char* dmfile, float thresh, float alpha, int path) {
+    ToolRun t("DinfAvalanche");
+    Raster ang, fel, ass;
+    t.input(angfile, F32, ang);
+    t.input(felfile, F32, fel, Mismatch::Avalanche);
+    t.input(assfile, I16, ass, Mismatch::Avalanche);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> rz(t.cells()), dfs(t.cells());
+    const double geo[4] = {ang.info.xleftedge, ang.info.ytopedge, ang.info.dlon, ang.info.dlat};
+    const int geographic = ang.info.geographic ? 1 : 0;
+    const float nd = (float)ang.info.nodata, fel_nd = (float)fel.info.nodata;
+    const int16_t ass_nd = (int16_t)ass.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dinfavalanche(c, ang.f.data(), ang.info.nx, ang.info.ny, nd, ang.info.dxc.data(), ang.info.dyc.data(), fel.f.data(), fel_nd, ass.s.data(), ass_nd, thresh, alpha,
+                                     path, geo, geographic, rz.data(), dfs.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_ang = j.in(ang.f), *d_fel = j.in(fel.f);
+            int16_t* d_ass = j.in(ass.s);
+            float *d_rz = j.out(rz), *d_dfs = j.out(dfs);
+            if (j.error) return j.error;
+            return tdx_dinfavalanche_strip(j.ctx, j.comm, d_ang, j.nx, j.nyl, nd, j.dxs.data(), j.dys.data(), d_fel, fel_nd, d_ass, ass_nd, thresh, alpha, path, geo, geographic, j.y0,
+                                           j.ny, d_rz, d_dfs, s);
+        });
+    if (!ok) return t.rc;
+    t.output(rzfile, rz, ang, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, header of ang (src/DinfAvalanche.cpp:384-389)
+    t.output(dmfile, dfs, ang, (double)TDX_ANG_NODATA);
+    return t.finish("Processors", "dinfavalanche");
+}
+
+// p, then src read as LONG
+int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* distfile, int thresh) {
+    ToolRun t("D8HDistToStrm");
+    Raster p, src;
+    t.input(pfile, I16, p);
+    t.input(srcfile, I32, src);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> dist(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t s_nd = (int32_t)src.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_d8hdisttostrm(c, p.s.data(), p.info.nx, p.info.ny, p_nd, src.l.data(), s_nd, thresh, p.info.dxc.data(), p.info.dyc.data(), dist.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_src = j.in(src.l);
+            float* d_dist = j.out(dist);
+            if (j.error) return j.error;
+            return tdx_d8hdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_src, s_nd, thresh, j.dxs.data(), j.dys.data(), d_dist, s);
+        });
+    if (!ok) return t.rc;
+    t.output(distfile, dist, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8HDistToStrm.cpp:223-225)
+    return t.finish("Processors", "d8hdisttostrm");
+}
+
+// -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  -upid is refused: the reference appends a line per visit of a
+// nodata neighbour in queue order (src/gagewatershed.cpp:246-253), which depends on the schedule.
+int tdx_tool_gagewatershed(const char* pfile, const char* wfile, const char* datasrc, const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/,
+                           const char* idfile, int writeid, int writeupid, const char* /*upidfile*/) {
+    ToolRun t("Gage Watershed");
+    if (writeupid == 1) {
+        fprintf(stderr, "taudem_amd: gagewatershed -upid is not supported (the reference's upstream-id file depends on its queue order)\n");
+        g_tdx_thread_error = "gagewatershed: -upid is not supported";
+        return TDX_ERR_ARG;
     }
-    const double computet = now_s();
-    rc = save_raster(adecfile, tdx::DType::F32, out.data(), ang.info, (double)TDX_ANG_NODATA);
-    if (rc != TDX_OK) return rc;
-    const double writet = now_s();
-    printf("Processors: %d\nRead time: %f\nCompute time: %f\nWrite time: %f\nTotal time: %f\n", nproc, readt - begint, computet - readt,
-           writet - computet, writet - begint);
-    print_gpu_stats("dinfdecayaccum", st, ang.info.nx * ang.info.ny);
-    return 0;
+    Raster p;
+    Outlets o;
+    t.input(pfile, I16, p);
+    t.outlets(datasrc, 1, o);
+    if (!t.read_done()) return t.rc;
+    const int64_t nout = o.n();
+    std::vector<int32_t> gw(t.cells()), placed(size_t(nout) + 1), iddown(size_t(nout) + 1);
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_gagewatershed(c, p.s.data(), p.info.nx, p.info.ny, p_nd, o.xs(), o.ys(), o.ids.data(), nout, gw.data(), placed.data(), iddown.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_gw = j.out(gw);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            std::vector<int32_t> pl(size_t(nout) + 1), dn(size_t(nout) + 1);   // (every rank gets the reduced table: rank 0's is kept)
+            const int e = tdx_gagewatershed_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, lo.xs(), lo.ys(), o.ids.data(), nout, d_gw, pl.data(), dn.data(), s);
+            if (e == TDX_OK && j.rank == 0) { placed = pl; iddown = dn; }
+            return e;
+        });
+    if (!ok) return t.rc;
+    if (writeid == 1) {   // before the raster (src/gagewatershed.cpp:327-341)
+        FILE* f = fopen(idfile, "w");
+        if (!f) { printf("Error opening file %s.\n", idfile); fflush(stdout); return TDX_ERR_FILE; }
+        fprintf(f, "id iddown\n");
+        for (int64_t i = 0; i < nout; i++)
+            if (placed[size_t(i)] > 0) fprintf(f, "%d %d\n", o.ids[size_t(i)], iddown[size_t(i)]);
+        fclose(f);
+    }
+    t.output(wfile, gw, p, -2147483647.0);   // MISSINGLONG (src/gagewatershed.cpp:346-348)
+    return t.finish("Size", "gagewatershed");
+}
+
+// p, then z; the output is written like z, with z's nodata value (src/flowdircond.cpp:224)
+int tdx_tool_flowdircond(const char* pfile, const char* zfile, const char* zfdcfile) {
+    ToolRun t("FlowDirCond");
+    Raster p, z;
+    t.input(pfile, I16, p);
+    t.input(zfile, F32, z);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> out(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float z_nd = (float)z.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_flowdircond(c, p.s.data(), p.info.nx, p.info.ny, p_nd, z.f.data(), z_nd, out.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            float *d_z = j.in(z.f), *d_o = j.out(out);
+            if (j.error) return j.error;
+            return tdx_flowdircond_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_z, z_nd, d_o, s);
+        });
+    if (!ok) return t.rc;
+    t.output(zfdcfile, out, z, z.info.nodata);
+    return t.finish("Processors", "flowdircond");
+}
+
+// p, fel, then src read as LONG
+int tdx_tool_d8vdisttostrm(const char* pfile, const char* felfile, const char* srcfile, const char* distfile, int thresh) {
+    ToolRun t("D8VDistToStrm");
+    Raster p, fel, src;
+    t.input(pfile, I16, p);
+    t.input(felfile, F32, fel);
+    t.input(srcfile, I32, src);
+    if (!t.read_done()) return t.rc;
+    std::vector<float> dist(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t s_nd = (int32_t)src.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_d8vdisttostrm(c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), src.l.data(), s_nd, thresh, dist.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            float* d_fel = j.in(fel.f);
+            int32_t* d_src = j.in(src.l);
+            float* d_dist = j.out(dist);
+            if (j.error) return j.error;
+            return tdx_d8vdisttostrm_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, d_src, s_nd, thresh, d_dist, s);
+        });
+    if (!ok) return t.rc;
+    t.output(distfile, dist, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8VDistToStrm.cpp:250-252)
+    return t.finish("Processors", "d8vdisttostrm");
+}
+
+// fel first, then p compared with it: the cell sizes are fel's, the output is written like p.  niter = int(dn / min(dxA, dyA)) + 1
+// (src/SlopeAveDown.cpp:172) is not capped; a dn that is negative or not finite is refused.
+int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* slpdfile, double dn) {
+    ToolRun t("SlopeAveDown");
+    if (!std::isfinite(dn) || dn < 0.0) {
+        fprintf(stderr, "taudem_amd: slopeavedown: dn must be finite and not negative\n");
+        g_tdx_thread_error = "slopeavedown: dn must be finite and not negative";
+        return TDX_ERR_ARG;
+    }
+    Raster p, fel;
+    t.input(felfile, F32, fel);
+    t.input(pfile, I16, p);
+    if (!t.read_done()) return t.rc;
+    const int64_t niter = tdx_slopeavedown_niter(dn, fel.info.dxc.data(), fel.info.dyc.data(), fel.info.ny);
+    if (niter <= 0) { g_tdx_thread_error = "slopeavedown: the cell sizes give no iteration count"; return TDX_ERR_ARG; }
+    fprintf(stderr, "Number of slope down interations to do %lld\n", (long long)niter);
+    fflush(stderr);
+    std::vector<float> sd(t.cells());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float f_nd = (float)fel.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_slopeavedown(c, p.s.data(), p.info.nx, p.info.ny, p_nd, fel.f.data(), f_nd, fel.info.dxc.data(), fel.info.dyc.data(), dn, niter, sd.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            float *d_fel = j.in(fel.f), *d_sd = j.out(sd);
+            if (j.error) return j.error;
+            return tdx_slopeavedown_strip(j.ctx, j.comm, d_p, j.nx, j.nyl, p_nd, d_fel, f_nd, j.dxs.data(), j.dys.data(), dn, niter, d_sd, s);
+        });
+    if (!ok) return t.rc;
+    t.output(slpdfile, sd, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, like pIO (src/SlopeAveDown.cpp:302-304)
+    return t.finish("Processors", "slopeavedown");
 }
 
 }  // extern "C"

@@ -115,6 +115,4 @@ static int rev_prepare(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t 
     return TDX_OK;
 }
 
-static inline bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
-
 }  // namespace d8rev

@@ -211,8 +211,6 @@ __global__ __launch_bounds__(256) void aval_unpack_kernel(const float4* __restri
     else dfs[i] = has ? direct_dist(G, __float_as_uint(aux[i].y), __float_as_uint(r.z)) : TDX_ANG_NODATA;
 }
 
-bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
-
 // prop() of src/commonLib.cpp:76-91 on the host: can a cell whose angle is `a` send anywhere in a row with these cell sizes?
 bool host_sends(float a0, double dx1, double dy1) {
     const double a2 = atan2(dy1, dx1);

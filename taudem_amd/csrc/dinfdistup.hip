@@ -216,7 +216,6 @@ int distup_impl(tdx_context* ctx, const Strip& st, const DuArgs& a, tdx_stats* s
 }
 
 bool bad_mode(int stat, int kind) { return stat < 0 || stat > 2 || kind < 0 || kind > 3; }
-bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
 
 }  // namespace
 

@@ -213,8 +213,6 @@ int translim_impl(tdx_context* ctx, const Strip& st, float* d_ang, float ang_nod
     return TDX_OK;
 }
 
-bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
-
 }  // namespace
 
 extern "C" int tdx_dinfconclimaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,

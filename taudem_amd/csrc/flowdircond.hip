@@ -92,8 +92,6 @@ int fdc_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     return TDX_OK;
 }
 
-inline bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
-
 }  // namespace
 
 extern "C" int tdx_flowdircond_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_z, float z_nodata, float* d_zfdc,

@@ -144,7 +144,6 @@ int sad_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     return TDX_OK;
 }
 
-inline bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
 inline bool bad_dn(double dn) { return !std::isfinite(dn) || dn < 0.0; }
 
 }  // namespace

@@ -36,6 +36,8 @@ static inline Strip strip_from_comm(const tdx_comm* comm, int nx, int ny_local) 
     if (comm && comm->size > 1) { s.up = comm->rank > 0; s.down = comm->rank < comm->size - 1; }
     return s;
 }
+// the kernels index a device array with 32 bits: (rows x nx) has to fit, for the whole raster or for a strip with its halo rows
+inline bool too_big(int64_t nx, int64_t rows) { return nx > 0x7fffffff || rows > 0x7ffffff0 || uint64_t(nx) * uint64_t(rows) > 0xffffffffull; }
 
 namespace stripk {
 template <class T>

@@ -12,13 +12,51 @@
 
 namespace toolstrips {
 
+// Outlet cells the way every library call takes them: (x, y, n), or (nullptr, nullptr, -1) for a tool run without -o.
+struct Outlets {
+    bool use = false;
+    std::vector<int32_t> x, y, ids;
+    const int32_t* xs() const { return use ? x.data() : nullptr; }
+    const int32_t* ys() const { return use ? y.data() : nullptr; }
+    int64_t n() const { return use ? int64_t(x.size()) : -1; }
+};
+// A strip's view of them: the same columns and count, the rows in the strip's array
+struct LocalOutlets {
+    const Outlets& all;
+    std::vector<int32_t> rows;
+    const int32_t* xs() const { return all.xs(); }
+    const int32_t* ys() const { return all.use ? rows.data() : nullptr; }
+    int64_t n() const { return all.n(); }
+};
+
 struct RankJob {
     tdx_context* ctx = nullptr;
     const tdx_comm* comm = nullptr;
     int rank = 0, size = 1;
     int64_t nx = 0, ny = 0, y0 = 0, y1 = 0, nyl = 0;   // global raster, owned global rows [y0, y1)
+    std::vector<double> dxs, dys;                       // cell sizes of the nyl + 2 strip rows (run() fills them)
+    int error = TDX_OK;                                 // sticky: a strip array could not be allocated or uploaded
     std::vector<void*> owned;                           // device allocations of this job
     ~RankJob() { for (void* p : owned) (void)hipFree(p); }
+
+    // strip array of an input raster / of an output raster, which run() fetches into `host_full` once the body has returned TDX_OK
+    template <class T>
+    T* in(const std::vector<T>& host_full) { T* p = strip<T>(host_full.data()); if (!p) error = TDX_ERR_NOMEM; return p; }
+    template <class T>
+    T* out(std::vector<T>& host_full) {
+        T* p = strip<T>(nullptr);
+        if (!p) error = TDX_ERR_NOMEM;
+        else outputs.push_back({host_full.data() + size_t(y0) * size_t(nx), p + size_t(nx), size_t(nx) * size_t(nyl) * sizeof(T)});
+        return p;
+    }
+    struct Output { void* host; const void* dev; size_t bytes; };
+    std::vector<Output> outputs;
+    bool fetch_outputs() {
+        for (const Output& o : outputs)
+            if (hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return false;
+        return hipStreamSynchronize(ctx->stream) == hipSuccess;
+    }
+    LocalOutlets local(const Outlets& o) const { return {o, local_rows(o.y)}; }
 
     size_t strip_cells() const { return size_t(nx) * size_t(nyl + 2); }
     // a (nyl + 2) x nx strip array in HBM; host_full != nullptr: its owned rows are uploaded into rows 1..nyl (halo rows are the library's)
@@ -30,12 +68,6 @@ struct RankJob {
         if (host_full && hipMemcpyAsync(static_cast<T*>(p) + size_t(nx), host_full + size_t(y0) * size_t(nx), size_t(nx) * size_t(nyl) * sizeof(T),
                                         hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
         return static_cast<T*>(p);
-    }
-    // owned rows of a strip array back into the full host raster
-    template <class T>
-    bool fetch(T* host_full, const T* dev) {
-        return hipMemcpyAsync(host_full + size_t(y0) * size_t(nx), dev + size_t(nx), size_t(nx) * size_t(nyl) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-               hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
     // per-row values (cell sizes) of the nyl + 2 strip rows: global rows y0 - 1 .. y1, clamped into the raster
     std::vector<double> rows_of(const std::vector<double>& per_row) const {
@@ -54,11 +86,12 @@ struct RankJob {
     }
 };
 
-// Runs body(job) on every rank's thread.  Returns the first non-zero code (a failing rank ends the process with that code
-// when others may be waiting for it in a collective - what MPI_Abort does in the reference).  stats0: rank 0's statistics
-// with the integer counters the ranks agree on; device time = the slowest rank's.
+// Runs body(job, stats) on every rank's thread and fetches the outputs the body registered.  Returns the first non-zero code (a
+// failing rank ends the process with that code when others may be waiting for it in a collective - what MPI_Abort does in the
+// reference).  dxc, dyc: the raster's per-row cell sizes.  stats0: rank 0's statistics with the integer counters the ranks
+// agree on; device time = the slowest rank's.
 template <class F>
-int run(int ngpus, int base_device, int64_t nx, int64_t ny, tdx_stats* stats0, F body) {
+int run(int ngpus, int base_device, int64_t nx, int64_t ny, const std::vector<double>& dxc, const std::vector<double>& dyc, tdx_stats* stats0, F body) {
     int ndev = tdx_device_count();
     if (ndev < 1) return tdx_fail(nullptr, TDX_ERR_NOGPU, "no HIP device");
     int size = int(std::min<int64_t>(ngpus, ny));   // at least one row per rank
@@ -81,8 +114,10 @@ int run(int ngpus, int base_device, int64_t nx, int64_t ny, tdx_stats* stats0, F
             job.rank = r; job.size = size; job.nx = nx; job.ny = ny;
             job.y0 = int64_t(r) * base; job.y1 = (r == size - 1) ? ny : int64_t(r + 1) * base;   // remainder to the last rank (src/linearpart.h:133-134)
             job.nyl = job.y1 - job.y0;
+            job.dxs = job.rows_of(dxc); job.dys = job.rows_of(dyc);
             memset(&sts[size_t(r)], 0, sizeof(tdx_stats));
             int e = hipSetDevice(job.ctx->device) == hipSuccess ? body(job, &sts[size_t(r)]) : TDX_ERR_HIP;
+            if (e == TDX_OK && !job.fetch_outputs()) e = TDX_ERR_HIP;
             rcs[size_t(r)] = e;
             if (e != TDX_OK && size > 1) {
                 // The other ranks may be waiting for this one in a collective: the group is aborted, so that their waits fail at once and
