@@ -479,6 +479,39 @@ int tdx_flowdircond_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, 
                           float z_nodata, float* d_zfdc, tdx_stats* stats);
 int tdx_slopeavedown_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const float* d_fel,
                            float fel_nodata, const double* dxc, const double* dyc, double dn, int64_t niter, float* d_slpd, tdx_stats* stats);
+/* CatchHydroGeo and InunDepth: what consumes a HAND raster (dinfdistdown -m ave v).
+ * catchhydrogeo() src/CatchHydroGeo.cpp:69-413: per listed catchment and stage, the wetted cells of its cells whose hand is below the stage
+ * (or within 1e-6 of 0): their number, plan area, bed area cellArea * sqrt(1 + slp^2) and volume (stage - hand) * cellArea, and the
+ * catchment's whole plan area.  ids: HOST list of ncatch ids (the last row of a repeated id wins; earlier rows stay 0); stages: HOST, nheight
+ * values in any order.  Outputs are HOST arrays: count / surface / bed / volume [nheight][ncatch], catcharea [ncatch].  The fp64 sums are
+ * taken in a fixed order (cells of a 64 x 64 tile, then tiles ascending): the same input gives the same bits.  dxc / dyc: per-row cell sizes.
+ * The strip form (arrays of ny_local + 2 rows, dxc / dyc of those rows) returns the STRIP's sums; the caller adds the strips in order. */
+int tdx_catchhydrogeo_dev(tdx_context* ctx, const float* d_hand, const int32_t* d_catch, const float* d_slp, int64_t nx, int64_t ny, float hand_nodata,
+                          int32_t catch_nodata, float slp_nodata, const double* dxc, const double* dyc, const int32_t* ids, int64_t ncatch,
+                          const double* stages, int64_t nheight, int32_t* count, double* surface, double* bed, double* volume, double* catcharea,
+                          tdx_stats* stats);
+int tdx_catchhydrogeo(tdx_context* ctx, const float* hand, const int32_t* catchr, const float* slp, int64_t nx, int64_t ny, float hand_nodata,
+                      int32_t catch_nodata, float slp_nodata, const double* dxc, const double* dyc, const int32_t* ids, int64_t ncatch,
+                      const double* stages, int64_t nheight, int32_t* count, double* surface, double* bed, double* volume, double* catcharea,
+                      tdx_stats* stats);
+int tdx_catchhydrogeo_strip(tdx_context* ctx, const tdx_comm* comm, const float* d_hand, const int32_t* d_catch, const float* d_slp, int64_t nx,
+                            int64_t ny_local, float hand_nodata, int32_t catch_nodata, float slp_nodata, const double* dxc, const double* dyc,
+                            const int32_t* ids, int64_t ncatch, const double* stages, int64_t nheight, int32_t* count, double* surface, double* bed,
+                            double* volume, double* catcharea, tdx_stats* stats);
+/* inundepth() src/InunDepth.cpp:53-545, the raster part: ids / depth are HOST arrays of nfc forecast rows (depth per row, the last row of a
+ * repeated id wins).  map float32, nodata -3.0e38: depth - hand where catch and hand have data, the id has a depth >= 0 and depth > hand +
+ * 0.001 in double.  mask (int16, may be NULL): as in the reference, with a mask EVERY cell is nodata (its line 465).  area (HOST, may be NULL):
+ * per row the plan area of the cells with depth > 0 and depth - hand > 0 (float), summed in fp64 and rounded once, at the winning row of
+ * its id, 0 elsewhere.  The strip form returns the strip's fp64 sums. */
+int tdx_inundepth_dev(tdx_context* ctx, const float* d_hand, const int32_t* d_catch, const int16_t* d_mask, int64_t nx, int64_t ny, float hand_nodata,
+                      int32_t catch_nodata, int16_t mask_nodata, const double* dxc, const double* dyc, const int32_t* ids, const float* depth,
+                      int64_t nfc, float* d_map, float* area, tdx_stats* stats);
+int tdx_inundepth(tdx_context* ctx, const float* hand, const int32_t* catchr, const int16_t* mask, int64_t nx, int64_t ny, float hand_nodata,
+                  int32_t catch_nodata, int16_t mask_nodata, const double* dxc, const double* dyc, const int32_t* ids, const float* depth, int64_t nfc,
+                  float* map, float* area, tdx_stats* stats);
+int tdx_inundepth_strip(tdx_context* ctx, const tdx_comm* comm, const float* d_hand, const int32_t* d_catch, const int16_t* d_mask, int64_t nx,
+                        int64_t ny_local, float hand_nodata, int32_t catch_nodata, int16_t mask_nodata, const double* dxc, const double* dyc,
+                        const int32_t* ids, const float* depth, int64_t nfc, float* d_map, double* area_partial, tdx_stats* stats);
 /* the limited D-infinity accumulations on strips (outlet_row: array row of the strip, as for tdx_areadinf_strip) */
 int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg,
@@ -589,6 +622,13 @@ int tdx_tool_flowdircond(const char* pfile, const char* zfile, const char* zfdcf
 int tdx_tool_d8vdisttostrm(const char* pfile, const char* felfile, const char* srcfile, const char* distfile, int thresh);
 /* int sloped(char* pfile, char* felfile, char* slpdfile, double dn)               src/SlopeAveDown.cpp:59 */
 int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* slpdfile, double dn);
+/* int catchhydrogeo(char* handfile, char* catchfile, char* catchlistfile, char* slpfile, char* hfile, char* hpfile)   src/CatchHydroGeo.cpp:69 */
+int tdx_tool_catchhydrogeo(const char* handfile, const char* catchfile, const char* catchlistfile, const char* slpfile, const char* hfile,
+                           const char* hpfile);
+/* int inundepth(char* handfile, char* catchfile, char* maskfile, char* fcfile, char* hpfile, char* mapfile, char* depthfile)
+ *                                                               src/InunDepth.cpp:53 (maskfile / depthfile NULL: not given) */
+int tdx_tool_inundepth(const char* handfile, const char* catchfile, const char* maskfile, const char* fcfile, const char* hpfile,
+                       const char* mapfile, const char* depthfile);
 /* int dsllArea(char* angfile, char* ctptfile, char* dmfile, char* datasrc, char* lyrname, int uselyrname, int lyrno, char* qfile,
  *              char* dgfile, int useOutlets, int contcheck, float cSol)          src/DinfConcLimAccum.cpp:61-62 */
 int tdx_tool_dinfconclimaccum(const char* angfile, const char* ctptfile, const char* dmfile, const char* datasrc, const char* lyrname,

@@ -183,6 +183,16 @@ _SIGNATURES = {
     "tdx_slopeavedown": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
     "tdx_slopeavedown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
     "tdx_tool_slopeavedown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_double]),
+    # ctx, [comm,] hand, catch, slp, nx, ny, hand_nd, catch_nd, slp_nd, dxc, dyc, ids, ncatch, stages, nheight, count, surface, bed, volume, catcharea, stats
+    "tdx_catchhydrogeo": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "tdx_catchhydrogeo_dev": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "tdx_catchhydrogeo_strip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "tdx_tool_catchhydrogeo": (C.c_int, [C.c_char_p] * 6),
+    # ctx, [comm,] hand, catch, mask, nx, ny, hand_nd, catch_nd, mask_nd, dxc, dyc, ids, depth, nfc, map, area, stats
+    "tdx_inundepth": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "tdx_inundepth_dev": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "tdx_inundepth_strip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "tdx_tool_inundepth": (C.c_int, [C.c_char_p] * 7),
     "tdx_dinfdistup_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),

@@ -442,6 +442,63 @@ class Context:
                                                   C.c_void_p(dyc.ctypes.data), float(dn), int(niter) if niter else 0, po, C.byref(st)), self._h)
         return (out, st.as_dict()) if stats else out
 
+    def catchhydrogeo(self, hand, catch, slp, ids, stages, *, dx=1.0, dy=1.0, hand_nodata=float(ANG_NODATA), catch_nodata=-9999, slp_nodata=-1.0, stats=False):
+        """count, surface, bed, volume, catcharea = catchhydrogeo(hand, catch, slp, ids, stages)  (src/CatchHydroGeo.cpp:69).
+
+        Per listed catchment id and stage: the cells of the catchment whose hand is below the stage (or within 1e-6 of 0), their plan area,
+        bed area and volume; and each catchment's whole plan area.  ids: int32 list (the last row of a repeated id wins, earlier rows stay 0);
+        stages: float64, any order.  count int32 and surface / bed / volume float64 are [len(stages)][len(ids)], catcharea float64 [len(ids)];
+        all numpy arrays on the host.  The fp64 sums are taken in a fixed order: the same input gives the same bits."""
+        ny, nx = hand.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32)).reshape(-1)
+        stages = np.ascontiguousarray(np.asarray(stages, dtype=np.float64)).reshape(-1)
+        nc, nh = ids.size, stages.size
+        ph, dev = self._ptr(hand, np.float32, name="hand")
+        pc, cdev = self._ptr(catch, np.int32, (ny, nx), "catch")
+        ps, sdev = self._ptr(slp, np.float32, (ny, nx), "slp")
+        if cdev != dev or sdev != dev:
+            raise ValueError("all rasters must be on the same side (host or device)")
+        count = np.zeros((nh, nc), np.int32)
+        surface, bed, volume = (np.zeros((nh, nc), np.float64) for _ in range(3))
+        catcharea = np.zeros(nc, np.float64)
+        st = TdxStats()
+        self._sync_torch(hand, catch, slp)
+        v = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        check(self._pick(dev, "tdx_catchhydrogeo")(self._h, ph, pc, ps, nx, ny, float(hand_nodata), int(catch_nodata), float(slp_nodata), v(dxc), v(dyc), v(ids), nc,
+                                                   v(stages), nh, v(count), v(surface), v(bed), v(volume), v(catcharea), C.byref(st)), self._h)
+        res = (count, surface, bed, volume, catcharea)
+        return res + (st.as_dict(),) if stats else res
+
+    def inundepth(self, hand, catch, ids, depth, *, mask=None, area=True, dx=1.0, dy=1.0, hand_nodata=float(ANG_NODATA), catch_nodata=-9999, mask_nodata=-32768,
+                  stats=False):
+        """map, area = inundepth(hand, catch, ids, depth)  (src/InunDepth.cpp:53, the raster part).
+
+        ids / depth: one forecast depth (float32) per id, the last row of a repeated id wins.  map float32, nodata -3.0e38: depth - hand where
+        catch and hand have data, depth >= 0 and depth > hand + 0.001.  mask (int16): as in the reference, with a mask every cell of the map is
+        nodata.  area (float32 per row, None with area=False): plan area of the cells with depth > 0 and depth - hand > 0, at the winning row
+        of each id, 0 elsewhere; summed in fp64 and rounded once."""
+        ny, nx = hand.shape
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32)).reshape(-1)
+        depth = np.ascontiguousarray(np.asarray(depth, dtype=np.float32)).reshape(-1)
+        if ids.size != depth.size:
+            raise ValueError("ids and depth: need equal lengths")
+        out = self._out(hand, np.float32, (ny, nx))
+        ph, dev = self._ptr(hand, np.float32, name="hand")
+        pc, cdev = self._ptr(catch, np.int32, (ny, nx), "catch")
+        pm, mdev = self._ptr(mask, np.int16, (ny, nx), "mask")
+        po, _ = self._ptr(out, np.float32, (ny, nx), "map")
+        if cdev != dev or (mask is not None and mdev != dev):
+            raise ValueError("all rasters must be on the same side (host or device)")
+        wet = np.zeros(ids.size, np.float32) if area else None
+        st = TdxStats()
+        self._sync_torch(hand, catch, mask)
+        v = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        check(self._pick(dev, "tdx_inundepth")(self._h, ph, pc, pm, nx, ny, float(hand_nodata), int(catch_nodata), int(mask_nodata), v(dxc), v(dyc), v(ids), v(depth),
+                                               ids.size, po, v(wet) if area else None, C.byref(st)), self._h)
+        return (out, wet, st.as_dict()) if stats else (out, wet)
+
     def gagewatershed(self, p, outlets, *, nodata=int(P_NODATA), stats=False):
         """gw, id_table = gagewatershed(p, outlets)  (src/gagewatershed.cpp:56): every cell gets the id of the first gauge downstream of it.
 
@@ -600,6 +657,18 @@ class Context:
         torch.cuda.synchronize(self.device)
         check(self._lib.tdx_synth_dem_dev(self._h, int(seed), nx, ny, int(x0), int(y0), int(base_wavelength), C.c_void_p(t.data_ptr())), self._h)
         return t
+
+
+def catchhydrogeo(hand, catch, slp, ids, stages, device=0, **kw):
+    """Context(device).catchhydrogeo(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.catchhydrogeo(hand, catch, slp, ids, stages, **kw)
+
+
+def inundepth(hand, catch, ids, depth, device=0, **kw):
+    """Context(device).inundepth(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.inundepth(hand, catch, ids, depth, **kw)
 
 
 def synth_base_wavelength(n: int) -> int:

@@ -29,6 +29,8 @@
 //   tdx_tool_flowdircond         <- flowdircond()         src/flowdircond.cpp:54-252
 //   tdx_tool_d8vdisttostrm       <- d8vdistdown()         src/D8VDistToStrm.cpp:58-276
 //   tdx_tool_slopeavedown        <- sloped()              src/SlopeAveDown.cpp:59-330
+//   tdx_tool_catchhydrogeo       <- catchhydrogeo()       src/CatchHydroGeo.cpp:69-413
+//   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -42,6 +44,7 @@
 
 #include "context.hpp"
 #include "geotiff.hpp"
+#include "hand_tables.hpp"
 #include "outlets.hpp"
 #include "tool_strips.hpp"
 
@@ -221,7 +224,8 @@ enum class Footer {
     Times,         // <label>: N + read / compute / write / total
     HeaderTimes,   // PitRemove: a header read time of its own (src/flood.cpp:517-519)
     FlowDir,       // D8FlowDir / DinfFlowDir: slopes and flats apart, the slope raster written in between (src/d8.cpp, src/dinf.cpp)
-    CountOnly      // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
+    CountOnly,     // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
+    ComputeOnly    // CatchHydroGeo / InunDepth: one line, <label>: the whole run in seconds
 };
 
 template <class T> constexpr tdx::DType dtype_of();
@@ -314,6 +318,7 @@ struct ToolRun {
                    label, nproc, 0.0, readt - begint, slope_s, midt - computet, (computet - readt) - slope_s, writet - midt, writet - begint);
             break;
         case Footer::CountOnly: printf("%s: %d\n", label, nproc); break;
+        case Footer::ComputeOnly: printf("%s: %f\n", label, writet - begint); break;
         }
         if (stats_name) print_gpu_stats(stats_name, st, grid->info.nx * grid->info.ny);
         return 0;
@@ -969,6 +974,108 @@ int tdx_tool_slopeavedown(const char* pfile, const char* felfile, const char* sl
     if (!ok) return t.rc;
     t.output(slpdfile, sd, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT, like pIO (src/SlopeAveDown.cpp:302-304)
     return t.finish("Processors", "slopeavedown");
+}
+
+// hand, catch (LONG), slp, each compared with hand: a mismatch returns 1 without a word.  Then the catchment list and the stage file; a list that cannot be
+// used ends the run with the reference's message and 1 (the reference calls exit(1) there).  With N GPUs every strip returns its own sums and they are
+// added here in strip order.
+int tdx_tool_catchhydrogeo(const char* handfile, const char* catchfile, const char* catchlistfile, const char* slpfile, const char* hfile, const char* hpfile) {
+    ToolRun t("CatchHydroGeo");
+    Raster hand, cat, slp;
+    t.input(handfile, F32, hand);
+    t.input(catchfile, I32, cat, Mismatch::Silent);
+    t.input(slpfile, F32, slp, Mismatch::Silent);
+    if (!t.read_done()) return t.rc;
+    handtables::CatchList cl;
+    std::vector<double> stage;
+    if (!handtables::read_catch_list(catchlistfile, cl)) return 1;
+    if (!handtables::read_stages(hfile, stage)) { fprintf(stderr, "taudem_amd: cannot open stage file %s\n", hfile); return TDX_ERR_FILE; }
+    const int64_t nc = int64_t(cl.id.size()), nh = int64_t(stage.size());
+    const size_t nt = size_t(nc) * size_t(nh);
+    struct Sums {
+        std::vector<int32_t> count;
+        std::vector<double> surface, bed, volume, area;
+        void size(size_t nt, size_t nc) { count.assign(nt, 0); surface.assign(nt, 0.0); bed.assign(nt, 0.0); volume.assign(nt, 0.0); area.assign(nc, 0.0); }
+    } total;
+    total.size(nt, size_t(nc));
+    std::vector<Sums> part(size_t(std::max(tool_gpus(), 1)));
+    const float h_nd = (float)hand.info.nodata, s_nd = (float)slp.info.nodata;
+    const int32_t c_nd = (int32_t)cat.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_catchhydrogeo(c, hand.f.data(), cat.l.data(), slp.f.data(), hand.info.nx, hand.info.ny, h_nd, c_nd, s_nd, hand.info.dxc.data(), hand.info.dyc.data(),
+                                     cl.id.data(), nc, stage.data(), nh, total.count.data(), total.surface.data(), total.bed.data(), total.volume.data(), total.area.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_h = j.in(hand.f), *d_s = j.in(slp.f);
+            int32_t* d_c = j.in(cat.l);
+            if (j.error) return j.error;
+            Sums& p = part[size_t(j.rank)];
+            p.size(nt, size_t(nc));
+            return tdx_catchhydrogeo_strip(j.ctx, j.comm, d_h, d_c, d_s, j.nx, j.nyl, h_nd, c_nd, s_nd, j.dxs.data(), j.dys.data(), cl.id.data(), nc, stage.data(), nh,
+                                           p.count.data(), p.surface.data(), p.bed.data(), p.volume.data(), p.area.data(), s);
+        });
+    if (!ok) return t.rc;
+    if (t.nproc > 1)
+        for (int r = 0; r < t.nproc; r++) {   // strip order: fixed
+            const Sums& p = part[size_t(r)];
+            for (size_t i = 0; i < nt; i++) { total.count[i] += p.count[i]; total.surface[i] += p.surface[i]; total.bed[i] += p.bed[i]; total.volume[i] += p.volume[i]; }
+            for (size_t i = 0; i < size_t(nc); i++) total.area[i] += p.area[i];
+        }
+    if (!handtables::write_hydroprop(hpfile, cl, stage, total.count, total.surface, total.bed, total.volume, total.area)) {
+        printf("Error opening file %s.\n", hpfile);
+        fflush(stdout);
+        return TDX_ERR_FILE;
+    }
+    return t.finish("Compute time", "catchhydrogeo", Footer::ComputeOnly);
+}
+
+// hand, catch (LONG), the mask (SHORT) when given, each compared with hand: a mismatch returns 1 without a word.  maskfile / depthfile: NULL or "" when
+// not given.  With a mask the depth raster is nodata everywhere, as in the reference (its line 465); the depth CSV is not affected.
+int tdx_tool_inundepth(const char* handfile, const char* catchfile, const char* maskfile, const char* fcfile, const char* hpfile, const char* mapfile, const char* depthfile) {
+    ToolRun t("InunDepth");
+    const bool use_mask = maskfile && *maskfile, want_depths = depthfile && *depthfile;
+    Raster hand, cat, mask;
+    t.input(handfile, F32, hand);
+    t.input(catchfile, I32, cat, Mismatch::Silent);
+    if (use_mask) t.input(maskfile, I16, mask, Mismatch::Silent);
+    if (!t.read_done()) return t.rc;
+    handtables::Forecast fc;
+    if (!handtables::read_forecast(fcfile, hpfile, fc)) return 1;
+    const int64_t nfc = int64_t(fc.id.size());
+    std::vector<float> map(t.cells()), area(want_depths ? size_t(nfc) : 0);
+    std::vector<std::vector<double>> part(size_t(std::max(tool_gpus(), 1)));
+    const float h_nd = (float)hand.info.nodata;
+    const int32_t c_nd = (int32_t)cat.info.nodata;
+    const int16_t m_nd = use_mask ? (int16_t)mask.info.nodata : int16_t(0);
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_inundepth(c, hand.f.data(), cat.l.data(), use_mask ? mask.s.data() : nullptr, hand.info.nx, hand.info.ny, h_nd, c_nd, m_nd, hand.info.dxc.data(),
+                                 hand.info.dyc.data(), fc.id.data(), fc.depth.data(), nfc, map.data(), want_depths ? area.data() : nullptr, s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float* d_h = j.in(hand.f);
+            int32_t* d_c = j.in(cat.l);
+            int16_t* d_m = use_mask ? j.in(mask.s) : nullptr;
+            float* d_map = j.out(map);
+            if (j.error) return j.error;
+            std::vector<double>& p = part[size_t(j.rank)];
+            if (want_depths) p.assign(size_t(nfc), 0.0);
+            return tdx_inundepth_strip(j.ctx, j.comm, d_h, d_c, d_m, j.nx, j.nyl, h_nd, c_nd, m_nd, j.dxs.data(), j.dys.data(), fc.id.data(), fc.depth.data(), nfc, d_map,
+                                       want_depths ? p.data() : nullptr, s);
+        });
+    if (!ok) return t.rc;
+    if (want_depths) {
+        if (t.nproc > 1)
+            for (size_t i = 0; i < size_t(nfc); i++) {
+                double sum = 0.0;
+                for (int r = 0; r < t.nproc; r++) sum += part[size_t(r)][i];   // strip order, rounded once
+                area[i] = float(sum);
+            }
+        handtables::write_depths(depthfile, fc, area);
+    }
+    t.output(mapfile, map, hand, (double)-3.0e38f);   // felNodata, header of hand (src/InunDepth.cpp:446,521)
+    return t.finish("Inundation depth Compute time", "inundepth", Footer::ComputeOnly);
 }
 
 }  // extern "C"

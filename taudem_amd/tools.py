@@ -137,6 +137,17 @@ def sloped(pfile, felfile, slpdfile, dn=50.0):
 slopeavedown = sloped
 
 
+def catchhydrogeo(handfile, catchfile, catchlistfile, slpfile, hfile, hpfile):
+    """src/CatchHydroGeo.cpp:69 (CatchHydroGeo)"""
+    return _lib.load().tdx_tool_catchhydrogeo(_b(handfile), _b(catchfile), _b(catchlistfile), _b(slpfile), _b(hfile), _b(hpfile))
+
+
+def inundepth(handfile, catchfile, maskfile, fcfile, hpfile, mapfile, depthfile=None):
+    """src/InunDepth.cpp:53 (InunDepth); maskfile / depthfile None or "": not given.  With a mask the map is nodata everywhere, as in the reference."""
+    return _lib.load().tdx_tool_inundepth(_b(handfile), _b(catchfile), _b(maskfile) if maskfile else None, _b(fcfile), _b(hpfile), _b(mapfile),
+                                          _b(depthfile) if depthfile else None)
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
