@@ -209,6 +209,17 @@ def test_strips_with_random_cuts(ctx, restate, seed):
     check_sums(got, ref, M.exact_sums(hand, cat, slp, dxc, dyc, ids, STAGES), f"strips cut at {cuts}")
 
 
+def test_strips_of_one_row(ctx, restate):
+    """Every strip one row tall (what --gpus 8 makes of a short raster): both halo rows of a strip are its neighbours' only owned rows."""
+    ny, nx = 12, 150
+    hand, cat, slp = seeded((ny, nx), 23, 6)
+    ids = np.arange(1, 7, dtype=np.int32)
+    dxc, dyc = np.full(ny, 30.0) + 0.01 * np.arange(ny), np.full(ny, 28.0)
+    got = _strips(ctx, hand, cat, slp, dxc, dyc, ids, STAGES, list(range(1, ny)))
+    ref = restate.chg_sums(hand, cat, slp, dxc, dyc, ids, STAGES)
+    check_sums(got, ref, M.exact_sums(hand, cat, slp, dxc, dyc, ids, STAGES), "12 strips of one row")
+
+
 def _write_rasters(d, g):
     gt, geo = tuple(g["gt"]), bool(g["geographic"])
     f = lambda s: os.path.join(str(d), s)  # noqa: E731

@@ -4,7 +4,22 @@ D8HDistToStrm, GageWatershed, GridNet, D8FlowPathExtremeUp and Threshold, each f
 located in the tool itself, each held bit for bit to its pinned restatement (tests/downstream.py), the -id text byte for byte.  The
 restatements are held to the reference on reduced versions of these rasters by tests/test_pathological_restatements.py; the GPU is held
 to those fixtures directly as well.  Strips of one and two rows: both halo rows belong to neighbours whose only owned row is the one
-exchanged (`--gpus 8` on a 5-row raster runs five 1-row ranks, capi_tools.cpp)."""
+exchanged (`--gpus 8` on a 5-row raster runs five 1-row ranks, capi_tools.cpp).
+
+The five sweep tools that came later - RetLimFlow, DinfAvalanche, FlowDirCond, D8VDistToStrm, SlopeAveDown - run in the same four settings
+in tests of their own (test_late_tools_*: downstream.extras_late / reference_late / single_late / strip_late / compare_late), so that a
+failure names the tool and the tests above keep their times.  DinfAvalanche is compared by aval_model.compare_aval; every line it prints
+holds the cells with rz data and the tainted share.  The restatement alone, with the sources extras_late chooses (path / -direct at
+alpha 18, path / -direct at alpha 1; no tainted cell in any of them):
+
+    ramp_diag       168 /   1,  68 646 /    755   (-direct: one source cell; scattered sources taint 12 - 55 % of a -direct runout)
+    ramp_antidiag   170 /   1,  70 084 /  7 132   (the same)
+    ramp_x          148 / 148,  14 887 / 14 887        ramp_-x       168 / 168,  16 024 / 16 024
+    ramp_y          164 / 164,  13 584 / 13 584        ramp_-y       141 / 141,  11 933 / 11 933
+    spiral        2 939 / 3 076,  9 264 /  9 557       nan_cells     210 / 210,   7 065 /  7 401
+    +inf_cells      207 / 207,   7 173 /  7 634        -inf_cells    186 / 186,   6 130 /  6 472
+    plane 239, ramp_shallow 171, checkerboard_pits 153 in all four (the sources alone: nothing slopes by a degree)
+    one_row, one_column, two_rows, one_data_cell, all_nodata: none (every cell is an edge cell without a direction)"""
 import time
 
 import numpy as np
@@ -41,12 +56,40 @@ def test_downstream_on_pathological_input(name, ctx, oracle, R, monkeypatch):
     assert not bad, "\n".join(bad)
 
 
+def _late_inputs(oracle, R, dem, dx, dy, seed, i, name=None, cut=()):
+    """derive() and extras_late() for one raster; a case of tests/pathological.py by `name` runs the avalanche on 30 x 40 cells, with its
+    floor and its -direct sources (downstream.LATE_FLOOR / LATE_DIRECT)."""
+    inp = D.derive(oracle, dem, dx, dy, seed, cut_rows=cut)
+    return D.extras_late(inp, seed, R, dx, dy, i, direct=D.LATE_DIRECT.get(name, "scattered"), floor=D.LATE_FLOOR.get(name, 0), aval_rows=name is None)
+
+
+@pytest.mark.parametrize("name", sorted(P.CASES))
+def test_late_tools_on_pathological_input(name, ctx, oracle, R, monkeypatch):
+    monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
+    i = sorted(P.CASES).index(name)
+    dem = P.CASES[name](oracle)
+    dx, dy = _sizes(i, dem.shape[0])
+    inp = _late_inputs(oracle, R, dem, dx, dy, 60 + i, i, name)
+    ref = D.reference_late(R, inp, dx, dy, i)
+    bad = D.compare_late(D.single_late(ctx, inp, dx, dy, i), ref, name)
+    assert not bad, "\n".join(bad)
+
+
 @pytest.mark.parametrize("name", F.names())
 def test_downstream_matches_reference_fixtures(name, ctx, monkeypatch):
     """The GPU against the reference's own rasters on the reduced pathological inputs (tests/golden/make_golden_pathological.py)."""
     monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
     g = F.load(name)
     bad = D.compare(F.gpu(ctx, g), F.expected(g), f"patho_{name}")
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("name", F.late_names())
+def test_late_tools_match_reference_fixtures(name, ctx, R, monkeypatch):
+    """The GPU against the reference's own rasters on the reduced pathological inputs (tests/golden/make_golden_patholate.py)."""
+    monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
+    g, inp = F.load_late(name)
+    bad = D.compare_late(D.single_late(ctx, inp, F.DX, F.DY, int(g["index"])), F.expected_late(g, R, inp), f"patholate_{name}")
     assert not bad, "\n".join(bad)
 
 
@@ -99,6 +142,51 @@ def test_strips_of_one_and_two_rows(label, make, world, oracle, R, monkeypatch):
     _in_strips(oracle, R, dem, world, dx, dy, i, label)
 
 
+def _late_in_strips(oracle, R, dem, world, dx, dy, i, label, name=None):
+    """The five late tools' strip entry points on `dem` cut into `world` strips against the restatements on the global rasters."""
+    import torch
+
+    from taudem_amd.distributed import StripGroup, StripPipeline, partition_rows, strip_rows
+
+    ny, nx = dem.shape
+    parts = partition_rows(ny, world)
+    cut = sorted({y for y0, y1 in parts for y in (y0 - 1, y0, y1 - 1, y1) if 0 <= y < ny})
+    inp = _late_inputs(oracle, R, dem, dx, dy, 80 + i, i, name, cut)
+    ref = D.reference_late(R, inp, dx, dy, i)
+    dns = D.late_dns(dx, dy, i)
+    with StripGroup(world, nx, [0] * world) as grp:
+        def rank_main(r, c, comm):
+            y0, y1 = parts[r]
+            nyl = y1 - y0
+            pipe = StripPipeline(c, comm, nx, nyl)
+
+            def put(a):
+                t = pipe.empty(getattr(torch, np.asarray(a).dtype.name))
+                t[1:nyl + 1] = torch.from_numpy(np.ascontiguousarray(a[y0:y1])).cuda()
+                return t
+            return D.strip_late(pipe, put, inp, strip_rows(dx, y0, y1), strip_rows(dy, y0, y1), y0, y1, ny, dns, i)
+        res = grp.run(rank_main)
+    bad = D.compare_late({k: np.concatenate([r[k] for r in res], axis=0) for k in res[0]}, ref, label)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("label,make,world", SHORT, ids=[s[0].replace(" ", "_") for s in SHORT])
+def test_late_tools_in_strips_of_one_and_two_rows(label, make, world, oracle, R, monkeypatch):
+    monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
+    i = [s[0] for s in SHORT].index(label)
+    dem = make(oracle)
+    dx, dy = _sizes(i, dem.shape[0])
+    _late_in_strips(oracle, R, dem, world, dx, dy, i, label, "two_rows" if label.startswith("two_rows") else None)
+
+
+@pytest.mark.parametrize("name", ["spiral", "plane", "checkerboard_pits", "nan_cells", "one_data_cell"])
+def test_late_tools_pathological_in_three_strips(name, oracle, R, monkeypatch):
+    monkeypatch.setenv("TDX_SWEEP_VERIFY", "1")
+    i = sorted(P.CASES).index(name)
+    dem = P.CASES[name](oracle)
+    _late_in_strips(oracle, R, dem, 3, *_sizes(i, dem.shape[0]), i, f"{name} in 3 strips", name)
+
+
 @pytest.mark.parametrize("name", ["spiral", "plane", "checkerboard_pits", "nan_cells", "one_data_cell"])
 def test_pathological_downstream_in_three_strips(name, oracle, R, monkeypatch):
     """the downstream counterpart of test_gpu_pathological.py::test_pathological_input_in_three_strips"""
@@ -112,7 +200,8 @@ def test_pathological_downstream_in_three_strips(name, oracle, R, monkeypatch):
 def test_spiral_at_2048_downstream(ctx, oracle, R, capsys):
     """The longest dependency chain the sweeps can meet, for the tools downstream of the directions: a spiral channel at 2048^2 (pitch 8:
     256 windings, a flow path of ~500 k cells).  Every stage is checked on every cell against its restatement; its ms_total / rounds are
-    printed.  The first MI355X run took 4.4 s of wall for the nine stages (0.27 - 0.73 s each, one round each); the bound is 60 s, as for
+    printed.  The first MI355X run took 4.4 s of wall for the first nine stages (0.27 - 0.73 s each, one round each); RetLimFlow,
+    FlowDirCond and D8VDistToStrm (its single source at the outlet) are stages ten to twelve; the bound is 60 s, as for
     test_gpu_pathological.py::test_spiral_at_4096_completes."""
     import torch
 
@@ -133,9 +222,13 @@ def test_spiral_at_2048_downstream(ctx, oracle, R, capsys):
     src16 = src.astype(np.int16)
     gauges = (np.array([outlet[1], mid[1]], np.int32), np.array([outlet[0], mid[0]], np.int32), np.array([7, 3], np.int32))
     sa = (rng.integers(-4, 5, (ny, nx)) * 0.5).astype(np.float32)
+    late = np.random.default_rng([2048, 1])                               # (a generator of its own: the draws above keep their bits)
+    wg = (late.integers(0, 33, (ny, nx)) / 8.0).astype(np.float32)
+    rc = (late.integers(0, 9, (ny, nx)) / 8.0).astype(np.float32)
+    z = (fel + np.rint(late.normal(0.0, 3.0, (ny, nx)) * 16.0) / 16.0).astype(np.float32)
     d = f"cuda:{ctx.device}"
     T = {k: torch.from_numpy(np.ascontiguousarray(v)).to(d) for k, v in (("p", p), ("ang", ang), ("fel", fel), ("dg", dg), ("w", w), ("src", src),
-                                                                          ("src16", src16), ("sa", sa))}
+                                                                          ("src16", src16), ("sa", sa), ("wg", wg), ("rc", rc), ("z", z))}
     stages = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -153,6 +246,9 @@ def test_spiral_at_2048_downstream(ctx, oracle, R, capsys):
     gw, table = run("gagewatershed", lambda: ctx.gagewatershed(T["p"], gauges, stats=True))
     plen, tlen, gord = run("gridnet", lambda: ctx.gridnet(T["p"], -32768, 30.0, 30.0, stats=True))
     xup, = run("d8flowpathextremeup", lambda: ctx.d8flowpathextremeup(T["p"], T["sa"], -32768, usemax=True, contcheck=False, stats=True))
+    qrl, = run("retlimflow", lambda: ctx.retlimflow(T["ang"], T["wg"], T["rc"], dx=30.0, dy=30.0, stats=True))
+    zfdc, = run("flowdircond", lambda: ctx.flowdircond(T["p"], T["z"], z_nodata=D.FEL_ND, stats=True))
+    vd, = run("d8vdisttostrm", lambda: ctx.d8vdisttostrm(T["p"], T["fel"], T["src"], 1, src_nodata=D.SRC_ND, stats=True))
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     with capsys.disabled():
@@ -171,6 +267,8 @@ def test_spiral_at_2048_downstream(ctx, oracle, R, capsys):
     pl_o, tl_o, go_o = o.gridnet(p, -32768, 30.0, 30.0)
     checks += [("plen", plen, pl_o), ("tlen", tlen, tl_o), ("gord", gord, go_o)]
     checks.append(("xup", xup, o.d8flowpathextremeup(p, sa, -32768, usemax=True, contcheck=False)))
+    checks += [("qrl", qrl, R.aval.retlimflow(ang, wg, rc, dxc=30.0, dyc=30.0)), ("zfdc", zfdc, R.last.flowdircond(p, z, D.FEL_ND)),
+               ("vd", vd, R.last.vdist(p, fel, src, 1, src_nodata=D.SRC_ND))]
     bad = [describe_diff(a, b, f"spiral 2048^2: {k}") for k, a, b in checks if not bits_equal(a, b)]
     import d8rev_model
 

@@ -2,10 +2,13 @@
 versions of tests/pathological.py's rasters: a plane, ramps, a checkerboard of pits, a spiral channel, 1 x N / N x 1 / 2 x N rasters,
 all-nodata, one data cell, NaN and +-Inf cells).  The five fractal goldens pin them on terrain-like rasters only; the GPU tests on the
 pathological rasters (tests/test_gpu_pathological.py, tests/test_gpu_pathological_downstream.py) trust them at full size.  Every tool
-from PitRemove to the downstream tools, bit for bit; GageWatershed's -id text byte for byte."""
+from PitRemove to the downstream tools, bit for bit; GageWatershed's -id text byte for byte.  The five late sweep tools have fixtures of
+their own (patholate_*.npz): qrl, zfdc, vd* and slpd* bit for bit; rz / dfs under the rule of tests/test_aval_restatement.py - bit for bit
+where the host's libc is the one that made the fixtures (the reference calls its float atan), and under aval_model.compare_aval anywhere."""
 import numpy as np
 import pytest
 
+import aval_model
 import downstream as D
 import patho_fixture as F
 from conftest import bits_equal, describe_diff
@@ -60,3 +63,29 @@ def test_downstream_restatements_match_reference(name, R):
     assert set(got) == set(exp)
     bad = D.compare(got, exp, name)
     assert not bad, "\n".join(bad)
+
+
+def test_late_fixtures_cover_the_cases():
+    assert F.late_names() == NAMES
+    assert {n for n in NAMES if str(F.load_late(n)[0]["direct"]) == "single"} == set(D.LATE_DIRECT) & set(NAMES)
+
+
+@pytest.mark.parametrize("name", F.late_names())
+def test_late_restatements_match_reference(name, R, oracle):
+    g, inp = F.load_late(name)
+    i = int(g["index"])
+    ang_a = oracle.dinfflowdir(inp["fel"], D.FEL_ND, *D.PYTH)[0]
+    assert bits_equal(ang_a, g["in_ang_a"]), describe_diff(ang_a, g["in_ang_a"], f"{name}: the angles on 30 x 40 cells")
+    got = D.reference_late(R, inp, F.DX, F.DY, i)
+    exp = F.expected_late(g, R, inp)
+    assert set(got) == set(exp)
+    bad = D.compare_late(got, exp, name)        # everything but rz / dfs bit for bit; rz / dfs under the tolerant rule
+    if str(g["libc"]) == aval_model.libc_tag():
+        bad += [describe_diff(got[k], exp[k], f"{name}: {k} (same libc: bit for bit)") for k in exp if k[:3] in ("rz_", "dfs") and not bits_equal(got[k], exp[k])]
+    assert not bad, "\n".join(bad)
+    # the chosen sources are the ones extras_late chooses again, and every other new input is drawn again with the same bits
+    again = D.extras_late({k: v for k, v in F.inputs(F.load(name)).items()} | {"ang_a": g["in_ang_a"]}, 40 + i, R, F.DX, F.DY, i,
+                          direct=D.LATE_DIRECT.get(name, "scattered"))
+    for k in g:
+        if k.startswith("in_"):
+            assert bits_equal(again[k[3:]], g[k]), k
