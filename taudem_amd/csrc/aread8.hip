@@ -1463,13 +1463,19 @@ static int aread8_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t 
     return TDX_OK;
 }
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int aread8_check(tdx_context* ctx, const void* p, const void* out, int64_t nx, int64_t ny, int64_t halo, const int32_t* outlet_x, const int32_t* outlet_y,
+                        int64_t n_outlets, const char* who) {
+    if (!ctx || !p || !out || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    if (too_big(nx, ny + halo)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (n_outlets > 0 && (!outlet_x || !outlet_y)) return tdx_fail(ctx, TDX_ERR_ARG, "outlets missing");
+    return TDX_OK;
+}
+
 extern "C" int tdx_aread8_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata,
                                    const float* d_w, float w_nodata, int contcheck, const int32_t* outlet_x, const int32_t* outlet_row,
                                    int64_t n_outlets, float* d_ad8, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_ad8 || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_aread8_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
-    if (n_outlets > 0 && (!outlet_x || !outlet_row)) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_aread8_strip: outlets missing");
+    if (int rc = aread8_check(ctx, d_p, d_ad8, nx, ny_local, 2, outlet_x, outlet_row, n_outlets, "tdx_aread8_strip: bad argument")) return rc;
     return aread8_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_w, w_nodata, contcheck, outlet_x, outlet_row, n_outlets, d_ad8,
                        stats);
 }
@@ -1478,10 +1484,7 @@ extern "C" int tdx_aread8_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, 
                               const float* d_w, float w_nodata, int contcheck,
                               const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets,
                               float* d_ad8, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_ad8 || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_aread8_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
-    if (n_outlets > 0 && (!outlet_x || !outlet_y)) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_aread8_dev: outlets missing");
+    if (int rc = aread8_check(ctx, d_p, d_ad8, nx, ny, 0, outlet_x, outlet_y, n_outlets, "tdx_aread8_dev: bad argument")) return rc;
     return aread8_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_w, w_nodata, contcheck, outlet_x, outlet_y, n_outlets,
                        d_ad8, stats);
 }
@@ -1491,23 +1494,17 @@ extern "C" int tdx_aread8(tdx_context* ctx, const int16_t* p, int64_t nx, int64_
                           const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets,
                           float* ad8, tdx_stats* stats) {
     if (!ctx || !p || !ad8 || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_aread8: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_w = w ? static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4)) : nullptr;
-    if (!d_p || !d_a || (w && !d_w)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    if (w) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, w, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_aread8_dev(ctx, d_p, nx, ny, p_nodata, d_w, w_nodata, contcheck, outlet_x, outlet_y, n_outlets, d_a, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ad8, d_a, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    float* d_a = h.out(TDX_S_IO1, ad8);
+    float* d_w = h.in(TDX_S_IO2, w);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_aread8_dev(ctx, d_p, nx, ny, p_nodata, d_w, w_nodata, contcheck, outlet_x, outlet_y, n_outlets, d_a, stats));
 }
 
 // ---- D8FlowPathExtremeUp (src/D8flowpathextremeup.cpp:58-285): the same dependency sweep, outlets closure and strip
 // protocol as the weighted AreaD8, with max / min instead of the sum.  sa: the grid whose upstream extreme is sought; ssa: result, nodata
-// -FLT_MAX (MISSINGFLOAT, src/commonLib.h:80).
+// -FLT_MAX (MISSINGFLOAT, src/commonLib.h:80).  The device forms test what AreaD8's test (aread8_check), and that sa is there.
 static int extremeup_check(tdx_context* ctx, const void* p, const void* sa, const void* ssa, int64_t nx, int64_t ny, const char* who) {
     if (!ctx || !p || !sa || !ssa || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
     return TDX_OK;
@@ -1516,9 +1513,8 @@ extern "C" int tdx_d8flowpathextremeup_dev(tdx_context* ctx, const int16_t* d_p,
                                            int contcheck, const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_ssa,
                                            tdx_stats* stats) {
     int rc = extremeup_check(ctx, d_p, d_sa, d_ssa, nx, ny, "tdx_d8flowpathextremeup_dev: bad argument");
+    if (rc == TDX_OK) rc = aread8_check(ctx, d_p, d_ssa, nx, ny, 0, outlet_x, outlet_y, n_outlets, "tdx_d8flowpathextremeup_dev: bad argument");
     if (rc != TDX_OK) return rc;
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
-    if (n_outlets > 0 && (!outlet_x || !outlet_y)) return tdx_fail(ctx, TDX_ERR_ARG, "outlets missing");
     return aread8_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_sa, 0.f, contcheck, outlet_x, outlet_y, n_outlets, d_ssa, stats,
                        D8Expr{usemax ? D8X_MAX : D8X_MIN, -FLT_MAX});
 }
@@ -1526,27 +1522,18 @@ extern "C" int tdx_d8flowpathextremeup_strip(tdx_context* ctx, const tdx_comm* c
                                              const float* d_sa, int usemax, int contcheck, const int32_t* outlet_x, const int32_t* outlet_row,
                                              int64_t n_outlets, float* d_ssa, tdx_stats* stats) {
     int rc = extremeup_check(ctx, d_p, d_sa, d_ssa, nx, ny_local, "tdx_d8flowpathextremeup_strip: bad argument");
+    if (rc == TDX_OK) rc = aread8_check(ctx, d_p, d_ssa, nx, ny_local, 2, outlet_x, outlet_row, n_outlets, "tdx_d8flowpathextremeup_strip: bad argument");
     if (rc != TDX_OK) return rc;
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
-    if (n_outlets > 0 && (!outlet_x || !outlet_row)) return tdx_fail(ctx, TDX_ERR_ARG, "outlets missing");
     return aread8_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_sa, 0.f, contcheck, outlet_x, outlet_row, n_outlets, d_ssa, stats,
                        D8Expr{usemax ? D8X_MAX : D8X_MIN, -FLT_MAX});
 }
 extern "C" int tdx_d8flowpathextremeup(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* sa, int usemax, int contcheck,
                                        const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* ssa, tdx_stats* stats) {
-    int rc = extremeup_check(ctx, p, sa, ssa, nx, ny, "tdx_d8flowpathextremeup: bad argument");
-    if (rc != TDX_OK) return rc;
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_w = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_p || !d_a || !d_w) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, sa, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = tdx_d8flowpathextremeup_dev(ctx, d_p, nx, ny, p_nodata, d_w, usemax, contcheck, outlet_x, outlet_y, n_outlets, d_a, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ssa, d_a, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    if (int rc = extremeup_check(ctx, p, sa, ssa, nx, ny, "tdx_d8flowpathextremeup: bad argument")) return rc;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    float* d_a = h.out(TDX_S_IO1, ssa);
+    float* d_w = h.in(TDX_S_IO2, sa);
+    if (h.error) return h.error;
+    return h.finish(tdx_d8flowpathextremeup_dev(ctx, d_p, nx, ny, p_nodata, d_w, usemax, contcheck, outlet_x, outlet_y, n_outlets, d_a, stats));
 }

@@ -957,12 +957,21 @@ int dinf_outlet_recode(tdx_context* ctx, const Strip& st, const float* d_ang, fl
     return TDX_OK;
 }
 
+// the argument tests of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int areadinf_check(tdx_context* ctx, const void* ang, const void* sca, const void* dxc, const void* dyc, int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !ang || !sca || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+static int decayaccum_check(tdx_context* ctx, const void* ang, const void* dm, const void* dsca, const void* dxc, const void* dyc, int64_t nx, int64_t ny,
+                            int64_t halo, const char* who) {
+    if (!ctx || !ang || !dm || !dsca || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_areadinf_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
                                 const double* dxc, const double* dyc, const float* d_w, int contcheck,
                                 const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_sca, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_sca || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_areadinf_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = areadinf_check(ctx, d_ang, d_sca, dxc, dyc, nx, ny, 0, "tdx_areadinf_dev: bad argument")) return rc;
     AreaAlg alg{d_w};
     return run_dinf_accum(ctx, alg, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, contcheck, outlet_x, outlet_y, n_outlets,
                           d_sca, TDX_AREA_NODATA, nullptr, 0.f, stats);
@@ -971,9 +980,7 @@ extern "C" int tdx_areadinf_dev(tdx_context* ctx, const float* d_ang, int64_t nx
 extern "C" int tdx_areadinf_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                   const double* dxc, const double* dyc, const float* d_w, int contcheck, const int32_t* outlet_x,
                                   const int32_t* outlet_row, int64_t n_outlets, float* d_sca, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_sca || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_areadinf_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = areadinf_check(ctx, d_ang, d_sca, dxc, dyc, nx, ny_local, 2, "tdx_areadinf_strip: bad argument")) return rc;
     AreaAlg alg{d_w};
     return run_dinf_accum(ctx, alg, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, contcheck, outlet_x, outlet_row, n_outlets,
                           d_sca, TDX_AREA_NODATA, nullptr, 0.f, stats);
@@ -982,9 +989,7 @@ extern "C" int tdx_areadinf_strip(tdx_context* ctx, const tdx_comm* comm, float*
 extern "C" int tdx_dinfdecayaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata,
                                       const double* dxc, const double* dyc, const float* d_dm, float dm_nodata, const float* d_w, int contcheck,
                                       const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_dsca, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dm || !d_dsca || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdecayaccum_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = decayaccum_check(ctx, d_ang, d_dm, d_dsca, dxc, dyc, nx, ny, 0, "tdx_dinfdecayaccum_dev: bad argument")) return rc;
     DecayAlg alg{d_w, d_dm, dm_nodata};
     return run_dinf_accum(ctx, alg, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, contcheck, outlet_x, outlet_y, n_outlets,
                           d_dsca, TDX_ANG_NODATA, nullptr, dm_nodata, stats);
@@ -993,9 +998,7 @@ extern "C" int tdx_dinfdecayaccum_dev(tdx_context* ctx, const float* d_ang, int6
 extern "C" int tdx_dinfdecayaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata,
                                         const double* dxc, const double* dyc, float* d_dm, float dm_nodata, const float* d_w, int contcheck,
                                         const int32_t* outlet_x, const int32_t* outlet_row, int64_t n_outlets, float* d_dsca, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dm || !d_dsca || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdecayaccum_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = decayaccum_check(ctx, d_ang, d_dm, d_dsca, dxc, dyc, nx, ny_local, 2, "tdx_dinfdecayaccum_strip: bad argument")) return rc;
     DecayAlg alg{d_w, d_dm, dm_nodata};
     return run_dinf_accum(ctx, alg, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, contcheck, outlet_x, outlet_row, n_outlets,
                           d_dsca, TDX_ANG_NODATA, d_dm, dm_nodata, stats);
@@ -1005,36 +1008,23 @@ extern "C" int tdx_areadinf(tdx_context* ctx, const float* ang, int64_t nx, int6
                             const double* dxc, const double* dyc, const float* w, int contcheck,
                             const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* sca, tdx_stats* stats) {
     if (!ctx || !ang || !sca || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_areadinf: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_s = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_w = w ? static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4)) : nullptr;
-    if (!d_a || !d_s || (w && !d_w)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (w) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, w, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_areadinf_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, contcheck, outlet_x, outlet_y, n_outlets, d_s, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(sca, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_s = h.out(TDX_S_IO1, sca);
+    float* d_w = h.in(TDX_S_IO2, w);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_areadinf_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, contcheck, outlet_x, outlet_y, n_outlets, d_s, stats));
 }
 
 extern "C" int tdx_dinfdecayaccum(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata,
                                   const double* dxc, const double* dyc, const float* dm, float dm_nodata, const float* w, int contcheck,
                                   const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* dsca, tdx_stats* stats) {
     if (!ctx || !ang || !dm || !dsca || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdecayaccum: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_s = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_d = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    float* d_w = w ? static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4)) : nullptr;
-    if (!d_a || !d_s || !d_d || (w && !d_w)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_d, dm, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (w) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, w, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_dinfdecayaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_d, dm_nodata, d_w, contcheck, outlet_x, outlet_y, n_outlets, d_s, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dsca, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_s = h.out(TDX_S_IO1, dsca);
+    float* d_d = h.in(TDX_S_IO2, dm);
+    float* d_w = h.in(TDX_S_IO3, w);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfdecayaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_d, dm_nodata, d_w, contcheck, outlet_x, outlet_y, n_outlets, d_s, stats));
 }

@@ -121,3 +121,44 @@ static inline int tdx_fail(tdx_context* ctx, int code, const std::string& msg) {
     g_tdx_thread_error = msg;
     return code;
 }
+
+// The host form of a library call: every raster of nx x ny cells gets a scratch slot, in() uploads an input, tdx_x_dev() runs on the device
+// copies and finish() downloads what out() registered (the vocabulary of toolstrips::RankJob, tool_strips.hpp).  The slot is the caller's choice:
+// slots only grow and are shared by every stage on the context.  A null host pointer is an optional raster that is absent.
+struct HostCall {
+    tdx_context* ctx;
+    size_t n;
+    int error = TDX_OK;                     // sticky: TDX_ERR_NOMEM (scratch) or TDX_ERR_HIP (copy); in() / out() do nothing after it
+    struct Out { void* host; const void* dev; size_t bytes; };
+    std::vector<Out> outs;
+    HostCall(tdx_context* c, int64_t nx, int64_t ny) : ctx(c), n(size_t(nx) * size_t(ny)) {}
+    template <class T> T* in(int slot, const T* host) {
+        T* d = buffer(slot, host);
+        if (d) error = copy(d, host, n * sizeof(T), hipMemcpyHostToDevice);
+        return error ? nullptr : d;
+    }
+    template <class T> T* out(int slot, T* host) {
+        T* d = buffer(slot, host);
+        if (d) outs.push_back({host, d, n * sizeof(T)});
+        return d;
+    }
+    int finish(int rc) {                    // rc: what tdx_x_dev() returned.  Without an output there is nothing to wait for: the _dev form has ended its call
+        if (rc != TDX_OK || outs.empty()) return rc;
+        for (const Out& o : outs)
+            if (int e = copy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost)) return e;
+        TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        return TDX_OK;
+    }
+
+private:
+    template <class T> T* buffer(int slot, const T* host) {
+        if (error || !host) return nullptr;
+        T* d = static_cast<T*>(ctx->scratch(slot, n * sizeof(T)));
+        if (!d) error = TDX_ERR_NOMEM;
+        return d;
+    }
+    int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+        return TDX_OK;
+    }
+};

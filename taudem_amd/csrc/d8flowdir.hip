@@ -628,35 +628,31 @@ static int d8flowdir_impl(tdx_context* ctx, const Strip& st, float* d_fel, float
     return rc;
 }
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int d8flowdir_check(tdx_context* ctx, const void* fel, const void* p, const void* dxc, const void* dyc, int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !fel || !p || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_d8flowdir_dev(tdx_context* ctx, const float* d_fel, int64_t nx, int64_t ny, float fel_nodata,
                                  const double* dxc, const double* dyc, int16_t* d_p, float* d_sd8, tdx_stats* stats) {
-    if (!ctx || !d_fel || !d_p || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8flowdir_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8flowdir_check(ctx, d_fel, d_p, dxc, dyc, nx, ny, 0, "tdx_d8flowdir_dev: bad argument")) return rc;
     return d8flowdir_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_fel), fel_nodata, dxc, dyc, d_p, d_sd8, stats);
 }
 
 extern "C" int tdx_d8flowdir_strip(tdx_context* ctx, const tdx_comm* comm, float* d_fel, int64_t nx, int64_t ny_local, float fel_nodata,
                                    const double* dxc, const double* dyc, int16_t* d_p, float* d_sd8, tdx_stats* stats) {
-    if (!ctx || !d_fel || !d_p || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8flowdir_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8flowdir_check(ctx, d_fel, d_p, dxc, dyc, nx, ny_local, 2, "tdx_d8flowdir_strip: bad argument")) return rc;
     return d8flowdir_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_fel, fel_nodata, dxc, dyc, d_p, d_sd8, stats);
 }
 
 extern "C" int tdx_d8flowdir(tdx_context* ctx, const float* fel, int64_t nx, int64_t ny, float fel_nodata,
                              const double* dxc, const double* dyc, int16_t* p, float* sd8, tdx_stats* stats) {
     if (!ctx || !fel || !p || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8flowdir: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_z = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO1, n * 2));
-    float* d_s = sd8 ? static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4)) : nullptr;
-    if (!d_z || !d_p || (sd8 && !d_s)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_z, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_d8flowdir_dev(ctx, d_z, nx, ny, fel_nodata, dxc, dyc, d_p, d_s, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(p, d_p, n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    if (sd8) TDX_HIP_CHECK(ctx, hipMemcpyAsync(sd8, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_z = h.in(TDX_S_IO0, fel);
+    int16_t* d_p = h.out(TDX_S_IO1, p);
+    float* d_s = h.out(TDX_S_IO2, sd8);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_d8flowdir_dev(ctx, d_z, nx, ny, fel_nodata, dxc, dyc, d_p, d_s, stats));
 }

@@ -249,96 +249,86 @@ int gage_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata,
 
 }  // namespace
 
+// the argument tests of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int d8hdist_check(tdx_context* ctx, const void* p, const void* src, const void* dist, const void* dxc, const void* dyc, int64_t nx, int64_t ny, int64_t halo,
+                         const char* who) {
+    if (!ctx || !p || !src || !dist || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+static int d8vdist_check(tdx_context* ctx, const void* p, const void* fel, const void* src, const void* dist, int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !p || !fel || !src || !dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+static int gage_check(tdx_context* ctx, const void* p, const void* gw, int64_t nx, int64_t ny, int64_t halo, const int32_t* outlet_x, const int32_t* outlet_y,
+                      int64_t n_outlets, const void* placed, const void* iddown, const char* who) {
+    if (!ctx || !p || !gw || nx <= 0 || ny <= 0 || n_outlets < 0 || n_outlets > 0x7ffffffe || (n_outlets > 0 && (!outlet_x || !outlet_y || !placed || !iddown)))
+        return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_d8hdisttostrm_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* d_src, int32_t src_nodata,
                                      int32_t thresh, const double* dxc, const double* dyc, float* d_dist, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_src || !d_dist || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8hdisttostrm_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8hdist_check(ctx, d_p, d_src, d_dist, dxc, dyc, nx, ny, 0, "tdx_d8hdisttostrm_dev: bad argument")) return rc;
     return d8dist_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_src, src_nodata, thresh, dxc, dyc, d_dist, stats);
 }
 extern "C" int tdx_d8hdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const int32_t* d_src,
                                        int32_t src_nodata, int32_t thresh, const double* dxc, const double* dyc, float* d_dist, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_src || !d_dist || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8hdisttostrm_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8hdist_check(ctx, d_p, d_src, d_dist, dxc, dyc, nx, ny_local, 2, "tdx_d8hdisttostrm_strip: bad argument")) return rc;
     return d8dist_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_src, src_nodata, thresh, dxc, dyc, d_dist, stats);
 }
 extern "C" int tdx_d8hdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* src, int32_t src_nodata, int32_t thresh,
                                  const double* dxc, const double* dyc, float* dist, tdx_stats* stats) {
     if (!ctx || !p || !src || !dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8hdisttostrm: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    int32_t* d_s = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_p || !d_s || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, src, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_d8hdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_s, src_nodata, thresh, dxc, dyc, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dist, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    int32_t* d_s = h.in(TDX_S_IO1, src);
+    float* d_o = h.out(TDX_S_IO2, dist);
+    if (h.error) return h.error;
+    return h.finish(tdx_d8hdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_s, src_nodata, thresh, dxc, dyc, d_o, stats));
 }
 
 // D8VDistToStrm (d8vdistdown, src/D8VDistToStrm.cpp:58-276): the same sweep with the drop to the receiver as the step.  fel's halo rows are
 // exchanged by the set-up, so the strip form writes them.
 extern "C" int tdx_d8vdisttostrm_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_fel, const int32_t* d_src,
                                      int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_fel || !d_src || !d_dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8vdist_check(ctx, d_p, d_fel, d_src, d_dist, nx, ny, 0, "tdx_d8vdisttostrm_dev: bad argument")) return rc;
     return d8dist_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_src, src_nodata, thresh, nullptr, nullptr, d_dist, stats,
                        const_cast<float*>(d_fel));   // (a single strip has no halo rows: nothing is written)
 }
 extern "C" int tdx_d8vdisttostrm_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, float* d_fel,
                                        const int32_t* d_src, int32_t src_nodata, int32_t thresh, float* d_dist, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_fel || !d_src || !d_dist || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = d8vdist_check(ctx, d_p, d_fel, d_src, d_dist, nx, ny_local, 2, "tdx_d8vdisttostrm_strip: bad argument")) return rc;
     return d8dist_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_src, src_nodata, thresh, nullptr, nullptr, d_dist, stats, d_fel);
 }
 extern "C" int tdx_d8vdisttostrm(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* fel, const int32_t* src,
                                  int32_t src_nodata, int32_t thresh, float* dist, tdx_stats* stats) {
     if (!ctx || !p || !fel || !src || !dist || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_d8vdisttostrm: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    int32_t* d_s = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    float* d_f = static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4));
-    if (!d_p || !d_s || !d_o || !d_f) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, src, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_f, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_d8vdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_f, d_s, src_nodata, thresh, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dist, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    int32_t* d_s = h.in(TDX_S_IO1, src);
+    float* d_o = h.out(TDX_S_IO2, dist);
+    float* d_f = h.in(TDX_S_IO3, fel);
+    if (h.error) return h.error;
+    return h.finish(tdx_d8vdisttostrm_dev(ctx, d_p, nx, ny, p_nodata, d_f, d_s, src_nodata, thresh, d_o, stats));
 }
 
 extern "C" int tdx_gagewatershed_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* outlet_x, const int32_t* outlet_y,
                                      const int32_t* ids, int64_t n_outlets, int32_t* d_gw, int32_t* placed, int32_t* iddown, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_gw || nx <= 0 || ny <= 0 || n_outlets < 0 || n_outlets > 0x7ffffffe || (n_outlets > 0 && (!outlet_x || !outlet_y || !placed || !iddown)))
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gagewatershed_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = gage_check(ctx, d_p, d_gw, nx, ny, 0, outlet_x, outlet_y, n_outlets, placed, iddown, "tdx_gagewatershed_dev: bad argument")) return rc;
     return gage_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, outlet_x, outlet_y, ids, n_outlets, d_gw, placed, iddown, stats);
 }
 extern "C" int tdx_gagewatershed_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const int32_t* outlet_x,
                                        const int32_t* outlet_row, const int32_t* ids, int64_t n_outlets, int32_t* d_gw, int32_t* placed, int32_t* iddown,
                                        tdx_stats* stats) {
-    if (!ctx || !d_p || !d_gw || nx <= 0 || ny_local <= 0 || n_outlets < 0 || n_outlets > 0x7ffffffe ||
-        (n_outlets > 0 && (!outlet_x || !outlet_row || !placed || !iddown)))
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gagewatershed_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = gage_check(ctx, d_p, d_gw, nx, ny_local, 2, outlet_x, outlet_row, n_outlets, placed, iddown, "tdx_gagewatershed_strip: bad argument")) return rc;
     return gage_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, outlet_x, outlet_row, ids, n_outlets, d_gw, placed, iddown, stats);
 }
 extern "C" int tdx_gagewatershed(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const int32_t* outlet_x, const int32_t* outlet_y,
                                  const int32_t* ids, int64_t n_outlets, int32_t* gw, int32_t* placed, int32_t* iddown, tdx_stats* stats) {
     if (!ctx || !p || !gw || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gagewatershed: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    int32_t* d_o = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    if (!d_p || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_gagewatershed_dev(ctx, d_p, nx, ny, p_nodata, outlet_x, outlet_y, ids, n_outlets, d_o, placed, iddown, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(gw, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    int32_t* d_o = h.out(TDX_S_IO1, gw);
+    if (h.error) return h.error;
+    return h.finish(tdx_gagewatershed_dev(ctx, d_p, nx, ny, p_nodata, outlet_x, outlet_y, ids, n_outlets, d_o, placed, iddown, stats));
 }

@@ -338,35 +338,33 @@ int aval_impl(tdx_context* ctx, const Strip& st, const AvalArgs& a, int path, td
 
 }  // namespace
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int retlim_check(tdx_context* ctx, const void* ang, const void* wg, const void* rc_in, const void* qrl, const void* dxc, const void* dyc, int64_t nx, int64_t ny,
+                        int64_t halo, const char* who) {
+    if (!ctx || !ang || !wg || !rc_in || !qrl || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_retlimflow_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                   const float* d_wg, float wg_nodata, const float* d_rc, float rc_nodata, float* d_qrl, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_wg || !d_rc || !d_qrl || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_retlimflow_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = retlim_check(ctx, d_ang, d_wg, d_rc, d_qrl, dxc, dyc, nx, ny, 0, "tdx_retlimflow_dev: bad argument")) return rc;
     return retlim_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, d_wg, wg_nodata, d_rc, rc_nodata, d_qrl, stats);
 }
 extern "C" int tdx_retlimflow_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata, const double* dxc,
                                     const double* dyc, const float* d_wg, float wg_nodata, const float* d_rc, float rc_nodata, float* d_qrl, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_wg || !d_rc || !d_qrl || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_retlimflow_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = retlim_check(ctx, d_ang, d_wg, d_rc, d_qrl, dxc, dyc, nx, ny_local, 2, "tdx_retlimflow_strip: bad argument")) return rc;
     return retlim_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, d_wg, wg_nodata, d_rc, rc_nodata, d_qrl, stats);
 }
 extern "C" int tdx_retlimflow(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc, const float* wg,
                               float wg_nodata, const float* rc_in, float rc_nodata, float* qrl, tdx_stats* stats) {
     if (!ctx || !ang || !wg || !rc_in || !qrl || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_retlimflow: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_w = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_r = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO4, n * 4));
-    if (!d_a || !d_w || !d_r || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, wg, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_r, rc_in, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_retlimflow_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, wg_nodata, d_r, rc_nodata, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(qrl, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_w = h.in(TDX_S_IO1, wg);
+    float* d_r = h.in(TDX_S_IO2, rc_in);
+    float* d_o = h.out(TDX_S_IO4, qrl);
+    if (h.error) return h.error;
+    return h.finish(tdx_retlimflow_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, wg_nodata, d_r, rc_nodata, d_o, stats));
 }
 
 extern "C" int tdx_dinfavalanche_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
@@ -390,20 +388,12 @@ extern "C" int tdx_dinfavalanche(tdx_context* ctx, const float* ang, int64_t nx,
                                  float fel_nodata, const int16_t* ass, int16_t ass_nodata, float thresh, float alpha, int path, const double* geo, int geographic,
                                  float* rz, float* dfs, tdx_stats* stats) {
     if (!ctx || !ang || !fel || !ass || !rz || !dfs || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfavalanche: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_f = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    int16_t* d_s = static_cast<int16_t*>(ctx->scratch(TDX_S_IO2, n * 2));
-    float* d_r = static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4));
-    float* d_d = static_cast<float*>(ctx->scratch(TDX_S_IO4, n * 4));
-    if (!d_a || !d_f || !d_s || !d_r || !d_d) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_f, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, ass, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinfavalanche_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_f, fel_nodata, d_s, ass_nodata, thresh, alpha, path, geo, geographic, d_r, d_d, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(rz, d_r, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dfs, d_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_f = h.in(TDX_S_IO1, fel);
+    int16_t* d_s = h.in(TDX_S_IO2, ass);
+    float* d_r = h.out(TDX_S_IO3, rz);
+    float* d_d = h.out(TDX_S_IO4, dfs);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfavalanche_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_f, fel_nodata, d_s, ass_nodata, thresh, alpha, path, geo, geographic, d_r, d_d, stats));
 }

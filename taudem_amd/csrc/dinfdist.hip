@@ -336,12 +336,18 @@ bool bad_mode(int stat, int kind) { return stat < 0 || stat > 2 || kind < 0 || k
 
 }  // namespace
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int distdown_check(tdx_context* ctx, const void* ang, const void* fel, const void* src, const void* dd, const void* dxc, const void* dyc, int64_t nx, int64_t ny,
+                          int64_t halo, int statmethod, int typemethod, const char* who) {
+    if (!ctx || !ang || !src || !dd || !dxc || !dyc || nx <= 0 || ny <= 0 || bad_mode(statmethod, typemethod) || (typemethod != KIND_H && !fel))
+        return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_dinfdistdown_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                     const float* d_fel, float fel_nodata, const int16_t* d_src, const float* d_w, float w_nodata, int statmethod, int typemethod,
                                     int contcheck, float* d_dd, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_src || !d_dd || !dxc || !dyc || nx <= 0 || ny <= 0 || bad_mode(statmethod, typemethod) || (typemethod != KIND_H && !d_fel))
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdistdown_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = distdown_check(ctx, d_ang, d_fel, d_src, d_dd, dxc, dyc, nx, ny, 0, statmethod, typemethod, "tdx_dinfdistdown_dev: bad argument")) return rc;
     const DdArgs a{const_cast<float*>(d_ang), ang_nodata, dxc, dyc, const_cast<float*>(d_fel), fel_nodata, d_src, const_cast<float*>(d_w), w_nodata,
                    statmethod, typemethod, contcheck, d_dd};
     return distdown_impl(ctx, strip_single(int(nx), int(ny)), a, stats);
@@ -349,9 +355,7 @@ extern "C" int tdx_dinfdistdown_dev(tdx_context* ctx, const float* d_ang, int64_
 extern "C" int tdx_dinfdistdown_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata, const double* dxc,
                                       const double* dyc, float* d_fel, float fel_nodata, const int16_t* d_src, float* d_w, float w_nodata, int statmethod,
                                       int typemethod, int contcheck, float* d_dd, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_src || !d_dd || !dxc || !dyc || nx <= 0 || ny_local <= 0 || bad_mode(statmethod, typemethod) || (typemethod != KIND_H && !d_fel))
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdistdown_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = distdown_check(ctx, d_ang, d_fel, d_src, d_dd, dxc, dyc, nx, ny_local, 2, statmethod, typemethod, "tdx_dinfdistdown_strip: bad argument")) return rc;
     const DdArgs a{d_ang, ang_nodata, dxc, dyc, d_fel, fel_nodata, d_src, d_w, w_nodata, statmethod, typemethod, contcheck, d_dd};
     return distdown_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), a, stats);
 }
@@ -360,21 +364,12 @@ extern "C" int tdx_dinfdistdown(tdx_context* ctx, const float* ang, int64_t nx, 
                                 tdx_stats* stats) {
     if (!ctx || !ang || !src || !dd || nx <= 0 || ny <= 0 || bad_mode(statmethod, typemethod) || (typemethod != KIND_H && !fel))
         return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfdistdown: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    const bool use_fel = typemethod != KIND_H, use_w = w != nullptr && typemethod != KIND_V;
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_f = use_fel ? static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4)) : nullptr;
-    float* d_w = use_w ? static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4)) : nullptr;
-    int16_t* d_s = static_cast<int16_t*>(ctx->scratch(TDX_S_IO3, n * 2));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO4, n * 4));
-    if (!d_a || (use_fel && !d_f) || (use_w && !d_w) || !d_s || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (use_fel) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_f, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (use_w) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, w, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, src, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinfdistdown_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_f, fel_nodata, d_s, d_w, w_nodata, statmethod, typemethod, contcheck, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dd, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_f = h.in(TDX_S_IO1, typemethod != KIND_H ? fel : nullptr);   // the horizontal distance reads no elevations,
+    float* d_w = h.in(TDX_S_IO2, typemethod != KIND_V ? w : nullptr);     // the vertical one no weights (optional anyway)
+    int16_t* d_s = h.in(TDX_S_IO3, src);
+    float* d_o = h.out(TDX_S_IO4, dd);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfdistdown_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_f, fel_nodata, d_s, d_w, w_nodata, statmethod, typemethod, contcheck, d_o, stats));
 }

@@ -481,35 +481,32 @@ static int dinfflowdir_impl(tdx_context* ctx, const Strip& st, float* d_fel, flo
     return rc;
 }
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int dinfflowdir_check(tdx_context* ctx, const void* fel, const void* ang, const void* slp, const void* dxc, const void* dyc, int64_t nx, int64_t ny,
+                             int64_t halo, const char* who) {
+    if (!ctx || !fel || !ang || !slp || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_dinfflowdir_dev(tdx_context* ctx, const float* d_fel, int64_t nx, int64_t ny, float fel_nodata,
                                    const double* dxc, const double* dyc, float* d_ang, float* d_slp, tdx_stats* stats) {
-    if (!ctx || !d_fel || !d_ang || !d_slp || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfflowdir_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = dinfflowdir_check(ctx, d_fel, d_ang, d_slp, dxc, dyc, nx, ny, 0, "tdx_dinfflowdir_dev: bad argument")) return rc;
     return dinfflowdir_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_fel), fel_nodata, dxc, dyc, d_ang, d_slp, stats);
 }
 
 extern "C" int tdx_dinfflowdir_strip(tdx_context* ctx, const tdx_comm* comm, float* d_fel, int64_t nx, int64_t ny_local, float fel_nodata,
                                      const double* dxc, const double* dyc, float* d_ang, float* d_slp, tdx_stats* stats) {
-    if (!ctx || !d_fel || !d_ang || !d_slp || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfflowdir_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = dinfflowdir_check(ctx, d_fel, d_ang, d_slp, dxc, dyc, nx, ny_local, 2, "tdx_dinfflowdir_strip: bad argument")) return rc;
     return dinfflowdir_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_fel, fel_nodata, dxc, dyc, d_ang, d_slp, stats);
 }
 
 extern "C" int tdx_dinfflowdir(tdx_context* ctx, const float* fel, int64_t nx, int64_t ny, float fel_nodata,
                                const double* dxc, const double* dyc, float* ang, float* slp, tdx_stats* stats) {
     if (!ctx || !fel || !ang || !slp || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfflowdir: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_z = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_s = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_z || !d_a || !d_s) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_z, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_dinfflowdir_dev(ctx, d_z, nx, ny, fel_nodata, dxc, dyc, d_a, d_s, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ang, d_a, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(slp, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_z = h.in(TDX_S_IO0, fel);
+    float* d_a = h.out(TDX_S_IO1, ang);
+    float* d_s = h.out(TDX_S_IO2, slp);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfflowdir_dev(ctx, d_z, nx, ny, fel_nodata, dxc, dyc, d_a, d_s, stats));
 }

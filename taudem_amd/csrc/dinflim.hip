@@ -215,20 +215,29 @@ int translim_impl(tdx_context* ctx, const Strip& st, float* d_ang, float ang_nod
 
 }  // namespace
 
+// the argument tests of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int conclim_check(tdx_context* ctx, const void* ang, const void* dm, const void* dg, const void* q, const void* ctpt, const void* dxc, const void* dyc, int64_t nx,
+                         int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !ang || !dm || !dg || !q || !ctpt || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+static int translim_check(tdx_context* ctx, const void* ang, const void* tsup, const void* tc, const void* tla, const void* tdep, const void* dxc, const void* dyc,
+                          int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !ang || !tsup || !tc || !tla || !tdep || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_dinfconclimaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                         const float* d_dm, float dm_nodata, const int16_t* d_dg, const float* d_q, float q_nodata, float csol, int contcheck,
                                         const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_ctpt, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dm || !d_dg || !d_q || !d_ctpt || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfconclimaccum_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = conclim_check(ctx, d_ang, d_dm, d_dg, d_q, d_ctpt, dxc, dyc, nx, ny, 0, "tdx_dinfconclimaccum_dev: bad argument")) return rc;
     return conclim_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, d_dm, dm_nodata, d_dg, d_q, q_nodata, csol, contcheck,
                         outlet_x, outlet_y, n_outlets, d_ctpt, stats);
 }
 extern "C" int tdx_dinfconclimaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata, const double* dxc,
                                           const double* dyc, const float* d_dm, float dm_nodata, const int16_t* d_dg, const float* d_q, float q_nodata, float csol,
                                           int contcheck, const int32_t* outlet_x, const int32_t* outlet_row, int64_t n_outlets, float* d_ctpt, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dm || !d_dg || !d_q || !d_ctpt || !dxc || !dyc || nx <= 0 || ny_local <= 0)
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfconclimaccum_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = conclim_check(ctx, d_ang, d_dm, d_dg, d_q, d_ctpt, dxc, dyc, nx, ny_local, 2, "tdx_dinfconclimaccum_strip: bad argument")) return rc;
     return conclim_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, d_dm, dm_nodata, d_dg, d_q, q_nodata, csol, contcheck, outlet_x,
                         outlet_row, n_outlets, d_ctpt, stats);
 }
@@ -236,32 +245,22 @@ extern "C" int tdx_dinfconclimaccum(tdx_context* ctx, const float* ang, int64_t 
                                     float dm_nodata, const int16_t* dg, const float* q, float q_nodata, float csol, int contcheck, const int32_t* outlet_x,
                                     const int32_t* outlet_y, int64_t n_outlets, float* ctpt, tdx_stats* stats) {
     if (!ctx || !ang || !dm || !dg || !q || !ctpt || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfconclimaccum: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_m = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_q = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    int16_t* d_g = static_cast<int16_t*>(ctx->scratch(TDX_S_IO3, n * 2));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO4, n * 4));
-    if (!d_a || !d_m || !d_q || !d_g || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_m, dm, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_q, q, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_g, dg, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinfconclimaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_m, dm_nodata, d_g, d_q, q_nodata, csol, contcheck, outlet_x, outlet_y, n_outlets, d_o,
-                                            stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctpt, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_m = h.in(TDX_S_IO1, dm);
+    float* d_q = h.in(TDX_S_IO2, q);
+    int16_t* d_g = h.in(TDX_S_IO3, dg);
+    float* d_o = h.out(TDX_S_IO4, ctpt);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfconclimaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_m, dm_nodata, d_g, d_q, q_nodata, csol, contcheck, outlet_x, outlet_y, n_outlets,
+                                             d_o, stats));
 }
 
 extern "C" int tdx_dinftranslimaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                          const float* d_tsup, float tsup_nodata, const float* d_tc, float tc_nodata, const float* d_cs, float cs_nodata, int contcheck,
                                          const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_tla, float* d_tdep, float* d_ctpt,
                                          tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_tsup || !d_tc || !d_tla || !d_tdep || !dxc || !dyc || nx <= 0 || ny <= 0)
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinftranslimaccum_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = translim_check(ctx, d_ang, d_tsup, d_tc, d_tla, d_tdep, dxc, dyc, nx, ny, 0, "tdx_dinftranslimaccum_dev: bad argument")) return rc;
     return translim_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, d_tsup, tsup_nodata, d_tc, tc_nodata, d_cs, cs_nodata,
                          contcheck, outlet_x, outlet_y, n_outlets, d_tla, d_tdep, d_ctpt, stats);
 }
@@ -269,9 +268,7 @@ extern "C" int tdx_dinftranslimaccum_strip(tdx_context* ctx, const tdx_comm* com
                                            const double* dyc, const float* d_tsup, float tsup_nodata, const float* d_tc, float tc_nodata, const float* d_cs,
                                            float cs_nodata, int contcheck, const int32_t* outlet_x, const int32_t* outlet_row, int64_t n_outlets, float* d_tla,
                                            float* d_tdep, float* d_ctpt, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_tsup || !d_tc || !d_tla || !d_tdep || !dxc || !dyc || nx <= 0 || ny_local <= 0)
-        return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinftranslimaccum_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = translim_check(ctx, d_ang, d_tsup, d_tc, d_tla, d_tdep, dxc, dyc, nx, ny_local, 2, "tdx_dinftranslimaccum_strip: bad argument")) return rc;
     return translim_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, d_tsup, tsup_nodata, d_tc, tc_nodata, d_cs, cs_nodata, contcheck,
                          outlet_x, outlet_row, n_outlets, d_tla, d_tdep, d_ctpt, stats);
 }
@@ -280,25 +277,15 @@ extern "C" int tdx_dinftranslimaccum(tdx_context* ctx, const float* ang, int64_t
                                      const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* tla, float* tdep, float* ctpt, tdx_stats* stats) {
     if (!ctx || !ang || !tsup || !tc || !tla || !tdep || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinftranslimaccum: bad argument");
     if ((cs == nullptr) != (ctpt == nullptr)) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinftranslimaccum: the concentration input and output go together");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_s = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_c = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    float* d_t = static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4));
-    float* d_d = static_cast<float*>(ctx->scratch(TDX_S_IO4, n * 4));
-    float* d_ci = cs ? static_cast<float*>(ctx->scratch(TDX_S_E, n * 4)) : nullptr;
-    float* d_co = cs ? static_cast<float*>(ctx->scratch(TDX_S_F, n * 4)) : nullptr;
-    if (!d_a || !d_s || !d_c || !d_t || !d_d || (cs && (!d_ci || !d_co))) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, tsup, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_c, tc, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (cs) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_ci, cs, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinftranslimaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_s, tsup_nodata, d_c, tc_nodata, d_ci, cs_nodata, contcheck, outlet_x, outlet_y,
-                                             n_outlets, d_t, d_d, d_co, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(tla, d_t, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(tdep, d_d, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (cs) TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctpt, d_co, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_s = h.in(TDX_S_IO1, tsup);
+    float* d_c = h.in(TDX_S_IO2, tc);
+    float* d_t = h.out(TDX_S_IO3, tla);
+    float* d_d = h.out(TDX_S_IO4, tdep);
+    float* d_ci = h.in(TDX_S_E, cs);      // optional, with ctpt
+    float* d_co = h.out(TDX_S_F, ctpt);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinftranslimaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_s, tsup_nodata, d_c, tc_nodata, d_ci, cs_nodata, contcheck, outlet_x, outlet_y,
+                                              n_outlets, d_t, d_d, d_co, stats));
 }

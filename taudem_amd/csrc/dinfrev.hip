@@ -190,62 +190,57 @@ int revacc_impl(tdx_context* ctx, const Strip& st, float* d_ang, float ang_nodat
 
 }  // namespace
 
+// the argument tests of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int updep_check(tdx_context* ctx, const void* ang, const void* dg, const void* dep, const void* dxc, const void* dyc, int64_t nx, int64_t ny, int64_t halo,
+                       const char* who) {
+    if (!ctx || !ang || !dg || !dep || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+static int revacc_check(tdx_context* ctx, const void* ang, const void* w, const void* racc, const void* dmax, const void* dxc, const void* dyc, int64_t nx, int64_t ny,
+                        int64_t halo, const char* who) {
+    if (!ctx || !ang || !w || !racc || !dmax || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_dinfupdependence_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                         const int32_t* d_dg, float* d_dep, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dg || !d_dep || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfupdependence_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = updep_check(ctx, d_ang, d_dg, d_dep, dxc, dyc, nx, ny, 0, "tdx_dinfupdependence_dev: bad argument")) return rc;
     return updep_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, const_cast<int32_t*>(d_dg), d_dep, stats);
 }
 extern "C" int tdx_dinfupdependence_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata, const double* dxc,
                                           const double* dyc, int32_t* d_dg, float* d_dep, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_dg || !d_dep || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfupdependence_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = updep_check(ctx, d_ang, d_dg, d_dep, dxc, dyc, nx, ny_local, 2, "tdx_dinfupdependence_strip: bad argument")) return rc;
     return updep_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, d_dg, d_dep, stats);
 }
 extern "C" int tdx_dinfupdependence(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                     const int32_t* dg, float* dep, tdx_stats* stats) {
     if (!ctx || !ang || !dg || !dep || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfupdependence: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    int32_t* d_g = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_a || !d_g || !d_o) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_g, dg, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinfupdependence_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_g, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dep, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    int32_t* d_g = h.in(TDX_S_IO1, dg);
+    float* d_o = h.out(TDX_S_IO2, dep);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfupdependence_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_g, d_o, stats));
 }
 
 extern "C" int tdx_dinfrevaccum_dev(tdx_context* ctx, const float* d_ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc,
                                     const float* d_w, float w_nodata, float* d_racc, float* d_dmax, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_w || !d_racc || !d_dmax || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfrevaccum_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = revacc_check(ctx, d_ang, d_w, d_racc, d_dmax, dxc, dyc, nx, ny, 0, "tdx_dinfrevaccum_dev: bad argument")) return rc;
     return revacc_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_ang), ang_nodata, dxc, dyc, const_cast<float*>(d_w), w_nodata, d_racc, d_dmax, stats);
 }
 extern "C" int tdx_dinfrevaccum_strip(tdx_context* ctx, const tdx_comm* comm, float* d_ang, int64_t nx, int64_t ny_local, float ang_nodata, const double* dxc,
                                       const double* dyc, float* d_w, float w_nodata, float* d_racc, float* d_dmax, tdx_stats* stats) {
-    if (!ctx || !d_ang || !d_w || !d_racc || !d_dmax || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfrevaccum_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = revacc_check(ctx, d_ang, d_w, d_racc, d_dmax, dxc, dyc, nx, ny_local, 2, "tdx_dinfrevaccum_strip: bad argument")) return rc;
     return revacc_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_ang, ang_nodata, dxc, dyc, d_w, w_nodata, d_racc, d_dmax, stats);
 }
 extern "C" int tdx_dinfrevaccum(tdx_context* ctx, const float* ang, int64_t nx, int64_t ny, float ang_nodata, const double* dxc, const double* dyc, const float* w,
                                 float w_nodata, float* racc, float* dmax, tdx_stats* stats) {
     if (!ctx || !ang || !w || !racc || !dmax || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_dinfrevaccum: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_w = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_r = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    float* d_m = static_cast<float*>(ctx->scratch(TDX_S_IO3, n * 4));
-    if (!d_a || !d_w || !d_r || !d_m) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ang, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_w, w, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_dinfrevaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, w_nodata, d_r, d_m, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(racc, d_r, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(dmax, d_m, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ang);
+    float* d_w = h.in(TDX_S_IO1, w);
+    float* d_r = h.out(TDX_S_IO2, racc);
+    float* d_m = h.out(TDX_S_IO3, dmax);
+    if (h.error) return h.error;
+    return h.finish(tdx_dinfrevaccum_dev(ctx, d_a, nx, ny, ang_nodata, dxc, dyc, d_w, w_nodata, d_r, d_m, stats));
 }

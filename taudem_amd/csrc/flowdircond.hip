@@ -94,31 +94,29 @@ int fdc_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
 
 }  // namespace
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int fdc_check(tdx_context* ctx, const void* p, const void* z, const void* zfdc, int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !p || !z || !zfdc || z == zfdc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_flowdircond_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_z, float z_nodata, float* d_zfdc,
                                    tdx_stats* stats) {
-    if (!ctx || !d_p || !d_z || !d_zfdc || d_z == d_zfdc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_flowdircond_dev: bad argument");
-    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = fdc_check(ctx, d_p, d_z, d_zfdc, nx, ny, 0, "tdx_flowdircond_dev: bad argument")) return rc;
     return fdc_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, d_z, z_nodata, d_zfdc, stats);
 }
 extern "C" int tdx_flowdircond_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const float* d_z,
                                      float z_nodata, float* d_zfdc, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_z || !d_zfdc || d_z == d_zfdc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_flowdircond_strip: bad argument");
-    if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = fdc_check(ctx, d_p, d_z, d_zfdc, nx, ny_local, 2, "tdx_flowdircond_strip: bad argument")) return rc;
     return fdc_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_z, z_nodata, d_zfdc, stats);
 }
 extern "C" int tdx_flowdircond(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* z, float z_nodata, float* zfdc,
                                tdx_stats* stats) {
     if (!ctx || !p || !z || !zfdc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_flowdircond: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_z = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_p || !d_o || !d_z) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_z, z, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_flowdircond_dev(ctx, d_p, nx, ny, p_nodata, d_z, z_nodata, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(zfdc, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    float* d_o = h.out(TDX_S_IO1, zfdc);
+    float* d_z = h.in(TDX_S_IO2, z);
+    if (h.error) return h.error;
+    return h.finish(tdx_flowdircond_dev(ctx, d_p, nx, ny, p_nodata, d_z, z_nodata, d_o, stats));
 }

@@ -324,13 +324,19 @@ int gridnet_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_noda
 }
 }  // namespace
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int gridnet_check(tdx_context* ctx, const void* p, const void* dxc, const void* dyc, const void* plen, const void* tlen, const void* gord, int64_t nx, int64_t ny,
+                         int64_t halo, const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, const char* who) {
+    if (!ctx || !p || !dxc || !dyc || !plen || !tlen || !gord || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    if (too_big(nx, ny + halo)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (n_outlets > 0 && (!outlet_x || !outlet_y)) return tdx_fail(ctx, TDX_ERR_ARG, "outlets missing");
+    return TDX_OK;
+}
+
 extern "C" int tdx_gridnet_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const double* dxc, const double* dyc,
                                const int32_t* d_mask, int32_t thresh, const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* d_plen,
                                float* d_tlen, int16_t* d_gord, tdx_stats* stats) {
-    if (!ctx || !d_p || !dxc || !dyc || !d_plen || !d_tlen || !d_gord || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gridnet_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells");
-    if (n_outlets > 0 && (!outlet_x || !outlet_y)) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gridnet_dev: outlets missing");
+    if (int rc = gridnet_check(ctx, d_p, dxc, dyc, d_plen, d_tlen, d_gord, nx, ny, 0, outlet_x, outlet_y, n_outlets, "tdx_gridnet_dev: bad argument")) return rc;
     return gridnet_impl(ctx, strip_single(int(nx), int(ny)), const_cast<int16_t*>(d_p), p_nodata, dxc, dyc, d_mask, thresh, outlet_x, outlet_y, n_outlets, d_plen,
                         d_tlen, d_gord, stats);
 }
@@ -338,10 +344,7 @@ extern "C" int tdx_gridnet_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx,
 extern "C" int tdx_gridnet_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const double* dxc,
                                  const double* dyc, int32_t* d_mask, int32_t thresh, const int32_t* outlet_x, const int32_t* outlet_row, int64_t n_outlets,
                                  float* d_plen, float* d_tlen, int16_t* d_gord, tdx_stats* stats) {
-    if (!ctx || !d_p || !dxc || !dyc || !d_plen || !d_tlen || !d_gord || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gridnet_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
-    if (n_outlets > 0 && (!outlet_x || !outlet_row)) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gridnet_strip: outlets missing");
+    if (int rc = gridnet_check(ctx, d_p, dxc, dyc, d_plen, d_tlen, d_gord, nx, ny_local, 2, outlet_x, outlet_row, n_outlets, "tdx_gridnet_strip: bad argument")) return rc;
     return gridnet_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, dxc, dyc, d_mask, thresh, outlet_x, outlet_row, n_outlets, d_plen, d_tlen,
                         d_gord, stats);
 }
@@ -350,22 +353,14 @@ extern "C" int tdx_gridnet(tdx_context* ctx, const int16_t* p, int64_t nx, int64
                            const int32_t* mask, int32_t thresh, const int32_t* outlet_x, const int32_t* outlet_y, int64_t n_outlets, float* plen, float* tlen,
                            int16_t* gord, tdx_stats* stats) {
     if (!ctx || !p || !plen || !tlen || !gord || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_gridnet: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    float* d_pl = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_tl = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    int16_t* d_go = static_cast<int16_t*>(ctx->scratch(TDX_S_IO3, n * 2));
-    int32_t* d_m = mask ? static_cast<int32_t*>(ctx->scratch(TDX_S_IO4, n * 4)) : nullptr;
-    if (!d_p || !d_pl || !d_tl || !d_go || (mask && !d_m)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_m, mask, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_gridnet_dev(ctx, d_p, nx, ny, p_nodata, dxc, dyc, d_m, thresh, outlet_x, outlet_y, n_outlets, d_pl, d_tl, d_go, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(plen, d_pl, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(tlen, d_tl, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(gord, d_go, n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    float* d_pl = h.out(TDX_S_IO1, plen);
+    float* d_tl = h.out(TDX_S_IO2, tlen);
+    int16_t* d_go = h.out(TDX_S_IO3, gord);
+    int32_t* d_m = h.in(TDX_S_IO4, mask);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_gridnet_dev(ctx, d_p, nx, ny, p_nodata, dxc, dyc, d_m, thresh, outlet_x, outlet_y, n_outlets, d_pl, d_tl, d_go, stats));
 }
 
 extern "C" int tdx_threshold_dev(tdx_context* ctx, const float* d_ssa, int64_t nx, int64_t ny, float ssa_nodata, const float* d_mask, float thresh,
@@ -387,16 +382,10 @@ extern "C" int tdx_threshold_dev(tdx_context* ctx, const float* d_ssa, int64_t n
 extern "C" int tdx_threshold(tdx_context* ctx, const float* ssa, int64_t nx, int64_t ny, float ssa_nodata, const float* mask, float thresh, int16_t* src,
                              tdx_stats* stats) {
     if (!ctx || !ssa || !src || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_threshold: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_a = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_m = mask ? static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4)) : nullptr;
-    int16_t* d_s = static_cast<int16_t*>(ctx->scratch(TDX_S_IO2, n * 2));
-    if (!d_a || !d_s || (mask && !d_m)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_a, ssa, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_m, mask, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_threshold_dev(ctx, d_a, nx, ny, ssa_nodata, d_m, thresh, d_s, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(src, d_s, n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_a = h.in(TDX_S_IO0, ssa);
+    float* d_m = h.in(TDX_S_IO1, mask);   // optional
+    int16_t* d_s = h.out(TDX_S_IO2, src);
+    if (h.error) return h.error;
+    return h.finish(tdx_threshold_dev(ctx, d_a, nx, ny, ssa_nodata, d_m, thresh, d_s, stats));
 }

@@ -447,16 +447,13 @@ extern "C" int tdx_catchhydrogeo(tdx_context* ctx, const float* hand, const int3
                                  float slp_nodata, const double* dxc, const double* dyc, const int32_t* ids, int64_t ncatch, const double* stages, int64_t nheight, int32_t* count,
                                  double* surface, double* bed, double* volume, double* catcharea, tdx_stats* stats) {
     if (!ctx || !hand || !catchr || !slp || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_catchhydrogeo: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_h = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    int32_t* d_c = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_s = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_h || !d_c || !d_s) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_h, hand, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_c, catchr, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_s, slp, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    return tdx_catchhydrogeo_dev(ctx, d_h, d_c, d_s, nx, ny, hand_nodata, catch_nodata, slp_nodata, dxc, dyc, ids, ncatch, stages, nheight, count, surface, bed, volume, catcharea,
-                                 stats);
+    HostCall h(ctx, nx, ny);   // no raster comes back: the tables are host arrays, written by the _dev form
+    float* d_h = h.in(TDX_S_IO0, hand);
+    int32_t* d_c = h.in(TDX_S_IO1, catchr);
+    float* d_s = h.in(TDX_S_IO2, slp);
+    if (h.error) return h.error;
+    return h.finish(tdx_catchhydrogeo_dev(ctx, d_h, d_c, d_s, nx, ny, hand_nodata, catch_nodata, slp_nodata, dxc, dyc, ids, ncatch, stages, nheight, count, surface, bed, volume,
+                                          catcharea, stats));
 }
 
 extern "C" int tdx_inundepth_strip(tdx_context* ctx, const tdx_comm* comm, const float* d_hand, const int32_t* d_catch, const int16_t* d_mask, int64_t nx, int64_t ny_local,
@@ -485,18 +482,11 @@ extern "C" int tdx_inundepth(tdx_context* ctx, const float* hand, const int32_t*
                              int16_t mask_nodata, const double* dxc, const double* dyc, const int32_t* ids, const float* depth, int64_t nfc, float* map, float* area,
                              tdx_stats* stats) {
     if (!ctx || !hand || !catchr || !map || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_inundepth: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_h = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    int32_t* d_c = static_cast<int32_t*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    int16_t* d_m = mask ? static_cast<int16_t*>(ctx->scratch(TDX_S_IO3, n * 2)) : nullptr;
-    if (!d_h || !d_c || !d_o || (mask && !d_m)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_h, hand, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_c, catchr, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_m, mask, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_inundepth_dev(ctx, d_h, d_c, d_m, nx, ny, hand_nodata, catch_nodata, mask_nodata, dxc, dyc, ids, depth, nfc, d_o, area, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(map, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_h = h.in(TDX_S_IO0, hand);
+    int32_t* d_c = h.in(TDX_S_IO1, catchr);
+    float* d_o = h.out(TDX_S_IO2, map);
+    int16_t* d_m = h.in(TDX_S_IO3, mask);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_inundepth_dev(ctx, d_h, d_c, d_m, nx, ny, hand_nodata, catch_nodata, mask_nodata, dxc, dyc, ids, depth, nfc, d_o, area, stats));
 }

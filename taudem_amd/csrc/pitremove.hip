@@ -468,35 +468,31 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
     return TDX_OK;
 }
 
+// the argument test of the _dev (halo 0) and _strip (halo 2: the strip's two halo rows) entry points
+static int pitremove_check(tdx_context* ctx, const void* dem, const void* fel, int64_t nx, int64_t ny, int64_t halo, const char* who) {
+    if (!ctx || !dem || !fel || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return too_big(nx, ny + halo) ? tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip") : TDX_OK;
+}
+
 extern "C" int tdx_pitremove_dev(tdx_context* ctx, const float* d_dem, int64_t nx, int64_t ny, float dem_nodata,
                                  const int16_t* d_mask, int fourway, float* d_fel, tdx_stats* stats) {
-    if (!ctx || !d_dem || !d_fel || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_pitremove_dev: bad argument");
-    if (nx > 0x7fffffff || ny > 0x7fffffff || uint64_t(nx) * uint64_t(ny) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = pitremove_check(ctx, d_dem, d_fel, nx, ny, 0, "tdx_pitremove_dev: bad argument")) return rc;
     return pitremove_impl(ctx, strip_single(int(nx), int(ny)), const_cast<float*>(d_dem), d_mask, fourway, dem_nodata, d_fel, stats);
 }
 
 extern "C" int tdx_pitremove_strip(tdx_context* ctx, const tdx_comm* comm, float* d_dem, int64_t nx, int64_t ny_local, float dem_nodata,
                                    const int16_t* d_mask, int fourway, float* d_fel, tdx_stats* stats) {
-    if (!ctx || !d_dem || !d_fel || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_pitremove_strip: bad argument");
-    if (nx > 0x7fffffff || ny_local > 0x7ffffff0 || uint64_t(nx) * uint64_t(ny_local + 2) > 0xffffffffull)
-        return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    if (int rc = pitremove_check(ctx, d_dem, d_fel, nx, ny_local, 2, "tdx_pitremove_strip: bad argument")) return rc;
     return pitremove_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_dem, d_mask, fourway, dem_nodata, d_fel, stats);
 }
 
 extern "C" int tdx_pitremove(tdx_context* ctx, const float* dem, int64_t nx, int64_t ny, float dem_nodata,
                              const int16_t* mask, int fourway, float* fel, tdx_stats* stats) {
     if (!ctx || !dem || !fel || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_pitremove: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    float* d_z = static_cast<float*>(ctx->scratch(TDX_S_IO0, n * 4));
-    float* d_w = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    int16_t* d_m = mask ? static_cast<int16_t*>(ctx->scratch(TDX_S_IO2, n * 2)) : nullptr;
-    if (!d_z || !d_w || (mask && !d_m)) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_z, dem, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_m, mask, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    int rc = tdx_pitremove_dev(ctx, d_z, nx, ny, dem_nodata, d_m, fourway, d_w, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(fel, d_w, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    float* d_z = h.in(TDX_S_IO0, dem);
+    float* d_w = h.out(TDX_S_IO1, fel);
+    int16_t* d_m = h.in(TDX_S_IO2, mask);   // optional
+    if (h.error) return h.error;
+    return h.finish(tdx_pitremove_dev(ctx, d_z, nx, ny, dem_nodata, d_m, fourway, d_w, stats));
 }

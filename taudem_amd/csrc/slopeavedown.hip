@@ -157,10 +157,15 @@ extern "C" int64_t tdx_slopeavedown_niter(double dn, const double* dxc, const do
     return int64_t(q);
 }
 
+// the argument test of the _dev and _strip entry points, up to where the two part: a strip cannot derive niter
+static int sad_check(tdx_context* ctx, const void* p, const void* fel, const void* slpd, const void* dxc, const void* dyc, int64_t nx, int64_t ny, double dn, const char* who) {
+    if (!ctx || !p || !fel || !slpd || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, who);
+    return bad_dn(dn) ? tdx_fail(ctx, TDX_ERR_ARG, "slopeavedown: dn must be finite and not negative") : TDX_OK;
+}
+
 extern "C" int tdx_slopeavedown_dev(tdx_context* ctx, const int16_t* d_p, int64_t nx, int64_t ny, int16_t p_nodata, const float* d_fel, float fel_nodata,
                                     const double* dxc, const double* dyc, double dn, int64_t niter, float* d_slpd, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_fel || !d_slpd || !dxc || !dyc || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_slopeavedown_dev: bad argument");
-    if (bad_dn(dn)) return tdx_fail(ctx, TDX_ERR_ARG, "slopeavedown: dn must be finite and not negative");
+    if (int rc = sad_check(ctx, d_p, d_fel, d_slpd, dxc, dyc, nx, ny, dn, "tdx_slopeavedown_dev: bad argument")) return rc;
     if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
     if (niter <= 0) niter = tdx_slopeavedown_niter(dn, dxc, dyc, ny);
     if (niter <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "slopeavedown: the cell sizes give no iteration count");
@@ -168,8 +173,7 @@ extern "C" int tdx_slopeavedown_dev(tdx_context* ctx, const int16_t* d_p, int64_
 }
 extern "C" int tdx_slopeavedown_strip(tdx_context* ctx, const tdx_comm* comm, int16_t* d_p, int64_t nx, int64_t ny_local, int16_t p_nodata, const float* d_fel,
                                       float fel_nodata, const double* dxc, const double* dyc, double dn, int64_t niter, float* d_slpd, tdx_stats* stats) {
-    if (!ctx || !d_p || !d_fel || !d_slpd || !dxc || !dyc || nx <= 0 || ny_local <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_slopeavedown_strip: bad argument");
-    if (bad_dn(dn)) return tdx_fail(ctx, TDX_ERR_ARG, "slopeavedown: dn must be finite and not negative");
+    if (int rc = sad_check(ctx, d_p, d_fel, d_slpd, dxc, dyc, nx, ny_local, dn, "tdx_slopeavedown_strip: bad argument")) return rc;
     if (niter <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_slopeavedown_strip: niter must be given (a strip does not know the raster's middle row)");
     if (too_big(nx, ny_local + 2)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
     return sad_impl(ctx, strip_from_comm(comm, int(nx), int(ny_local)), d_p, p_nodata, d_fel, fel_nodata, dxc, dyc, dn, niter, d_slpd, stats);
@@ -177,16 +181,10 @@ extern "C" int tdx_slopeavedown_strip(tdx_context* ctx, const tdx_comm* comm, in
 extern "C" int tdx_slopeavedown(tdx_context* ctx, const int16_t* p, int64_t nx, int64_t ny, int16_t p_nodata, const float* fel, float fel_nodata, const double* dxc,
                                 const double* dyc, double dn, int64_t niter, float* slpd, tdx_stats* stats) {
     if (!ctx || !p || !fel || !slpd || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_slopeavedown: bad argument");
-    const size_t n = size_t(nx) * size_t(ny);
-    int16_t* d_p = static_cast<int16_t*>(ctx->scratch(TDX_S_IO0, n * 2));
-    float* d_o = static_cast<float*>(ctx->scratch(TDX_S_IO1, n * 4));
-    float* d_z = static_cast<float*>(ctx->scratch(TDX_S_IO2, n * 4));
-    if (!d_p || !d_o || !d_z) return TDX_ERR_NOMEM;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, p, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_z, fel, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = tdx_slopeavedown_dev(ctx, d_p, nx, ny, p_nodata, d_z, fel_nodata, dxc, dyc, dn, niter, d_o, stats);
-    if (rc != TDX_OK) return rc;
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(slpd, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDX_OK;
+    HostCall h(ctx, nx, ny);
+    int16_t* d_p = h.in(TDX_S_IO0, p);
+    float* d_o = h.out(TDX_S_IO1, slpd);
+    float* d_z = h.in(TDX_S_IO2, fel);
+    if (h.error) return h.error;
+    return h.finish(tdx_slopeavedown_dev(ctx, d_p, nx, ny, p_nodata, d_z, fel_nodata, dxc, dyc, dn, niter, d_o, stats));
 }
