@@ -103,11 +103,82 @@ class TdxRasterInfo(C.Structure):
     ]
 
 
-# name -> (restype, argtypes): every symbol include/taudem_amd.h declares
 _P = C.c_void_p
 _I64 = C.c_int64
 _F = C.c_float
+_INT, _I16, _I32, _D = C.c_int, C.c_int16, C.c_int32, C.c_double
+
+# tool -> argtypes of tdx_<tool>, under the argument names of include/taudem_amd.h.  tdx_<tool>_dev takes the same list with device rasters,
+# tdx_<tool>_strip the comm pointer after the context (and ny_local for ny): _signatures() writes the three rows out.
+_TOOLS = {
+    # ctx, dem, nx, ny, dem_nodata, mask, fourway, fel, stats
+    "pitremove": [_P, _P, _I64, _I64, _F, _P, _INT, _P, _P],
+    # ctx, fel, nx, ny, fel_nodata, dxc, dyc, p, sd8, stats
+    "d8flowdir": [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P],
+    # ctx, p, nx, ny, p_nodata, w, w_nodata, contcheck, outlet_x, outlet_y, n_outlets, ad8, stats
+    "aread8": [_P, _P, _I64, _I64, _I16, _P, _F, _INT, _P, _P, _I64, _P, _P],
+    # ctx, p, nx, ny, p_nodata, sa, usemax, contcheck, outlet_x, outlet_y, n_outlets, ssa, stats
+    "d8flowpathextremeup": [_P, _P, _I64, _I64, _I16, _P, _INT, _INT, _P, _P, _I64, _P, _P],
+    # ctx, p, nx, ny, p_nodata, dxc, dyc, mask, thresh, outlet_x, outlet_y, n_outlets, plen, tlen, gord, stats
+    "gridnet": [_P, _P, _I64, _I64, _I16, _P, _P, _P, _I32, _P, _P, _I64, _P, _P, _P, _P],
+    # ctx, ssa, nx, ny, ssa_nodata, mask, thresh, src, stats (no strip form)
+    "threshold": [_P, _P, _I64, _I64, _F, _P, _F, _P, _P],
+    # ctx, fel, nx, ny, fel_nodata, dxc, dyc, ang, slp, stats
+    "dinfflowdir": [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, w, contcheck, outlet_x, outlet_y, n_outlets, sca, stats
+    "areadinf": [_P, _P, _I64, _I64, _F, _P, _P, _P, _INT, _P, _P, _I64, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, w, contcheck, outlet_x, outlet_y, n_outlets, dsca, stats
+    "dinfdecayaccum": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _INT, _P, _P, _I64, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dg, dep, stats
+    "dinfupdependence": [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, w, w_nodata, racc, dmax, stats
+    "dinfrevaccum": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, src, w, w_nodata, statmethod, typemethod, contcheck, dd, stats
+    "dinfdistdown": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, _INT, _INT, _INT, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, w, w_nodata, statmethod, typemethod, contcheck, thresh, du, stats
+    "dinfdistup": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _INT, _INT, _INT, _F, _P, _P],
+    # ctx, p, nx, ny, p_nodata, src, src_nodata, thresh, dxc, dyc, dist, stats
+    "d8hdisttostrm": [_P, _P, _I64, _I64, _I16, _P, _I32, _I32, _P, _P, _P, _P],
+    # ctx, p, nx, ny, p_nodata, outlet_x, outlet_y, ids, n_outlets, gw, placed, iddown, stats
+    "gagewatershed": [_P, _P, _I64, _I64, _I16, _P, _P, _P, _I64, _P, _P, _P, _P],
+    # ctx, p, nx, ny, p_nodata, fel, src, src_nodata, thresh, dist, stats
+    "d8vdisttostrm": [_P, _P, _I64, _I64, _I16, _P, _P, _I32, _I32, _P, _P],
+    # ctx, p, nx, ny, p_nodata, z, z_nodata, zfdc, stats
+    "flowdircond": [_P, _P, _I64, _I64, _I16, _P, _F, _P, _P],
+    # ctx, p, nx, ny, p_nodata, fel, fel_nodata, dxc, dyc, dn, niter, slpd, stats
+    "slopeavedown": [_P, _P, _I64, _I64, _I16, _P, _F, _P, _P, _D, _I64, _P, _P],
+    # ctx, hand, catch, slp, nx, ny, hand_nodata, catch_nodata, slp_nodata, dxc, dyc, ids, ncatch, stages, nheight, count, surface, bed, volume,
+    # catcharea, stats
+    "catchhydrogeo": [_P, _P, _P, _P, _I64, _I64, _F, _I32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P],
+    # ctx, hand, catch, mask, nx, ny, hand_nodata, catch_nodata, mask_nodata, dxc, dyc, ids, depth, nfc, map, area, stats
+    "inundepth": [_P, _P, _P, _P, _I64, _I64, _F, _I32, _I16, _P, _P, _P, _P, _I64, _P, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, wg, wg_nodata, rc, rc_nodata, qrl, stats
+    "retlimflow": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, ass, ass_nodata, thresh, alpha, path, geo, geographic, rz, dfs, stats
+    "dinfavalanche": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _I16, _F, _F, _INT, _P, _INT, _P, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, dg, q, q_nodata, csol, contcheck, outlet_x, outlet_y, n_outlets, ctpt, stats
+    "dinfconclimaccum": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, _F, _INT, _P, _P, _I64, _P, _P],
+    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, tsup, tsup_nodata, tc, tc_nodata, cs, cs_nodata, contcheck, outlet_x, outlet_y, n_outlets, tla, tdep,
+    # ctpt, stats
+    "dinftranslimaccum": [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _F, _INT, _P, _P, _I64, _P, _P, _P, _P],
+}
+
+
+def _signatures():
+    """tdx_<tool>, tdx_<tool>_dev and tdx_<tool>_strip of every tool in _TOOLS."""
+    out = {}
+    for tool, args in _TOOLS.items():
+        out["tdx_" + tool] = out["tdx_" + tool + "_dev"] = (C.c_int, args)
+        if tool != "threshold":
+            out["tdx_" + tool + "_strip"] = (C.c_int, args[:1] + [_P] + args[1:])
+    # ..., geographic, row0, ny_total, rz, dfs, stats: the strip says where it lies in the whole raster
+    out["tdx_dinfavalanche_strip"] = (C.c_int, out["tdx_dinfavalanche_strip"][1][:-3] + [_I64, _I64, _P, _P, _P])
+    return out
+
+
+# name -> (restype, argtypes): every symbol include/taudem_amd.h declares
 _SIGNATURES = {
+    **_signatures(),
     "tdx_context_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "tdx_context_destroy": (None, [_P]),
     "tdx_context_release_scratch": (C.c_int, [_P]),
@@ -121,102 +192,20 @@ _SIGNATURES = {
     "tdx_device_free": (C.c_int, [_P, _P]),
     "tdx_copy_to_device": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "tdx_copy_to_host": (C.c_int, [_P, _P, _P, C.c_uint64]),
-    "tdx_pitremove_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, C.c_int, _P, _P]),
-    "tdx_pitremove": (C.c_int, [_P, _P, _I64, _I64, _F, _P, C.c_int, _P, _P]),
-    "tdx_d8flowdir_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_d8flowdir": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_aread8_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_aread8": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_d8flowpathextremeup_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_d8flowpathextremeup": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_d8flowpathextremeup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, C.c_int, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_gridnet_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, C.c_int32, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_gridnet": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, C.c_int32, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_gridnet_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, _P, C.c_int32, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_threshold_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _F, _P, _P]),
-    "tdx_threshold": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _F, _P, _P]),
-    "tdx_dinfflowdir_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_dinfflowdir": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_areadinf_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_areadinf": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfdecayaccum_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfdecayaccum": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_pitremove_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, C.c_int, _P, _P]),
-    "tdx_d8flowdir_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_aread8_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfflowdir_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_areadinf_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfdecayaccum_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfupdependence_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_dinfupdependence": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_dinfupdependence_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
-    "tdx_dinfrevaccum_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
-    "tdx_dinfrevaccum": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
-    "tdx_dinfrevaccum_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _P]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, src, w, w_nodata, statmethod, typemethod, contcheck, dd, stats
-    "tdx_dinfdistdown_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
-    "tdx_dinfdistdown": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
-    "tdx_dinfdistdown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P]),
     "tdx_tool_dinfdistdown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, w, w_nodata, statmethod, typemethod, contcheck, thresh, du, stats
-    "tdx_d8hdisttostrm_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
-    "tdx_d8hdisttostrm": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
-    "tdx_d8hdisttostrm_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "tdx_tool_d8hdisttostrm": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
-    "tdx_gagewatershed_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_gagewatershed": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_gagewatershed_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "tdx_tool_gagewatershed": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
-    # ctx, p, nx, ny, p_nodata, fel, src, src_nodata, thresh, dist, stats
-    "tdx_d8vdisttostrm_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
-    "tdx_d8vdisttostrm": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
-    "tdx_d8vdisttostrm_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "tdx_tool_d8vdisttostrm": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
-    # ctx, p, nx, ny, p_nodata, z, z_nodata, zfdc, stats
-    "tdx_flowdircond_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
-    "tdx_flowdircond": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
-    "tdx_flowdircond_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P]),
     "tdx_tool_flowdircond": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
-    # ctx, p, nx, ny, p_nodata, fel, fel_nodata, dxc, dyc, dn, niter, slpd, stats
     "tdx_slopeavedown_niter": (_I64, [C.c_double, _P, _P, _I64]),
-    "tdx_slopeavedown_dev": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
-    "tdx_slopeavedown": (C.c_int, [_P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
-    "tdx_slopeavedown_strip": (C.c_int, [_P, _P, _P, _I64, _I64, C.c_int16, _P, _F, _P, _P, C.c_double, _I64, _P, _P]),
     "tdx_tool_slopeavedown": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_double]),
-    # ctx, [comm,] hand, catch, slp, nx, ny, hand_nd, catch_nd, slp_nd, dxc, dyc, ids, ncatch, stages, nheight, count, surface, bed, volume, catcharea, stats
-    "tdx_catchhydrogeo": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
-    "tdx_catchhydrogeo_dev": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
-    "tdx_catchhydrogeo_strip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, C.c_int32, _F, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "tdx_tool_catchhydrogeo": (C.c_int, [C.c_char_p] * 6),
-    # ctx, [comm,] hand, catch, mask, nx, ny, hand_nd, catch_nd, mask_nd, dxc, dyc, ids, depth, nfc, map, area, stats
-    "tdx_inundepth": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
-    "tdx_inundepth_dev": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
-    "tdx_inundepth_strip": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, C.c_int32, C.c_int16, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "tdx_tool_inundepth": (C.c_int, [C.c_char_p] * 7),
-    "tdx_dinfdistup_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
-    "tdx_dinfdistup": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
-    "tdx_dinfdistup_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, C.c_int, C.c_int, C.c_int, _F, _P, _P]),
     "tdx_tool_dinfdistup": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, wg, wg_nodata, rc, rc_nodata, qrl, stats
-    "tdx_retlimflow": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
-    "tdx_retlimflow_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
-    "tdx_retlimflow_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _P]),
     "tdx_tool_retlimflow": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, fel, fel_nodata, ass, ass_nodata, thresh, alpha, path, geo, geographic, [row0, ny_total,] rz, dfs, stats
-    "tdx_dinfavalanche": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _P, _P, _P]),
-    "tdx_dinfavalanche_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _P, _P, _P]),
-    "tdx_dinfavalanche_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, C.c_int16, _F, _F, C.c_int, _P, C.c_int, _I64, _I64, _P, _P, _P]),
     "tdx_tool_dinfavalanche": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _F, _F, C.c_int]),
     "tdx_tool_dinfupdependence": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     "tdx_tool_dinfrevaccum": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, dm, dm_nodata, dg, q, q_nodata, csol, contcheck, ox, oy, n_outlets, ctpt, stats
-    "tdx_dinfconclimaccum": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfconclimaccum_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    "tdx_dinfconclimaccum_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _P, _F, _F, C.c_int, _P, _P, _I64, _P, _P]),
-    # ctx, ang, nx, ny, ang_nodata, dxc, dyc, tsup, tsup_nodata, tc, tc_nodata, cs, cs_nodata, contcheck, ox, oy, n_outlets, tla, tdep, ctpt, stats
-    "tdx_dinftranslimaccum": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _F, C.c_int, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_dinftranslimaccum_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _F, C.c_int, _P, _P, _I64, _P, _P, _P, _P]),
-    "tdx_dinftranslimaccum_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _F, _P, _F, _P, _F, C.c_int, _P, _P, _I64, _P, _P, _P, _P]),
     "tdx_tool_dinfconclimaccum": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_float]),
     "tdx_tool_dinftranslimaccum": (C.c_int, [C.c_char_p] * 9 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tdx_synth_dem_dev": (C.c_int, [_P, C.c_uint64, _I64, _I64, _I64, _I64, _I64, _P]),

@@ -24,12 +24,16 @@ DISTDOWN_STATS = {"ave": 0, "max": 1, "min": 2}                    # -m <stat> o
 DISTDOWN_KINDS = {"h": 0, "v": 1, "p": 2, "s": 3}                   # -m <type>
 
 
-def _distdown_mode(stat, kind):
+def _distdown_mode(stat, kind, fel, weights):
+    """(statmethod, typemethod, fel, weights) of DinfDistDown / DinfDistUp: fel is needed by every kind but "h", which does not read it;
+    "v" does not read the weights."""
     if stat not in DISTDOWN_STATS:
         raise ValueError(f"stat must be one of {sorted(DISTDOWN_STATS)}, not {stat!r}")
     if kind not in DISTDOWN_KINDS:
         raise ValueError(f"kind must be one of {sorted(DISTDOWN_KINDS)}, not {kind!r}")
-    return DISTDOWN_STATS[stat], DISTDOWN_KINDS[kind]
+    if kind != "h" and fel is None:
+        raise ValueError(f"kind {kind!r} needs fel")
+    return DISTDOWN_STATS[stat], DISTDOWN_KINDS[kind], fel if kind != "h" else None, weights if kind != "v" else None
 
 
 def _is_torch(x):
@@ -39,6 +43,109 @@ def _is_torch(x):
 def _f64(a, n):
     a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n,)))
     return a
+
+
+def _flat(a, dtype):
+    return np.ascontiguousarray(np.asarray(a, dtype=dtype)).reshape(-1)
+
+
+def _v(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _torch_dtype(dtype):
+    import torch
+
+    return {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
+
+
+class _Call:
+    """The frame of one library call, shared by Context.<tool> and StripPipeline.<tool>.  It registers the rasters under one rule, turns
+    cell sizes and outlets into host arrays that live as long as it does, and makes the call: tdx_<tool> for numpy rasters,
+    tdx_<tool>_dev for tensors, tdx_<tool>_strip (with the comm after the context) for a strip.
+
+    The rule: every raster is a C-contiguous numpy array or a contiguous CUDA tensor of the dtype asked for; the first one registered
+    decides the side (host or device) and, for a Context, the shape (ny, nx); every later one, outputs included, has that side and that
+    shape.  A strip takes tensors only, of shape (ny_local + 2, nx).  Anything else raises ValueError before the library is entered."""
+
+    def __init__(self, ctx, strip_shape=None, comm=None):
+        self.ctx, self.strip, self.shape, self.comm = ctx, strip_shape is not None, strip_shape, comm
+        self.first = None      # the first raster: the side, and what outputs are allocated like
+        self.keep = []         # host arrays the library reads through the bare pointers handed out
+
+    def raster(self, a, dtype, name):
+        """The pointer of raster `a` (None for None, an optional raster not given) after the checks of the rule."""
+        if a is None:
+            return None
+        dev = _is_torch(a)
+        if dev:
+            if not a.is_cuda or (not self.strip and a.device.index != self.ctx.device):
+                raise ValueError(f"{name}: tensor must live on cuda:{self.ctx.device}")
+            if a.dtype != _torch_dtype(dtype) or not a.is_contiguous():
+                raise ValueError(f"{name}: need contiguous {_torch_dtype(dtype)}")
+        elif self.strip:
+            raise ValueError(f"{name}: a strip array is a CUDA tensor")
+        elif not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous:
+            raise ValueError(f"{name}: need C-contiguous numpy {np.dtype(dtype)}")
+        if self.first is None:
+            if self.shape is None:
+                ny, nx = a.shape
+                self.shape = (ny, nx)
+            self.first, self.dev = a, dev
+            self.rows, self.nx = self.shape                       # rows of the array in hand: what dx / dy are broadcast over
+            self.ny = self.rows - 2 if self.strip else self.rows   # what the library is told: a strip's owned rows
+        if dev != self.dev:
+            raise ValueError(f"{name}: all rasters must be on the same side (host or device)")
+        if tuple(a.shape) != tuple(self.shape):
+            raise ValueError(f"{name}: shape {tuple(a.shape)} != {tuple(self.shape)}")
+        return C.c_void_p(a.data_ptr() if dev else a.ctypes.data)
+
+    def out(self, given, dtype, name):
+        """(raster, pointer) of an output: the caller's out= if given, else a new one like the first raster."""
+        if given is not None:
+            a = given
+        elif self.dev:
+            import torch
+
+            a = torch.empty(self.shape, dtype=_torch_dtype(dtype), device=self.first.device)
+        else:
+            a = np.empty(self.shape, dtype=dtype)
+        return a, self.raster(a, dtype, name)
+
+    def cells(self, dx, dy):
+        """Pointers to dx and dy, scalars or per-row arrays, as one float64 per row of the array in hand."""
+        dxc, dyc = _f64(dx, self.rows), _f64(dy, self.rows)
+        self.keep += [dxc, dyc]
+        return _v(dxc), _v(dyc)
+
+    def outlets(self, outlets):
+        """(outlet_x, outlet_y, n_outlets) of (columns, rows); None: no outlets."""
+        if outlets is None:
+            return None, None, -1
+        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32))
+        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32))
+        if ox.shape != oy.shape or ox.ndim != 1:
+            raise ValueError("outlets: need two equal-length 1-D index arrays (columns, rows)")
+        self.keep += [ox, oy]
+        return _v(ox), _v(oy), int(ox.size)
+
+    def call(self, symbol, *args):
+        """symbol[_dev | _strip](ctx, [comm,] args..., &stats) -> the stats dict.  `args`: the header's arguments between the context and
+        the stats, in its order.  Device rasters: torch's work on them is waited for first."""
+        if self.dev:
+            import torch
+
+            torch.cuda.synchronize(self.ctx.device)
+        fn = getattr(self.ctx._lib, symbol + ("_strip" if self.strip else "_dev" if self.dev else ""))
+        head = (self.ctx._h, self.comm) if self.strip else (self.ctx._h,)
+        st = TdxStats()
+        check(fn(*head, *args, C.byref(st)), self.ctx._h)
+        return st.as_dict()
+
+
+def _ret(res, stats):
+    """What a Context method returns of a body's (outputs..., stats dict): all of it with stats=True, else the outputs, a single one bare."""
+    return res if stats else res[0] if len(res) == 2 else res[:-1]
 
 
 class Context:
@@ -98,247 +205,56 @@ class Context:
     def __exit__(self, *a):
         self.close()
 
-    # ---- helpers --------------------------------------------------------------------------
-    def _ptr(self, a, dtype, shape=None, name="array"):
-        """(pointer, is_device) for a numpy array or torch cuda tensor; validates dtype/contiguity."""
-        if a is None:
-            return None, None
-        if _is_torch(a):
-            import torch
-
-            want = {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
-            if not a.is_cuda or a.device.index != self.device:
-                raise ValueError(f"{name}: tensor must live on cuda:{self.device}")
-            if a.dtype != want or not a.is_contiguous():
-                raise ValueError(f"{name}: need contiguous {want}")
-            if shape is not None and tuple(a.shape) != tuple(shape):
-                raise ValueError(f"{name}: shape {tuple(a.shape)} != {tuple(shape)}")
-            return C.c_void_p(a.data_ptr()), True
-        if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous:
-            raise ValueError(f"{name}: need C-contiguous numpy {np.dtype(dtype)}")
-        if shape is not None and tuple(a.shape) != tuple(shape):
-            raise ValueError(f"{name}: shape {tuple(a.shape)} != {tuple(shape)}")
-        return C.c_void_p(a.ctypes.data), False
-
-    def _out(self, like, dtype, shape):
-        if _is_torch(like):
-            import torch
-
-            td = {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
-            return torch.empty(shape, dtype=td, device=like.device)
-        return np.empty(shape, dtype=dtype)
-
-    def _sync_torch(self, *arrs):
-        if any(_is_torch(a) for a in arrs):
-            import torch
-
-            torch.cuda.synchronize(self.device)
-
-    @staticmethod
-    def _outlets(outlets):
-        if outlets is None:
-            return None, None, -1, ()
-        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32))
-        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32))
-        if ox.shape != oy.shape or ox.ndim != 1:
-            raise ValueError("outlets: need two equal-length 1-D index arrays (columns, rows)")
-        return C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data), int(ox.size), (ox, oy)
-
-    def _pick(self, dev, name):
-        return getattr(self._lib, name + ("_dev" if dev else ""))
-
-    # ---- stages ---------------------------------------------------------------------------
+    # ---- stages: thin signatures over the shared bodies below (_pitremove(...) etc.), on a _Call frame of this context ---------------
     def pitremove(self, dem, nodata=-9999.0, mask=None, fourway=False, out=None, stats=False):
         """fel = flood(dem)  (src/flood.cpp:50)."""
-        ny, nx = dem.shape
-        fel = out if out is not None else self._out(dem, np.float32, (ny, nx))
-        pz, dev = self._ptr(dem, np.float32, name="dem")
-        pm, mdev = self._ptr(mask, np.int16, (ny, nx), "mask")
-        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
-        if fdev != dev or (mask is not None and mdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(dem, mask)
-        check(self._pick(dev, "tdx_pitremove")(self._h, pz, nx, ny, float(nodata), pm, int(bool(fourway)), pf, C.byref(st)), self._h)
-        return (fel, st.as_dict()) if stats else fel
+        return _ret(_pitremove(_Call(self), dem, nodata, mask, fourway, out), stats)
 
     def d8flowdir(self, fel, nodata=float(FEL_NODATA), dx=1.0, dy=1.0, want_slope=True, out=None, stats=False):
         """p, sd8 = setdird8(fel)  (src/d8.cpp:181).  dx, dy: scalars or per-row arrays (metres)."""
-        ny, nx = fel.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        p = out[0] if out is not None else self._out(fel, np.int16, (ny, nx))
-        sd8 = (out[1] if out is not None else self._out(fel, np.float32, (ny, nx))) if want_slope else None
-        pz, dev = self._ptr(fel, np.float32, name="fel")
-        pp, pdev = self._ptr(p, np.int16, (ny, nx), "p")
-        ps, _ = self._ptr(sd8, np.float32, (ny, nx), "sd8")
-        if pdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(fel)
-        check(self._pick(dev, "tdx_d8flowdir")(self._h, pz, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                pp, ps, C.byref(st)), self._h)
-        res = (p, sd8) if want_slope else (p, None)
-        return (res + (st.as_dict(),)) if stats else res
+        return _ret(_d8flowdir(_Call(self), fel, nodata, dx, dy, want_slope, out), stats)
 
     def aread8(self, p, nodata=int(P_NODATA), weights=None, weights_nodata=-9999.0, contcheck=True, outlets=None, out=None, stats=False):
         """ad8 = aread8(p)  (src/aread8.cpp:56).  outlets: (columns, rows) global indices or None."""
-        ny, nx = p.shape
-        ad8 = out if out is not None else self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pw, wdev = self._ptr(weights, np.float32, (ny, nx), "weights")
-        pa, adev = self._ptr(ad8, np.float32, (ny, nx), "ad8")
-        if adev != dev or (weights is not None and wdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(p, weights)
-        check(self._pick(dev, "tdx_aread8")(self._h, pp, nx, ny, int(nodata), pw, float(weights_nodata), int(bool(contcheck)), ox, oy, no, pa,
-                                             C.byref(st)), self._h)
-        del keep
-        return (ad8, st.as_dict()) if stats else ad8
+        return _ret(_aread8(_Call(self), p, nodata, weights, weights_nodata, contcheck, outlets, out), stats)
 
     def d8flowpathextremeup(self, p, sa, nodata=int(P_NODATA), usemax=True, contcheck=True, outlets=None, out=None, stats=False):
         """ssa = d8flowpathextremeup(p, sa)  (src/D8flowpathextremeup.cpp:58): upstream max / min of sa along D8 flow paths (nodata -FLT_MAX)."""
-        ny, nx = p.shape
-        ssa = out if out is not None else self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pa, adev = self._ptr(sa, np.float32, (ny, nx), "sa")
-        ps, sdev = self._ptr(ssa, np.float32, (ny, nx), "ssa")
-        if adev != dev or sdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(p, sa)
-        check(self._pick(dev, "tdx_d8flowpathextremeup")(self._h, pp, nx, ny, int(nodata), pa, int(bool(usemax)), int(bool(contcheck)), ox, oy, no, ps,
-                                                          C.byref(st)), self._h)
-        del keep
-        return (ssa, st.as_dict()) if stats else ssa
+        return _ret(_d8flowpathextremeup(_Call(self), p, sa, nodata, usemax, contcheck, outlets, out), stats)
 
     def gridnet(self, p, nodata=int(P_NODATA), dx=1.0, dy=1.0, mask=None, thresh=0, outlets=None, stats=False):
         """plen, tlen, gord = gridnet(p)  (src/gridnet.cpp:54).  mask: int32 raster, cells with mask >= thresh are evaluated;
         outlets: (columns, rows) - only their upstream closure is evaluated."""
-        ny, nx = p.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        plen = self._out(p, np.float32, (ny, nx))
-        tlen = self._out(p, np.float32, (ny, nx))
-        gord = self._out(p, np.int16, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pm, mdev = self._ptr(mask, np.int32, (ny, nx), "mask")
-        ppl, _ = self._ptr(plen, np.float32, (ny, nx), "plen")
-        ptl, _ = self._ptr(tlen, np.float32, (ny, nx), "tlen")
-        pgo, _ = self._ptr(gord, np.int16, (ny, nx), "gord")
-        if mask is not None and mdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        ox, oy, no, keep = self._outlets(outlets)
-        self._sync_torch(p, mask)
-        check(self._pick(dev, "tdx_gridnet")(self._h, pp, nx, ny, int(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pm, int(thresh),
-                                              ox, oy, no, ppl, ptl, pgo, C.byref(st)), self._h)
-        del keep
-        return (plen, tlen, gord, st.as_dict()) if stats else (plen, tlen, gord)
+        return _ret(_gridnet(_Call(self), p, nodata, dx, dy, mask, thresh, outlets), stats)
 
     def threshold(self, ssa, thresh, nodata=-1.0, mask=None, stats=False):
         """src = threshold(ssa)  (src/Threshold.cpp:49): 1 where ssa >= thresh (and mask >= 0), 0 elsewhere, -32768 where ssa is nodata."""
-        ny, nx = ssa.shape
-        src = self._out(ssa, np.int16, (ny, nx))
-        pa, dev = self._ptr(ssa, np.float32, name="ssa")
-        pm, mdev = self._ptr(mask, np.float32, (ny, nx), "mask")
-        ps, _ = self._ptr(src, np.int16, (ny, nx), "src")
-        if mask is not None and mdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ssa, mask)
-        check(self._pick(dev, "tdx_threshold")(self._h, pa, nx, ny, float(nodata), pm, float(thresh), ps, C.byref(st)), self._h)
-        return (src, st.as_dict()) if stats else src
+        f = _Call(self)
+        pa = f.raster(ssa, np.float32, "ssa")
+        pm = f.raster(mask, np.float32, "mask")
+        src, ps = f.out(None, np.int16, "src")
+        return _ret((src, f.call("tdx_threshold", pa, f.nx, f.ny, float(nodata), pm, float(thresh), ps)), stats)
 
     def dinfflowdir(self, fel, nodata=float(FEL_NODATA), dx=1.0, dy=1.0, out=None, stats=False):
         """ang, slp = setdir(fel)  (src/dinf.cpp:109)."""
-        ny, nx = fel.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        ang = out[0] if out is not None else self._out(fel, np.float32, (ny, nx))
-        slp = out[1] if out is not None else self._out(fel, np.float32, (ny, nx))
-        pz, dev = self._ptr(fel, np.float32, name="fel")
-        pa, adev = self._ptr(ang, np.float32, (ny, nx), "ang")
-        ps, _ = self._ptr(slp, np.float32, (ny, nx), "slp")
-        if adev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(fel)
-        check(self._pick(dev, "tdx_dinfflowdir")(self._h, pz, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                  pa, ps, C.byref(st)), self._h)
-        return (ang, slp, st.as_dict()) if stats else (ang, slp)
+        return _ret(_dinfflowdir(_Call(self), fel, nodata, dx, dy, out), stats)
 
     def areadinf(self, ang, nodata=float(ANG_NODATA), dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None, stats=False):
         """sca = area(ang)  (src/areadinf.cpp:53)."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        sca = out if out is not None else self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pw, wdev = self._ptr(weights, np.float32, (ny, nx), "weights")
-        ps, sdev = self._ptr(sca, np.float32, (ny, nx), "sca")
-        if sdev != dev or (weights is not None and wdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(ang, weights)
-        check(self._pick(dev, "tdx_areadinf")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw,
-                                               int(bool(contcheck)), ox, oy, no, ps, C.byref(st)), self._h)
-        del keep
-        return (sca, st.as_dict()) if stats else sca
+        return _ret(_areadinf(_Call(self), ang, nodata, dx, dy, weights, contcheck, outlets, out), stats)
 
     def dinfdecayaccum(self, ang, dm, nodata=float(ANG_NODATA), dm_nodata=-9999.0, dx=1.0, dy=1.0, weights=None, contcheck=True,
                        outlets=None, out=None, stats=False):
         """dsca = dmarea(ang, dm)  (src/dinfdecayaccum.cpp:61)."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        dsca = out if out is not None else self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pd, ddev = self._ptr(dm, np.float32, (ny, nx), "dm")
-        pw, wdev = self._ptr(weights, np.float32, (ny, nx), "weights")
-        ps, sdev = self._ptr(dsca, np.float32, (ny, nx), "dsca")
-        if sdev != dev or ddev != dev or (weights is not None and wdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(ang, dm, weights)
-        check(self._pick(dev, "tdx_dinfdecayaccum")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                     pd, float(dm_nodata), pw, int(bool(contcheck)), ox, oy, no, ps, C.byref(st)), self._h)
-        del keep
-        return (dsca, st.as_dict()) if stats else dsca
+        return _ret(_dinfdecayaccum(_Call(self), ang, dm, nodata, dm_nodata, dx, dy, weights, contcheck, outlets, out), stats)
 
     def dinfupdependence(self, ang, dg, nodata=float(ANG_NODATA), dx=1.0, dy=1.0, stats=False):
         """dep = depgrd(ang, dg)  (src/DinfUpDependence.cpp:52): dg int32, dep float32 (nodata -1)."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        dep = self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pg, gdev = self._ptr(dg, np.int32, (ny, nx), "dg")
-        po, _ = self._ptr(dep, np.float32, (ny, nx), "dep")
-        if gdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ang, dg)
-        check(self._pick(dev, "tdx_dinfupdependence")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pg, po,
-                                                       C.byref(st)), self._h)
-        return (dep, st.as_dict()) if stats else dep
+        return _ret(_dinfupdependence(_Call(self), ang, dg, nodata, dx, dy), stats)
 
     def dinfrevaccum(self, ang, w, nodata=float(ANG_NODATA), w_nodata=-9999.0, dx=1.0, dy=1.0, stats=False):
         """racc, dmax = dsaccum(ang, w)  (src/DinfRevAccum.cpp:51): float32, nodata -FLT_MAX."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        racc = self._out(ang, np.float32, (ny, nx))
-        dmax = self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pw, wdev = self._ptr(w, np.float32, (ny, nx), "w")
-        pr, _ = self._ptr(racc, np.float32, (ny, nx), "racc")
-        pm, _ = self._ptr(dmax, np.float32, (ny, nx), "dmax")
-        if wdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ang, w)
-        check(self._pick(dev, "tdx_dinfrevaccum")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw,
-                                                   float(w_nodata), pr, pm, C.byref(st)), self._h)
-        return (racc, dmax, st.as_dict()) if stats else (racc, dmax)
+        return _ret(_dinfrevaccum(_Call(self), ang, w, nodata, w_nodata, dx, dy), stats)
 
     def dinfdistdown(self, ang, src, fel=None, *, stat="ave", kind="v", weights=None, weights_nodata=-9999.0, contcheck=True, dx=1.0, dy=1.0,
                      nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
@@ -347,63 +263,21 @@ class Context:
         kind "h" horizontal, "v" vertical drop (with stat "ave": HAND), "p" Pythagorean, "s" surface; stat "ave", "max" or "min" over
         the receivers.  `fel` is required for v, p and s; `weights` scale the horizontal steps of h, p and s (v ignores them, as the
         reference does).  dd float32, nodata -FLT_MAX."""
-        sm, tm = _distdown_mode(stat, kind)
-        if tm != DISTDOWN_KINDS["h"] and fel is None:
-            raise ValueError(f"kind {kind!r} needs fel")
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        dd = self._out(ang, np.float32, (ny, nx))
-        use_fel = tm != DISTDOWN_KINDS["h"]
-        use_w = weights is not None and tm != DISTDOWN_KINDS["v"]
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        ps, sdev = self._ptr(src, np.int16, (ny, nx), "src")
-        pf, fdev = self._ptr(fel if use_fel else None, np.float32, (ny, nx), "fel")
-        pw, wdev = self._ptr(weights if use_w else None, np.float32, (ny, nx), "weights")
-        po, _ = self._ptr(dd, np.float32, (ny, nx), "dd")
-        if sdev != dev or (use_fel and fdev != dev) or (use_w and wdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ang, src, fel, weights)
-        check(self._pick(dev, "tdx_dinfdistdown")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf,
-                                                   float(fel_nodata), ps, pw, float(weights_nodata), sm, tm, int(bool(contcheck)), po, C.byref(st)), self._h)
-        return (dd, st.as_dict()) if stats else dd
+        return _ret(_dinfdistdown(_Call(self), ang, src, fel, stat, kind, weights, weights_nodata, contcheck, dx, dy, nodata, fel_nodata), stats)
 
     def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=int(P_NODATA), src_nodata=-2147483647, stats=False):
         """dist = distgrid(p, src)  (src/D8HDistToStrm.cpp:57): horizontal distance along the D8 flow path down to the stream.
 
         Stream cells are those where src (int32, the reference's LONG read) is not src_nodata and is >= thresh, whatever p is there;
         they get 0.  dist float32, nodata -FLT_MAX (off the raster, into a cell without a result, around a cycle)."""
-        ny, nx = p.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        dist = self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        ps, sdev = self._ptr(src, np.int32, (ny, nx), "src")
-        po, _ = self._ptr(dist, np.float32, (ny, nx), "dist")
-        if sdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(p, src)
-        check(self._pick(dev, "tdx_d8hdisttostrm")(self._h, pp, nx, ny, int(nodata), ps, int(src_nodata), int(thresh), C.c_void_p(dxc.ctypes.data),
-                                                   C.c_void_p(dyc.ctypes.data), po, C.byref(st)), self._h)
-        return (dist, st.as_dict()) if stats else dist
+        return _ret(_d8hdisttostrm(_Call(self), p, src, thresh, dx, dy, nodata, src_nodata), stats)
 
     def d8vdisttostrm(self, p, fel, src, thresh=1, *, nodata=int(P_NODATA), src_nodata=-2147483647, stats=False):
         """dist = d8vdistdown(p, fel, src)  (src/D8VDistToStrm.cpp:58): vertical drop along the D8 flow path down to the stream.
 
         Stream cells as for d8hdisttostrm; every other cell gets (fel - fel(receiver)) + dist(receiver) in float32.  fel is read with no
         nodata test, as in the reference.  dist float32, nodata -FLT_MAX."""
-        ny, nx = p.shape
-        dist = self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
-        ps, sdev = self._ptr(src, np.int32, (ny, nx), "src")
-        po, _ = self._ptr(dist, np.float32, (ny, nx), "dist")
-        if sdev != dev or fdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(p, fel, src)
-        check(self._pick(dev, "tdx_d8vdisttostrm")(self._h, pp, nx, ny, int(nodata), pf, ps, int(src_nodata), int(thresh), po, C.byref(st)), self._h)
-        return (dist, st.as_dict()) if stats else dist
+        return _ret(_d8vdisttostrm(_Call(self), p, fel, src, thresh, nodata, src_nodata), stats)
 
     def flowdircond(self, p, z, *, nodata=int(P_NODATA), z_nodata=float(FEL_NODATA), stats=False):
         """zfdc = flowdircond(p, z)  (src/flowdircond.cpp:54): z conditioned along the D8 directions - from the ridges downstream every
@@ -411,36 +285,14 @@ class Context:
 
         Cells the reference's queue never reaches (no valid direction, below a p == 0 cell, on or below a cycle) and cells with nodata z
         keep their input value; the result carries z's nodata value."""
-        ny, nx = p.shape
-        out = self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pz, zdev = self._ptr(z, np.float32, (ny, nx), "z")
-        po, _ = self._ptr(out, np.float32, (ny, nx), "zfdc")
-        if zdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(p, z)
-        check(self._pick(dev, "tdx_flowdircond")(self._h, pp, nx, ny, int(nodata), pz, float(z_nodata), po, C.byref(st)), self._h)
-        return (out, st.as_dict()) if stats else out
+        return _ret(_flowdircond(_Call(self), p, z, nodata, z_nodata), stats)
 
     def slopeavedown(self, p, fel, dn=50.0, *, dx=1.0, dy=1.0, niter=None, nodata=int(P_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
         """slpd = sloped(p, fel, dn)  (src/SlopeAveDown.cpp:59): the slope from each cell to the cell the distance dn down its D8 flow path.
 
         niter (default int(dn / min(dx, dy) of the middle row) + 1, the reference's count; not capped) synchronous one-step pulls along
         the D8 pointer.  dn must be finite and not negative.  slpd float32, nodata -FLT_MAX."""
-        ny, nx = p.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        out = self._out(p, np.float32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
-        po, _ = self._ptr(out, np.float32, (ny, nx), "slpd")
-        if fdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(p, fel)
-        check(self._pick(dev, "tdx_slopeavedown")(self._h, pp, nx, ny, int(nodata), pf, float(fel_nodata), C.c_void_p(dxc.ctypes.data),
-                                                  C.c_void_p(dyc.ctypes.data), float(dn), int(niter) if niter else 0, po, C.byref(st)), self._h)
-        return (out, st.as_dict()) if stats else out
+        return _ret(_slopeavedown(_Call(self), p, fel, dn, int(niter) if niter else 0, dx, dy, nodata, fel_nodata), stats)   # 0: the library counts
 
     def catchhydrogeo(self, hand, catch, slp, ids, stages, *, dx=1.0, dy=1.0, hand_nodata=float(ANG_NODATA), catch_nodata=-9999, slp_nodata=-1.0, stats=False):
         """count, surface, bed, volume, catcharea = catchhydrogeo(hand, catch, slp, ids, stages)  (src/CatchHydroGeo.cpp:69).
@@ -449,26 +301,19 @@ class Context:
         bed area and volume; and each catchment's whole plan area.  ids: int32 list (the last row of a repeated id wins, earlier rows stay 0);
         stages: float64, any order.  count int32 and surface / bed / volume float64 are [len(stages)][len(ids)], catcharea float64 [len(ids)];
         all numpy arrays on the host.  The fp64 sums are taken in a fixed order: the same input gives the same bits."""
-        ny, nx = hand.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32)).reshape(-1)
-        stages = np.ascontiguousarray(np.asarray(stages, dtype=np.float64)).reshape(-1)
+        f = _Call(self)
+        ph = f.raster(hand, np.float32, "hand")
+        pc = f.raster(catch, np.int32, "catch")
+        ps = f.raster(slp, np.float32, "slp")
+        pdx, pdy = f.cells(dx, dy)
+        ids, stages = _flat(ids, np.int32), _flat(stages, np.float64)
         nc, nh = ids.size, stages.size
-        ph, dev = self._ptr(hand, np.float32, name="hand")
-        pc, cdev = self._ptr(catch, np.int32, (ny, nx), "catch")
-        ps, sdev = self._ptr(slp, np.float32, (ny, nx), "slp")
-        if cdev != dev or sdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
         count = np.zeros((nh, nc), np.int32)
         surface, bed, volume = (np.zeros((nh, nc), np.float64) for _ in range(3))
         catcharea = np.zeros(nc, np.float64)
-        st = TdxStats()
-        self._sync_torch(hand, catch, slp)
-        v = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-        check(self._pick(dev, "tdx_catchhydrogeo")(self._h, ph, pc, ps, nx, ny, float(hand_nodata), int(catch_nodata), float(slp_nodata), v(dxc), v(dyc), v(ids), nc,
-                                                   v(stages), nh, v(count), v(surface), v(bed), v(volume), v(catcharea), C.byref(st)), self._h)
-        res = (count, surface, bed, volume, catcharea)
-        return res + (st.as_dict(),) if stats else res
+        st = f.call("tdx_catchhydrogeo", ph, pc, ps, f.nx, f.ny, float(hand_nodata), int(catch_nodata), float(slp_nodata), pdx, pdy, _v(ids), nc, _v(stages), nh,
+                    _v(count), _v(surface), _v(bed), _v(volume), _v(catcharea))
+        return _ret((count, surface, bed, volume, catcharea, st), stats)
 
     def inundepth(self, hand, catch, ids, depth, *, mask=None, area=True, dx=1.0, dy=1.0, hand_nodata=float(ANG_NODATA), catch_nodata=-9999, mask_nodata=-32768,
                   stats=False):
@@ -478,26 +323,19 @@ class Context:
         catch and hand have data, depth >= 0 and depth > hand + 0.001.  mask (int16): as in the reference, with a mask every cell of the map is
         nodata.  area (float32 per row, None with area=False): plan area of the cells with depth > 0 and depth - hand > 0, at the winning row
         of each id, 0 elsewhere; summed in fp64 and rounded once."""
-        ny, nx = hand.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32)).reshape(-1)
-        depth = np.ascontiguousarray(np.asarray(depth, dtype=np.float32)).reshape(-1)
+        ids, depth = _flat(ids, np.int32), _flat(depth, np.float32)
         if ids.size != depth.size:
             raise ValueError("ids and depth: need equal lengths")
-        out = self._out(hand, np.float32, (ny, nx))
-        ph, dev = self._ptr(hand, np.float32, name="hand")
-        pc, cdev = self._ptr(catch, np.int32, (ny, nx), "catch")
-        pm, mdev = self._ptr(mask, np.int16, (ny, nx), "mask")
-        po, _ = self._ptr(out, np.float32, (ny, nx), "map")
-        if cdev != dev or (mask is not None and mdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
+        f = _Call(self)
+        ph = f.raster(hand, np.float32, "hand")
+        pc = f.raster(catch, np.int32, "catch")
+        pm = f.raster(mask, np.int16, "mask")
+        pdx, pdy = f.cells(dx, dy)
+        out, po = f.out(None, np.float32, "map")
         wet = np.zeros(ids.size, np.float32) if area else None
-        st = TdxStats()
-        self._sync_torch(hand, catch, mask)
-        v = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
-        check(self._pick(dev, "tdx_inundepth")(self._h, ph, pc, pm, nx, ny, float(hand_nodata), int(catch_nodata), int(mask_nodata), v(dxc), v(dyc), v(ids), v(depth),
-                                               ids.size, po, v(wet) if area else None, C.byref(st)), self._h)
-        return (out, wet, st.as_dict()) if stats else (out, wet)
+        st = f.call("tdx_inundepth", ph, pc, pm, f.nx, f.ny, float(hand_nodata), int(catch_nodata), int(mask_nodata), pdx, pdy, _v(ids), _v(depth), ids.size, po,
+                    _v(wet) if area else None)
+        return _ret((out, wet, st), stats)
 
     def gagewatershed(self, p, outlets, *, nodata=int(P_NODATA), stats=False):
         """gw, id_table = gagewatershed(p, outlets)  (src/gagewatershed.cpp:56): every cell gets the id of the first gauge downstream of it.
@@ -505,25 +343,8 @@ class Context:
         outlets: (columns, rows[, ids]) global indices (ids default to 1..n, as the outlet reader's); outlets off the raster are skipped and
         the first one on a cell wins.  gw int32, nodata -2147483647.  id_table: int32 array (k, 2) of the `-id` file's lines (id, iddown)
         for the k placed outlets in input order; iddown is -1 where the gauge's downstream neighbour is off the raster or unlabelled."""
-        ny, nx = p.shape
-        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32)).reshape(-1)
-        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32)).reshape(-1)
-        ids = np.arange(1, ox.size + 1, dtype=np.int32) if len(outlets) < 3 else np.ascontiguousarray(np.asarray(outlets[2], dtype=np.int32)).reshape(-1)
-        if ox.shape != oy.shape or ox.shape != ids.shape:
-            raise ValueError("outlets: need equal-length 1-D arrays (columns, rows[, ids])")
-        gw = self._out(p, np.int32, (ny, nx))
-        pp, dev = self._ptr(p, np.int16, name="p")
-        pg, _ = self._ptr(gw, np.int32, (ny, nx), "gw")
-        placed = np.zeros(ox.size + 1, np.int32)
-        iddown = np.zeros(ox.size + 1, np.int32)
-        st = TdxStats()
-        self._sync_torch(p)
-        check(self._pick(dev, "tdx_gagewatershed")(self._h, pp, nx, ny, int(nodata), C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data),
-                                                   C.c_void_p(ids.ctypes.data), int(ox.size), pg, C.c_void_p(placed.ctypes.data),
-                                                   C.c_void_p(iddown.ctypes.data), C.byref(st)), self._h)
-        keep = placed[:ox.size] > 0
-        table = np.stack([ids[keep], iddown[:ox.size][keep]], axis=1).astype(np.int32)
-        return (gw, table, st.as_dict()) if stats else (gw, table)
+        ids = outlets[2] if len(outlets) > 2 else np.arange(1, np.size(outlets[0]) + 1, dtype=np.int32)
+        return _ret(_gagewatershed(_Call(self), p, outlets[0], outlets[1], ids, nodata), stats)
 
     def dinfdistup(self, ang, fel=None, *, stat="ave", kind="h", weights=None, weights_nodata=-9999.0, contcheck=True, thresh=0.0, dx=1.0, dy=1.0,
                    nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), stats=False):
@@ -532,44 +353,12 @@ class Context:
         kind "h" horizontal, "v" vertical rise, "p" Pythagorean, "s" surface; stat "ave", "max" or "min" over the contributors; a
         neighbour contributes only if its proportion exceeds `thresh`.  `fel` is required for v, p and s; `weights` scale the horizontal
         steps of h, p and s (v ignores them, as the reference does).  du float32, nodata -FLT_MAX; ridge cells get 0."""
-        sm, tm = _distdown_mode(stat, kind)
-        if tm != DISTDOWN_KINDS["h"] and fel is None:
-            raise ValueError(f"kind {kind!r} needs fel")
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        du = self._out(ang, np.float32, (ny, nx))
-        use_fel = tm != DISTDOWN_KINDS["h"]
-        use_w = weights is not None and tm != DISTDOWN_KINDS["v"]
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pf, fdev = self._ptr(fel if use_fel else None, np.float32, (ny, nx), "fel")
-        pw, wdev = self._ptr(weights if use_w else None, np.float32, (ny, nx), "weights")
-        po, _ = self._ptr(du, np.float32, (ny, nx), "du")
-        if (use_fel and fdev != dev) or (use_w and wdev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ang, fel, weights)
-        check(self._pick(dev, "tdx_dinfdistup")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf,
-                                                 float(fel_nodata), pw, float(weights_nodata), sm, tm, int(bool(contcheck)), float(thresh), po,
-                                                 C.byref(st)), self._h)
-        return (du, st.as_dict()) if stats else du
+        return _ret(_dinfdistup(_Call(self), ang, fel, stat, kind, weights, weights_nodata, contcheck, thresh, dx, dy, nodata, fel_nodata), stats)
 
     def retlimflow(self, ang, wg, rc, *, dx=1.0, dy=1.0, nodata=float(ANG_NODATA), wg_nodata=-9999.0, rc_nodata=-9999.0, stats=False):
         """qrl = retlimro(ang, wg, rc)  (src/RetlimFlow.cpp:53): retention limited runoff, max(0, inflow + wg - rc) accumulated along the
         D-infinity flow.  A cell whose wg or rc is nodata has no value, and neither has anything downstream of it.  qrl float32, nodata -FLT_MAX."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        qrl = self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pw, wdev = self._ptr(wg, np.float32, (ny, nx), "wg")
-        pr, rdev = self._ptr(rc, np.float32, (ny, nx), "rc")
-        po, _ = self._ptr(qrl, np.float32, (ny, nx), "qrl")
-        if wdev != dev or rdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        st = TdxStats()
-        self._sync_torch(ang, wg, rc)
-        check(self._pick(dev, "tdx_retlimflow")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw, float(wg_nodata), pr,
-                                                 float(rc_nodata), po, C.byref(st)), self._h)
-        return (qrl, st.as_dict()) if stats else qrl
+        return _ret(_retlimflow(_Call(self), ang, wg, rc, dx, dy, nodata, wg_nodata, rc_nodata), stats)
 
     def dinfavalanche(self, ang, fel, ass, *, thresh=0.2, alpha=18.0, direct=False, dx=1.0, dy=1.0, geo=None, geographic=False, nodata=float(ANG_NODATA),
                       fel_nodata=float(FEL_NODATA), ass_nodata=-32768, stats=False):
@@ -577,71 +366,17 @@ class Context:
         angle to the source in degrees, and the distance from the source - along the flow path, or with direct=True as a straight line in
         the raster's coordinates: geo = (xleftedge, ytopedge, dlon, dlat), by default (0, ny * dy[0], dx[0], dy[0]); needed when
         geographic, where dlon / dlat are degrees.  float32, nodata -FLT_MAX."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        rz = self._out(ang, np.float32, (ny, nx))
-        dfs = self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pf, fdev = self._ptr(fel, np.float32, (ny, nx), "fel")
-        ps, sdev = self._ptr(ass, np.int16, (ny, nx), "ass")
-        pz, _ = self._ptr(rz, np.float32, (ny, nx), "rz")
-        pd, _ = self._ptr(dfs, np.float32, (ny, nx), "dfs")
-        if fdev != dev or sdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        g4 = None if geo is None else np.ascontiguousarray(np.asarray(geo, dtype=np.float64).reshape(4))
-        st = TdxStats()
-        self._sync_torch(ang, fel, ass)
-        check(self._pick(dev, "tdx_dinfavalanche")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf, float(fel_nodata),
-                                                    ps, int(ass_nodata), float(thresh), float(alpha), 0 if direct else 1,
-                                                    None if g4 is None else C.c_void_p(g4.ctypes.data), int(bool(geographic)), pz, pd, C.byref(st)), self._h)
-        return (rz, dfs, st.as_dict()) if stats else (rz, dfs)
+        return _ret(_dinfavalanche(_Call(self), ang, fel, ass, thresh, alpha, direct, dx, dy, geo, geographic, nodata, fel_nodata, ass_nodata), stats)
 
     def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=float(ANG_NODATA), dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
                          outlets=None, stats=False):
         """ctpt = dsllArea(ang, dm, dg, q)  (src/DinfConcLimAccum.cpp:61): dg int16, ctpt float32 (nodata -FLT_MAX)."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        ctpt = self._out(ang, np.float32, (ny, nx))
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        pm, mdev = self._ptr(dm, np.float32, (ny, nx), "dm")
-        pg, gdev = self._ptr(dg, np.int16, (ny, nx), "dg")
-        pq, qdev = self._ptr(q, np.float32, (ny, nx), "q")
-        po, _ = self._ptr(ctpt, np.float32, (ny, nx), "ctpt")
-        if mdev != dev or gdev != dev or qdev != dev:
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(ang, dm, dg, q)
-        check(self._pick(dev, "tdx_dinfconclimaccum")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pm, float(dm_nodata),
-                                                       pg, pq, float(q_nodata), float(csol), int(bool(contcheck)), ox, oy, no, po, C.byref(st)), self._h)
-        del keep
-        return (ctpt, st.as_dict()) if stats else ctpt
+        return _ret(_dinfconclimaccum(_Call(self), ang, dm, dg, q, csol, nodata, dm_nodata, q_nodata, dx, dy, contcheck, outlets), stats)
 
     def dinftranslimaccum(self, ang, tsup, tc, cs=None, nodata=float(ANG_NODATA), tsup_nodata=-9999.0, tc_nodata=-9999.0, cs_nodata=-9999.0, dx=1.0, dy=1.0,
                           contcheck=True, outlets=None, stats=False):
         """tla, tdep, ctpt = tlaccum(ang, tsup, tc[, cs])  (src/DinfTransLimAccum.cpp:61): float32, nodata -FLT_MAX; ctpt is None without cs."""
-        ny, nx = ang.shape
-        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
-        tla = self._out(ang, np.float32, (ny, nx))
-        dep = self._out(ang, np.float32, (ny, nx))
-        cso = self._out(ang, np.float32, (ny, nx)) if cs is not None else None
-        pa, dev = self._ptr(ang, np.float32, name="ang")
-        ps, sdev = self._ptr(tsup, np.float32, (ny, nx), "tsup")
-        pc, cdev = self._ptr(tc, np.float32, (ny, nx), "tc")
-        pi, idev = self._ptr(cs, np.float32, (ny, nx), "cs")
-        pt, _ = self._ptr(tla, np.float32, (ny, nx), "tla")
-        pd, _ = self._ptr(dep, np.float32, (ny, nx), "tdep")
-        po, _ = self._ptr(cso, np.float32, (ny, nx), "ctpt")
-        if sdev != dev or cdev != dev or (cs is not None and idev != dev):
-            raise ValueError("all rasters must be on the same side (host or device)")
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        self._sync_torch(ang, tsup, tc, cs)
-        check(self._pick(dev, "tdx_dinftranslimaccum")(self._h, pa, nx, ny, float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), ps,
-                                                        float(tsup_nodata), pc, float(tc_nodata), pi, float(cs_nodata), int(bool(contcheck)), ox, oy, no, pt, pd, po,
-                                                        C.byref(st)), self._h)
-        del keep
-        return (tla, dep, cso, st.as_dict()) if stats else (tla, dep, cso)
+        return _ret(_dinftranslimaccum(_Call(self), ang, tsup, tc, cs, nodata, tsup_nodata, tc_nodata, cs_nodata, dx, dy, contcheck, outlets), stats)
 
     def synth_dem(self, n_or_shape, seed=1234, x0=0, y0=0, base_wavelength=None, out=None):
         """Seeded fractal DEM generated on the device (torch tensor on cuda:<device>)."""
@@ -657,6 +392,209 @@ class Context:
         torch.cuda.synchronize(self.device)
         check(self._lib.tdx_synth_dem_dev(self._h, int(seed), nx, ny, int(x0), int(y0), int(base_wavelength), C.c_void_p(t.data_ptr())), self._h)
         return t
+
+
+# ---- the tools: one marshalling body each, for Context.<tool> and StripPipeline.<tool> --------------------------------------------------
+# f is the _Call frame of either; every body returns (outputs..., stats dict).  The arguments of f.call are the header's, in its order.
+def _pitremove(f, dem, nodata, mask, fourway, out):
+    pz = f.raster(dem, np.float32, "dem")
+    pm = f.raster(mask, np.int16, "mask")
+    fel, pf = f.out(out, np.float32, "fel")
+    return fel, f.call("tdx_pitremove", pz, f.nx, f.ny, float(nodata), pm, int(bool(fourway)), pf)
+
+
+def _d8flowdir(f, fel, nodata, dx, dy, want_slope, out):
+    pz = f.raster(fel, np.float32, "fel")
+    pdx, pdy = f.cells(dx, dy)
+    p, pp = f.out(out[0] if out is not None else None, np.int16, "p")
+    sd8, ps = f.out(out[1] if out is not None else None, np.float32, "sd8") if want_slope else (None, None)
+    return p, sd8, f.call("tdx_d8flowdir", pz, f.nx, f.ny, float(nodata), pdx, pdy, pp, ps)
+
+
+def _aread8(f, p, nodata, weights, weights_nodata, contcheck, outlets, out):
+    pp = f.raster(p, np.int16, "p")
+    pw = f.raster(weights, np.float32, "weights")
+    ad8, pa = f.out(out, np.float32, "ad8")
+    ox, oy, no = f.outlets(outlets)
+    return ad8, f.call("tdx_aread8", pp, f.nx, f.ny, int(nodata), pw, float(weights_nodata), int(bool(contcheck)), ox, oy, no, pa)
+
+
+def _d8flowpathextremeup(f, p, sa, nodata, usemax, contcheck, outlets, out):
+    pp = f.raster(p, np.int16, "p")
+    pa = f.raster(sa, np.float32, "sa")
+    ssa, ps = f.out(out, np.float32, "ssa")
+    ox, oy, no = f.outlets(outlets)
+    return ssa, f.call("tdx_d8flowpathextremeup", pp, f.nx, f.ny, int(nodata), pa, int(bool(usemax)), int(bool(contcheck)), ox, oy, no, ps)
+
+
+def _gridnet(f, p, nodata, dx, dy, mask, thresh, outlets):
+    pp = f.raster(p, np.int16, "p")
+    pm = f.raster(mask, np.int32, "mask")
+    pdx, pdy = f.cells(dx, dy)
+    plen, ppl = f.out(None, np.float32, "plen")
+    tlen, ptl = f.out(None, np.float32, "tlen")
+    gord, pgo = f.out(None, np.int16, "gord")
+    ox, oy, no = f.outlets(outlets)
+    return plen, tlen, gord, f.call("tdx_gridnet", pp, f.nx, f.ny, int(nodata), pdx, pdy, pm, int(thresh), ox, oy, no, ppl, ptl, pgo)
+
+
+def _dinfflowdir(f, fel, nodata, dx, dy, out):
+    pz = f.raster(fel, np.float32, "fel")
+    pdx, pdy = f.cells(dx, dy)
+    ang, pa = f.out(out[0] if out is not None else None, np.float32, "ang")
+    slp, ps = f.out(out[1] if out is not None else None, np.float32, "slp")
+    return ang, slp, f.call("tdx_dinfflowdir", pz, f.nx, f.ny, float(nodata), pdx, pdy, pa, ps)
+
+
+def _areadinf(f, ang, nodata, dx, dy, weights, contcheck, outlets, out):
+    pa = f.raster(ang, np.float32, "ang")
+    pw = f.raster(weights, np.float32, "weights")
+    pdx, pdy = f.cells(dx, dy)
+    sca, ps = f.out(out, np.float32, "sca")
+    ox, oy, no = f.outlets(outlets)
+    return sca, f.call("tdx_areadinf", pa, f.nx, f.ny, float(nodata), pdx, pdy, pw, int(bool(contcheck)), ox, oy, no, ps)
+
+
+def _dinfdecayaccum(f, ang, dm, nodata, dm_nodata, dx, dy, weights, contcheck, outlets, out):
+    pa = f.raster(ang, np.float32, "ang")
+    pd = f.raster(dm, np.float32, "dm")
+    pw = f.raster(weights, np.float32, "weights")
+    pdx, pdy = f.cells(dx, dy)
+    dsca, ps = f.out(out, np.float32, "dsca")
+    ox, oy, no = f.outlets(outlets)
+    return dsca, f.call("tdx_dinfdecayaccum", pa, f.nx, f.ny, float(nodata), pdx, pdy, pd, float(dm_nodata), pw, int(bool(contcheck)), ox, oy, no, ps)
+
+
+def _dinfupdependence(f, ang, dg, nodata, dx, dy):
+    pa = f.raster(ang, np.float32, "ang")
+    pg = f.raster(dg, np.int32, "dg")
+    pdx, pdy = f.cells(dx, dy)
+    dep, po = f.out(None, np.float32, "dep")
+    return dep, f.call("tdx_dinfupdependence", pa, f.nx, f.ny, float(nodata), pdx, pdy, pg, po)
+
+
+def _dinfrevaccum(f, ang, w, nodata, w_nodata, dx, dy):
+    pa = f.raster(ang, np.float32, "ang")
+    pw = f.raster(w, np.float32, "w")
+    pdx, pdy = f.cells(dx, dy)
+    racc, pr = f.out(None, np.float32, "racc")
+    dmax, pm = f.out(None, np.float32, "dmax")
+    return racc, dmax, f.call("tdx_dinfrevaccum", pa, f.nx, f.ny, float(nodata), pdx, pdy, pw, float(w_nodata), pr, pm)
+
+
+def _dinfdistdown(f, ang, src, fel, stat, kind, weights, weights_nodata, contcheck, dx, dy, nodata, fel_nodata):
+    sm, tm, fel, weights = _distdown_mode(stat, kind, fel, weights)
+    pa = f.raster(ang, np.float32, "ang")
+    ps = f.raster(src, np.int16, "src")
+    pf = f.raster(fel, np.float32, "fel")
+    pw = f.raster(weights, np.float32, "weights")
+    pdx, pdy = f.cells(dx, dy)
+    dd, po = f.out(None, np.float32, "dd")
+    return dd, f.call("tdx_dinfdistdown", pa, f.nx, f.ny, float(nodata), pdx, pdy, pf, float(fel_nodata), ps, pw, float(weights_nodata), sm, tm,
+                      int(bool(contcheck)), po)
+
+
+def _dinfdistup(f, ang, fel, stat, kind, weights, weights_nodata, contcheck, thresh, dx, dy, nodata, fel_nodata):
+    sm, tm, fel, weights = _distdown_mode(stat, kind, fel, weights)
+    pa = f.raster(ang, np.float32, "ang")
+    pf = f.raster(fel, np.float32, "fel")
+    pw = f.raster(weights, np.float32, "weights")
+    pdx, pdy = f.cells(dx, dy)
+    du, po = f.out(None, np.float32, "du")
+    return du, f.call("tdx_dinfdistup", pa, f.nx, f.ny, float(nodata), pdx, pdy, pf, float(fel_nodata), pw, float(weights_nodata), sm, tm,
+                      int(bool(contcheck)), float(thresh), po)
+
+
+def _d8hdisttostrm(f, p, src, thresh, dx, dy, nodata, src_nodata):
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    pdx, pdy = f.cells(dx, dy)
+    dist, po = f.out(None, np.float32, "dist")
+    return dist, f.call("tdx_d8hdisttostrm", pp, f.nx, f.ny, int(nodata), ps, int(src_nodata), int(thresh), pdx, pdy, po)
+
+
+def _d8vdisttostrm(f, p, fel, src, thresh, nodata, src_nodata):
+    pp = f.raster(p, np.int16, "p")
+    pf = f.raster(fel, np.float32, "fel")
+    ps = f.raster(src, np.int32, "src")
+    dist, po = f.out(None, np.float32, "dist")
+    return dist, f.call("tdx_d8vdisttostrm", pp, f.nx, f.ny, int(nodata), pf, ps, int(src_nodata), int(thresh), po)
+
+
+def _flowdircond(f, p, z, nodata, z_nodata):
+    pp = f.raster(p, np.int16, "p")
+    pz = f.raster(z, np.float32, "z")
+    zfdc, po = f.out(None, np.float32, "zfdc")
+    return zfdc, f.call("tdx_flowdircond", pp, f.nx, f.ny, int(nodata), pz, float(z_nodata), po)
+
+
+def _slopeavedown(f, p, fel, dn, niter, dx, dy, nodata, fel_nodata):
+    pp = f.raster(p, np.int16, "p")
+    pf = f.raster(fel, np.float32, "fel")
+    pdx, pdy = f.cells(dx, dy)
+    slpd, po = f.out(None, np.float32, "slpd")
+    return slpd, f.call("tdx_slopeavedown", pp, f.nx, f.ny, int(nodata), pf, float(fel_nodata), pdx, pdy, float(dn), niter, po)
+
+
+def _gagewatershed(f, p, cols, rows, ids, nodata):
+    ox, oy, ids = _flat(cols, np.int32), _flat(rows, np.int32), _flat(ids, np.int32)
+    if ox.shape != oy.shape or ox.shape != ids.shape:
+        raise ValueError("outlets: need equal-length 1-D arrays (columns, rows[, ids])")
+    pp = f.raster(p, np.int16, "p")
+    gw, pg = f.out(None, np.int32, "gw")
+    placed = np.zeros(ox.size + 1, np.int32)
+    iddown = np.zeros(ox.size + 1, np.int32)
+    st = f.call("tdx_gagewatershed", pp, f.nx, f.ny, int(nodata), _v(ox), _v(oy), _v(ids), int(ox.size), pg, _v(placed), _v(iddown))
+    keep = placed[:ox.size] > 0
+    return gw, np.stack([ids[keep], iddown[:ox.size][keep]], axis=1).astype(np.int32), st
+
+
+def _retlimflow(f, ang, wg, rc, dx, dy, nodata, wg_nodata, rc_nodata):
+    pa = f.raster(ang, np.float32, "ang")
+    pw = f.raster(wg, np.float32, "wg")
+    pr = f.raster(rc, np.float32, "rc")
+    pdx, pdy = f.cells(dx, dy)
+    qrl, po = f.out(None, np.float32, "qrl")
+    return qrl, f.call("tdx_retlimflow", pa, f.nx, f.ny, float(nodata), pdx, pdy, pw, float(wg_nodata), pr, float(rc_nodata), po)
+
+
+def _dinfavalanche(f, ang, fel, ass, thresh, alpha, direct, dx, dy, geo, geographic, nodata, fel_nodata, ass_nodata, whole=()):
+    """whole: (row0, ny_total), where a strip lies in the whole raster - the two arguments only tdx_dinfavalanche_strip has."""
+    pa = f.raster(ang, np.float32, "ang")
+    pf = f.raster(fel, np.float32, "fel")
+    ps = f.raster(ass, np.int16, "ass")
+    pdx, pdy = f.cells(dx, dy)
+    rz, pz = f.out(None, np.float32, "rz")
+    dfs, pd = f.out(None, np.float32, "dfs")
+    g4 = None if geo is None else np.ascontiguousarray(np.asarray(geo, dtype=np.float64).reshape(4))
+    return rz, dfs, f.call("tdx_dinfavalanche", pa, f.nx, f.ny, float(nodata), pdx, pdy, pf, float(fel_nodata), ps, int(ass_nodata), float(thresh), float(alpha),
+                           0 if direct else 1, None if g4 is None else _v(g4), int(bool(geographic)), *whole, pz, pd)
+
+
+def _dinfconclimaccum(f, ang, dm, dg, q, csol, nodata, dm_nodata, q_nodata, dx, dy, contcheck, outlets):
+    pa = f.raster(ang, np.float32, "ang")
+    pm = f.raster(dm, np.float32, "dm")
+    pg = f.raster(dg, np.int16, "dg")
+    pq = f.raster(q, np.float32, "q")
+    pdx, pdy = f.cells(dx, dy)
+    ctpt, po = f.out(None, np.float32, "ctpt")
+    ox, oy, no = f.outlets(outlets)
+    return ctpt, f.call("tdx_dinfconclimaccum", pa, f.nx, f.ny, float(nodata), pdx, pdy, pm, float(dm_nodata), pg, pq, float(q_nodata), float(csol),
+                        int(bool(contcheck)), ox, oy, no, po)
+
+
+def _dinftranslimaccum(f, ang, tsup, tc, cs, nodata, tsup_nodata, tc_nodata, cs_nodata, dx, dy, contcheck, outlets):
+    pa = f.raster(ang, np.float32, "ang")
+    ps = f.raster(tsup, np.float32, "tsup")
+    pc = f.raster(tc, np.float32, "tc")
+    pi = f.raster(cs, np.float32, "cs")
+    pdx, pdy = f.cells(dx, dy)
+    tla, pt = f.out(None, np.float32, "tla")
+    tdep, pd = f.out(None, np.float32, "tdep")
+    ctpt, po = f.out(None, np.float32, "ctpt") if cs is not None else (None, None)
+    ox, oy, no = f.outlets(outlets)
+    return tla, tdep, ctpt, f.call("tdx_dinftranslimaccum", pa, f.nx, f.ny, float(nodata), pdx, pdy, ps, float(tsup_nodata), pc, float(tc_nodata), pi,
+                                   float(cs_nodata), int(bool(contcheck)), ox, oy, no, pt, pd, po)
 
 
 def catchhydrogeo(hand, catch, slp, ids, stages, device=0, **kw):

@@ -13,8 +13,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import TdxStats, check
+from . import _lib, api
+from ._lib import check
+from .api import ANG_NODATA, FEL_NODATA, P_NODATA
 
 
 def partition_rows(ny: int, size: int):
@@ -204,8 +205,6 @@ class StripGroup:
     bench.py's functional many-strips-on-one-GPU runs."""
 
     def __init__(self, size: int, nx: int, devices=None):
-        from .api import Context
-
         self._lib = _lib.load()
         self.size, self.nx = int(size), int(nx)
         devs = list(devices) if devices is not None else [0] * self.size
@@ -214,7 +213,7 @@ class StripGroup:
         check(self._lib.tdx_group_create(self.size, arr, self.nx, C.byref(g)))
         self._g = g
         self.transport = self._lib.tdx_group_transport(g).decode()
-        self.contexts = [Context.borrow(self._lib.tdx_group_context(g, r), devs[r]) for r in range(self.size)]
+        self.contexts = [api.Context.borrow(self._lib.tdx_group_context(g, r), devs[r]) for r in range(self.size)]
         self.comms = [_GroupComm(C.c_void_p(self._lib.tdx_group_comm(g, r)), self.transport) for r in range(self.size)]
 
     def run(self, fn):
@@ -294,17 +293,11 @@ def project_critical_path(logs, exchange_us: float = 10.0, vote_us: float = 30.0
                         "note": "projection from one-GPU segment traces (one rank on the device at a time), not an N-GPU measurement"}}
 
 
-def _tptr(t, dtype, shape, name):
-    import torch
-
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: need a contiguous CUDA tensor {dtype} of shape {tuple(shape)}")
-    return C.c_void_p(t.data_ptr())
-
-
 class StripPipeline:
-    """PitRemove -> D8FlowDir -> AreaD8 on one strip of a row-partitioned raster.  All rasters are CUDA
-    tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains."""
+    """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
+    tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
+    runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes
+    dx / dy as scalars or one value per row of the strip array (strip_rows()), and returns (outputs..., stats dict)."""
 
     def __init__(self, ctx, comm: StripComm | None, nx: int, ny_local: int):
         import torch
@@ -317,333 +310,100 @@ class StripPipeline:
     def empty(self, dtype):
         return self.torch.empty(self.shape, dtype=dtype, device=f"cuda:{self.ctx.device}")
 
-    def pitremove(self, dem, nodata=-9999.0, fourway=False, out=None):
-        torch = self.torch
-        fel = out if out is not None else self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_pitremove_strip(self.ctx._h, self._cp, _tptr(dem, torch.float32, self.shape, "dem"), self.nx, self.ny_local,
-                                                float(nodata), None, int(bool(fourway)), _tptr(fel, torch.float32, self.shape, "fel"), C.byref(st)),
-              self.ctx._h)
-        return fel, st.as_dict()
-
-    def d8flowdir(self, fel, nodata=-3.0e38, dx=1.0, dy=1.0, out=None):
-        torch = self.torch
-        rows = self.ny_local + 2
-        dxc = np.ascontiguousarray(np.broadcast_to(np.asarray(dx, dtype=np.float64), (rows,)))
-        dyc = np.ascontiguousarray(np.broadcast_to(np.asarray(dy, dtype=np.float64), (rows,)))
-        p = out[0] if out is not None else self.empty(torch.int16)
-        sd8 = out[1] if out is not None else self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_d8flowdir_strip(self.ctx._h, self._cp, _tptr(fel, torch.float32, self.shape, "fel"), self.nx, self.ny_local,
-                                                float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                _tptr(p, torch.int16, self.shape, "p"), _tptr(sd8, torch.float32, self.shape, "sd8"), C.byref(st)),
-              self.ctx._h)
-        return p, sd8, st.as_dict()
-
-    @staticmethod
-    def _outlets(outlets):
-        """(columns, STRIP-ARRAY rows) -> ctypes pointers; None = no outlets."""
-        if outlets is None:
-            return None, None, -1, ()
-        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32))
-        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32))
-        return C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data), int(ox.size), (ox, oy)
-
     def local_outlets(self, cols, global_rows, y0):
         """Global (column, row) outlet indices -> strip-array coordinates of the strip that starts at global row y0."""
         return np.asarray(cols, dtype=np.int32), (np.asarray(global_rows, dtype=np.int64) - int(y0) + 1).astype(np.int32)
 
-    def aread8(self, p, nodata=-32768, weights=None, weights_nodata=-9999.0, contcheck=True, outlets=None, out=None):
-        torch = self.torch
-        ad8 = out if out is not None else self.empty(torch.float32)
-        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None else None
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_aread8_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata), pw,
-                                             float(weights_nodata), int(bool(contcheck)), ox, oy, no, _tptr(ad8, torch.float32, self.shape, "ad8"),
-                                             C.byref(st)), self.ctx._h)
-        del keep
-        return ad8, st.as_dict()
+    def _call(self):
+        return api._Call(self.ctx, self.shape, self._cp)
 
-    def _cells(self, dx, dy):
-        rows = self.ny_local + 2
-        dxc = np.ascontiguousarray(np.broadcast_to(np.asarray(dx, dtype=np.float64), (rows,)))
-        dyc = np.ascontiguousarray(np.broadcast_to(np.asarray(dy, dtype=np.float64), (rows,)))
-        return dxc, dyc
+    def pitremove(self, dem, nodata=-9999.0, fourway=False, out=None):
+        return api._pitremove(self._call(), dem, nodata, None, fourway, out)
 
-    def dinfflowdir(self, fel, nodata=-3.0e38, dx=1.0, dy=1.0, out=None):
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        ang = out[0] if out is not None else self.empty(torch.float32)
-        slp = out[1] if out is not None else self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfflowdir_strip(self.ctx._h, self._cp, _tptr(fel, torch.float32, self.shape, "fel"), self.nx, self.ny_local,
-                                                  float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                  _tptr(ang, torch.float32, self.shape, "ang"), _tptr(slp, torch.float32, self.shape, "slp"), C.byref(st)),
-              self.ctx._h)
-        return ang, slp, st.as_dict()
+    def d8flowdir(self, fel, nodata=float(FEL_NODATA), dx=1.0, dy=1.0, out=None):
+        return api._d8flowdir(self._call(), fel, nodata, dx, dy, True, out)
 
-    def areadinf(self, ang, nodata=-3.402823466e38, dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        sca = out if out is not None else self.empty(torch.float32)
-        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None else None
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_areadinf_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                               C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pw, int(bool(contcheck)), ox, oy, no,
-                                               _tptr(sca, torch.float32, self.shape, "sca"), C.byref(st)), self.ctx._h)
-        del keep
-        return sca, st.as_dict()
+    def aread8(self, p, nodata=int(P_NODATA), weights=None, weights_nodata=-9999.0, contcheck=True, outlets=None, out=None):
+        """outlets: (columns, STRIP-ARRAY rows) (local_outlets()); None = no outlets."""
+        return api._aread8(self._call(), p, nodata, weights, weights_nodata, contcheck, outlets, out)
 
-    def dinfupdependence(self, ang, dg, nodata=-3.402823466e38, dx=1.0, dy=1.0):
+    def dinfflowdir(self, fel, nodata=float(FEL_NODATA), dx=1.0, dy=1.0, out=None):
+        return api._dinfflowdir(self._call(), fel, nodata, dx, dy, out)
+
+    def areadinf(self, ang, nodata=float(ANG_NODATA), dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
+        return api._areadinf(self._call(), ang, nodata, dx, dy, weights, contcheck, outlets, out)
+
+    def dinfupdependence(self, ang, dg, nodata=float(ANG_NODATA), dx=1.0, dy=1.0):
         """dep = depgrd(ang, dg) on this strip (src/DinfUpDependence.cpp:52): dg int32, dep float32 (nodata -1)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        dep = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfupdependence_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                       C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(dg, torch.int32, self.shape, "dg"),
-                                                       _tptr(dep, torch.float32, self.shape, "dep"), C.byref(st)), self.ctx._h)
-        return dep, st.as_dict()
+        return api._dinfupdependence(self._call(), ang, dg, nodata, dx, dy)
 
-    def dinfrevaccum(self, ang, w, nodata=-3.402823466e38, w_nodata=-9999.0, dx=1.0, dy=1.0):
+    def dinfrevaccum(self, ang, w, nodata=float(ANG_NODATA), w_nodata=-9999.0, dx=1.0, dy=1.0):
         """racc, dmax = dsaccum(ang, w) on this strip (src/DinfRevAccum.cpp:51)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        racc, dmax = self.empty(torch.float32), self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfrevaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                   C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(w, torch.float32, self.shape, "w"), float(w_nodata),
-                                                   _tptr(racc, torch.float32, self.shape, "racc"), _tptr(dmax, torch.float32, self.shape, "dmax"), C.byref(st)), self.ctx._h)
-        return racc, dmax, st.as_dict()
+        return api._dinfrevaccum(self._call(), ang, w, nodata, w_nodata, dx, dy)
 
     def dinfdistdown(self, ang, src, fel=None, *, stat="ave", kind="v", weights=None, weights_nodata=-9999.0, contcheck=True, dx=1.0, dy=1.0,
-                     nodata=-3.402823466e38, fel_nodata=-3.0e38):
+                     nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA)):
         """dd = dinfdistdown(ang, fel, src, w) on this strip (src/DinfDistDown.cpp:66): src int16, dd float32 (nodata -FLT_MAX)."""
-        from .api import DISTDOWN_KINDS, _distdown_mode
-
-        torch = self.torch
-        sm, tm = _distdown_mode(stat, kind)
-        if tm != DISTDOWN_KINDS["h"] and fel is None:
-            raise ValueError(f"kind {kind!r} needs fel")
-        dxc, dyc = self._cells(dx, dy)
-        dd = self.empty(torch.float32)
-        pf = _tptr(fel, torch.float32, self.shape, "fel") if tm != DISTDOWN_KINDS["h"] else None
-        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None and tm != DISTDOWN_KINDS["v"] else None
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfdistdown_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                   C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf, float(fel_nodata),
-                                                   _tptr(src, torch.int16, self.shape, "src"), pw, float(weights_nodata), sm, tm, int(bool(contcheck)),
-                                                   _tptr(dd, torch.float32, self.shape, "dd"), C.byref(st)), self.ctx._h)
-        return dd, st.as_dict()
+        return api._dinfdistdown(self._call(), ang, src, fel, stat, kind, weights, weights_nodata, contcheck, dx, dy, nodata, fel_nodata)
 
     def dinfdistup(self, ang, fel=None, *, stat="ave", kind="h", weights=None, weights_nodata=-9999.0, contcheck=True, thresh=0.0, dx=1.0, dy=1.0,
-                   nodata=-3.402823466e38, fel_nodata=-3.0e38):
+                   nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA)):
         """du = dinfdistup(ang, fel, w) on this strip (src/DinfDistUp.cpp:65): du float32 (nodata -FLT_MAX)."""
-        from .api import DISTDOWN_KINDS, _distdown_mode
+        return api._dinfdistup(self._call(), ang, fel, stat, kind, weights, weights_nodata, contcheck, thresh, dx, dy, nodata, fel_nodata)
 
-        torch = self.torch
-        sm, tm = _distdown_mode(stat, kind)
-        if tm != DISTDOWN_KINDS["h"] and fel is None:
-            raise ValueError(f"kind {kind!r} needs fel")
-        dxc, dyc = self._cells(dx, dy)
-        du = self.empty(torch.float32)
-        pf = _tptr(fel, torch.float32, self.shape, "fel") if tm != DISTDOWN_KINDS["h"] else None
-        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None and tm != DISTDOWN_KINDS["v"] else None
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfdistup_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                 C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pf, float(fel_nodata), pw, float(weights_nodata),
-                                                 sm, tm, int(bool(contcheck)), float(thresh), _tptr(du, torch.float32, self.shape, "du"), C.byref(st)), self.ctx._h)
-        return du, st.as_dict()
-
-    def retlimflow(self, ang, wg, rc, *, dx=1.0, dy=1.0, nodata=-3.402823466e38, wg_nodata=-9999.0, rc_nodata=-9999.0):
+    def retlimflow(self, ang, wg, rc, *, dx=1.0, dy=1.0, nodata=float(ANG_NODATA), wg_nodata=-9999.0, rc_nodata=-9999.0):
         """qrl = retlimro(ang, wg, rc) on this strip (src/RetlimFlow.cpp:53): qrl float32 (nodata -FLT_MAX)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        qrl = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_retlimflow_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                 C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(wg, torch.float32, self.shape, "wg"), float(wg_nodata),
-                                                 _tptr(rc, torch.float32, self.shape, "rc"), float(rc_nodata), _tptr(qrl, torch.float32, self.shape, "qrl"), C.byref(st)),
-              self.ctx._h)
-        return qrl, st.as_dict()
+        return api._retlimflow(self._call(), ang, wg, rc, dx, dy, nodata, wg_nodata, rc_nodata)
 
     def dinfavalanche(self, ang, fel, ass, *, row0, ny_total, thresh=0.2, alpha=18.0, direct=False, dx=1.0, dy=1.0, geo=None, geographic=False,
-                      nodata=-3.402823466e38, fel_nodata=-3.0e38, ass_nodata=-32768):
+                      nodata=float(ANG_NODATA), fel_nodata=float(FEL_NODATA), ass_nodata=-32768):
         """rz, dfs = avalancherunoutgrd(ang, fel, ass) on this strip (src/DinfAvalanche.cpp:62).  row0: global row of the strip's first owned row,
         ny_total: rows of the whole raster; geo = (xleftedge, ytopedge, dlon, dlat) of the WHOLE raster (direct mode)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        rz, dfs = self.empty(torch.float32), self.empty(torch.float32)
-        g4 = None if geo is None else np.ascontiguousarray(np.asarray(geo, dtype=np.float64).reshape(4))
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfavalanche_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                    C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(fel, torch.float32, self.shape, "fel"),
-                                                    float(fel_nodata), _tptr(ass, torch.int16, self.shape, "ass"), int(ass_nodata), float(thresh), float(alpha),
-                                                    0 if direct else 1, None if g4 is None else C.c_void_p(g4.ctypes.data), int(bool(geographic)), int(row0),
-                                                    int(ny_total), _tptr(rz, torch.float32, self.shape, "rz"), _tptr(dfs, torch.float32, self.shape, "dfs"),
-                                                    C.byref(st)), self.ctx._h)
-        return rz, dfs, st.as_dict()
+        return api._dinfavalanche(self._call(), ang, fel, ass, thresh, alpha, direct, dx, dy, geo, geographic, nodata, fel_nodata, ass_nodata,
+                                  whole=(int(row0), int(ny_total)))
 
-    def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=-32768, src_nodata=-2147483647):
+    def d8hdisttostrm(self, p, src, thresh=1, *, dx=1.0, dy=1.0, nodata=int(P_NODATA), src_nodata=-2147483647):
         """dist = distgrid(p, src) on this strip (src/D8HDistToStrm.cpp:57): src int32, dist float32 (nodata -FLT_MAX)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        dist = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_d8hdisttostrm_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                    _tptr(src, torch.int32, self.shape, "src"), int(src_nodata), int(thresh), C.c_void_p(dxc.ctypes.data),
-                                                    C.c_void_p(dyc.ctypes.data), _tptr(dist, torch.float32, self.shape, "dist"), C.byref(st)), self.ctx._h)
-        return dist, st.as_dict()
+        return api._d8hdisttostrm(self._call(), p, src, thresh, dx, dy, nodata, src_nodata)
 
-    def d8vdisttostrm(self, p, fel, src, thresh=1, *, nodata=-32768, src_nodata=-2147483647):
+    def d8vdisttostrm(self, p, fel, src, thresh=1, *, nodata=int(P_NODATA), src_nodata=-2147483647):
         """dist = d8vdistdown(p, fel, src) on this strip (src/D8VDistToStrm.cpp:58).  fel's halo rows are exchanged (written) by the call."""
-        torch = self.torch
-        dist = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_d8vdisttostrm_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                    _tptr(fel, torch.float32, self.shape, "fel"), _tptr(src, torch.int32, self.shape, "src"), int(src_nodata),
-                                                    int(thresh), _tptr(dist, torch.float32, self.shape, "dist"), C.byref(st)), self.ctx._h)
-        return dist, st.as_dict()
+        return api._d8vdisttostrm(self._call(), p, fel, src, thresh, nodata, src_nodata)
 
-    def flowdircond(self, p, z, *, nodata=-32768, z_nodata=-3.0e38):
+    def flowdircond(self, p, z, *, nodata=int(P_NODATA), z_nodata=float(FEL_NODATA)):
         """zfdc = flowdircond(p, z) on this strip (src/flowdircond.cpp:54)."""
-        torch = self.torch
-        out = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_flowdircond_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                  _tptr(z, torch.float32, self.shape, "z"), float(z_nodata), _tptr(out, torch.float32, self.shape, "zfdc"),
-                                                  C.byref(st)), self.ctx._h)
-        return out, st.as_dict()
+        return api._flowdircond(self._call(), p, z, nodata, z_nodata)
 
-    def slopeavedown(self, p, fel, dn, niter, *, dx=1.0, dy=1.0, nodata=-32768, fel_nodata=-3.0e38):
+    def slopeavedown(self, p, fel, dn, niter, *, dx=1.0, dy=1.0, nodata=int(P_NODATA), fel_nodata=float(FEL_NODATA)):
         """slpd = sloped(p, fel, dn) on this strip (src/SlopeAveDown.cpp:59).  niter: the pass count of the WHOLE raster
         (int(dn / min(dx, dy) of its middle row) + 1); the record halo rows are exchanged after every pass."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        out = self.empty(torch.float32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_slopeavedown_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                   _tptr(fel, torch.float32, self.shape, "fel"), float(fel_nodata), C.c_void_p(dxc.ctypes.data),
-                                                   C.c_void_p(dyc.ctypes.data), float(dn), int(niter), _tptr(out, torch.float32, self.shape, "slpd"), C.byref(st)),
-              self.ctx._h)
-        return out, st.as_dict()
+        return api._slopeavedown(self._call(), p, fel, dn, int(niter), dx, dy, nodata, fel_nodata)
 
-    def gagewatershed(self, p, outlets, *, nodata=-32768):
+    def gagewatershed(self, p, outlets, *, nodata=int(P_NODATA)):
         """gw, id_table = gagewatershed(p, outlets) on this strip (src/gagewatershed.cpp:56).  outlets: (columns, STRIP-ARRAY rows, ids) of ALL
         outlets (local_outlets(); those outside the owned rows are other ranks'); id_table as Context.gagewatershed's, the same on every rank."""
-        torch = self.torch
-        ox = np.ascontiguousarray(np.asarray(outlets[0], dtype=np.int32)).reshape(-1)
-        oy = np.ascontiguousarray(np.asarray(outlets[1], dtype=np.int32)).reshape(-1)
-        ids = np.ascontiguousarray(np.asarray(outlets[2], dtype=np.int32)).reshape(-1)
-        gw = self.empty(torch.int32)
-        placed = np.zeros(ox.size + 1, np.int32)
-        iddown = np.zeros(ox.size + 1, np.int32)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_gagewatershed_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                    C.c_void_p(ox.ctypes.data), C.c_void_p(oy.ctypes.data), C.c_void_p(ids.ctypes.data), int(ox.size),
-                                                    _tptr(gw, torch.int32, self.shape, "gw"), C.c_void_p(placed.ctypes.data), C.c_void_p(iddown.ctypes.data),
-                                                    C.byref(st)), self.ctx._h)
-        keep = placed[:ox.size] > 0
-        return gw, np.stack([ids[keep], iddown[:ox.size][keep]], axis=1).astype(np.int32), st.as_dict()
+        return api._gagewatershed(self._call(), p, outlets[0], outlets[1], outlets[2], nodata)
 
-    def dinfdecayaccum(self, ang, dm, nodata=-3.402823466e38, dm_nodata=-9999.0, dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        dsca = out if out is not None else self.empty(torch.float32)
-        pw = _tptr(weights, torch.float32, self.shape, "weights") if weights is not None else None
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfdecayaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local,
-                                                     float(nodata), C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data),
-                                                     _tptr(dm, torch.float32, self.shape, "dm"), float(dm_nodata), pw, int(bool(contcheck)), ox, oy, no,
-                                                     _tptr(dsca, torch.float32, self.shape, "dsca"), C.byref(st)), self.ctx._h)
-        del keep
-        return dsca, st.as_dict()
+    def dinfdecayaccum(self, ang, dm, nodata=float(ANG_NODATA), dm_nodata=-9999.0, dx=1.0, dy=1.0, weights=None, contcheck=True, outlets=None, out=None):
+        return api._dinfdecayaccum(self._call(), ang, dm, nodata, dm_nodata, dx, dy, weights, contcheck, outlets, out)
 
-    def d8flowpathextremeup(self, p, sa, nodata=-32768, usemax=True, contcheck=True, outlets=None):
+    def d8flowpathextremeup(self, p, sa, nodata=int(P_NODATA), usemax=True, contcheck=True, outlets=None):
         """ssa = d8flowpathextremeup(p, sa) on this strip (src/D8flowpathextremeup.cpp:58): sa float32, ssa float32 (nodata -FLT_MAX).
         outlets: (columns, STRIP-ARRAY rows) as for aread8."""
-        torch = self.torch
-        ssa = self.empty(torch.float32)
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_d8flowpathextremeup_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                                          _tptr(sa, torch.float32, self.shape, "sa"), int(bool(usemax)), int(bool(contcheck)), ox, oy, no,
-                                                          _tptr(ssa, torch.float32, self.shape, "ssa"), C.byref(st)), self.ctx._h)
-        del keep
-        return ssa, st.as_dict()
+        return api._d8flowpathextremeup(self._call(), p, sa, nodata, usemax, contcheck, outlets, None)
 
-    def gridnet(self, p, nodata=-32768, dx=1.0, dy=1.0, mask=None, thresh=0, outlets=None):
+    def gridnet(self, p, nodata=int(P_NODATA), dx=1.0, dy=1.0, mask=None, thresh=0, outlets=None):
         """plen, tlen, gord = gridnet(p) on this strip (src/gridnet.cpp:54): mask an optional int32 strip array (the library fills its halo
         rows); outlets: (columns, STRIP-ARRAY rows) as for aread8."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        plen, tlen, gord = self.empty(torch.float32), self.empty(torch.float32), self.empty(torch.int16)
-        pm = _tptr(mask, torch.int32, self.shape, "mask") if mask is not None else None
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_gridnet_strip(self.ctx._h, self._cp, _tptr(p, torch.int16, self.shape, "p"), self.nx, self.ny_local, int(nodata),
-                                              C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), pm, int(thresh), ox, oy, no,
-                                              _tptr(plen, torch.float32, self.shape, "plen"), _tptr(tlen, torch.float32, self.shape, "tlen"),
-                                              _tptr(gord, torch.int16, self.shape, "gord"), C.byref(st)), self.ctx._h)
-        del keep
-        return plen, tlen, gord, st.as_dict()
+        return api._gridnet(self._call(), p, nodata, dx, dy, mask, thresh, outlets)
 
-    def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=-3.402823466e38, dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
+    def dinfconclimaccum(self, ang, dm, dg, q, csol=1.0, nodata=float(ANG_NODATA), dm_nodata=-9999.0, q_nodata=-9999.0, dx=1.0, dy=1.0, contcheck=True,
                          outlets=None):
         """ctpt = dsllArea(ang, dm, dg, q) on this strip (src/DinfConcLimAccum.cpp:61): dg int16, ctpt float32 (nodata -FLT_MAX)."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        ctpt = self.empty(torch.float32)
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinfconclimaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                       C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(dm, torch.float32, self.shape, "dm"),
-                                                       float(dm_nodata), _tptr(dg, torch.int16, self.shape, "dg"), _tptr(q, torch.float32, self.shape, "q"),
-                                                       float(q_nodata), float(csol), int(bool(contcheck)), ox, oy, no,
-                                                       _tptr(ctpt, torch.float32, self.shape, "ctpt"), C.byref(st)), self.ctx._h)
-        del keep
-        return ctpt, st.as_dict()
+        return api._dinfconclimaccum(self._call(), ang, dm, dg, q, csol, nodata, dm_nodata, q_nodata, dx, dy, contcheck, outlets)
 
-    def dinftranslimaccum(self, ang, tsup, tc, cs=None, nodata=-3.402823466e38, tsup_nodata=-9999.0, tc_nodata=-9999.0, cs_nodata=-9999.0, dx=1.0, dy=1.0,
+    def dinftranslimaccum(self, ang, tsup, tc, cs=None, nodata=float(ANG_NODATA), tsup_nodata=-9999.0, tc_nodata=-9999.0, cs_nodata=-9999.0, dx=1.0, dy=1.0,
                           contcheck=True, outlets=None):
         """tla, tdep, ctpt = tlaccum(ang, tsup, tc[, cs]) on this strip (src/DinfTransLimAccum.cpp:61): float32, nodata -FLT_MAX; ctpt is None
         without cs."""
-        torch = self.torch
-        dxc, dyc = self._cells(dx, dy)
-        tla, tdep = self.empty(torch.float32), self.empty(torch.float32)
-        ctpt = self.empty(torch.float32) if cs is not None else None
-        pc = _tptr(cs, torch.float32, self.shape, "cs") if cs is not None else None
-        po = _tptr(ctpt, torch.float32, self.shape, "ctpt") if cs is not None else None
-        ox, oy, no, keep = self._outlets(outlets)
-        st = TdxStats()
-        torch.cuda.synchronize(self.ctx.device)
-        check(self.ctx._lib.tdx_dinftranslimaccum_strip(self.ctx._h, self._cp, _tptr(ang, torch.float32, self.shape, "ang"), self.nx, self.ny_local, float(nodata),
-                                                        C.c_void_p(dxc.ctypes.data), C.c_void_p(dyc.ctypes.data), _tptr(tsup, torch.float32, self.shape, "tsup"),
-                                                        float(tsup_nodata), _tptr(tc, torch.float32, self.shape, "tc"), float(tc_nodata), pc, float(cs_nodata),
-                                                        int(bool(contcheck)), ox, oy, no, _tptr(tla, torch.float32, self.shape, "tla"),
-                                                        _tptr(tdep, torch.float32, self.shape, "tdep"), po, C.byref(st)), self.ctx._h)
-        del keep
-        return tla, tdep, ctpt, st.as_dict()
+        return api._dinftranslimaccum(self._call(), ang, tsup, tc, cs, nodata, tsup_nodata, tc_nodata, cs_nodata, dx, dy, contcheck, outlets)
