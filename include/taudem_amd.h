@@ -646,6 +646,10 @@ int tdx_tool_set_device(int device);
  * TAUDEM_AMD_GPUS; the command-line tools take --gpus N).  Replaces `mpiexec -n P` (src/linearpart.h:133-134). */
 int tdx_tool_set_gpus(int ngpus);
 
+/* DropAnalysis (compute entry points, table function and file-level tool function): declared in a header of its own, which this one includes, so that
+ * every program that includes taudem_amd.h sees them */
+#include "taudem_amd_dropan.h"
+
 #ifdef __cplusplus
 }
 #endif

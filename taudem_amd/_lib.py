@@ -246,6 +246,20 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_dropan.h declares, the extension header that taudem_amd.h includes
+_DROPAN_SIGNATURES = {
+    # DropAnalysis: ctx, ad8, p, fel, ssa, nx, ny, p_nodata, ssa_nodata, dxc, dyc, dxA, dyA, outlet_x, outlet_y, n_outlets, thresh_min, thresh_max, nthresh, steptype,
+    # grid_th, order, elevout, thresh, n1, n2, sums, length, total_area, optimum, found, table, table_cap, stats.  The strip form has the comm after the context, no dxA / dyA,
+    # and outlet_term in the place of total_area ... table_cap.
+    "tdx_dropanalysis": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I16, _F, _P, _P, _D, _D, _P, _P, _I64, _F, _F, _I64, _INT, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "tdx_dropanalysis_dev": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I16, _F, _P, _P, _D, _D, _P, _P, _I64, _F, _F, _I64, _INT, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "tdx_dropanalysis_strip": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I16, _F, _P, _P, _P, _P, _I64, _F, _F, _I64, _INT, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # nthresh, thresh, n1, n2, s1, s1sq, s2, s2sq, length, total_area, table, table_cap, console, console_cap, optimum, found
+    "tdx_dropanalysis_table": (C.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I64, _P, _I64, _P, _P]),
+    "tdx_tool_dropanalysis": (C.c_int, [C.c_char_p] * 7 + [C.c_int, C.c_int, _F, _F, C.c_int, C.c_int, _P]),
+}
+DROPAN_SYMBOLS = tuple(_DROPAN_SIGNATURES)
+
 _lib = None
 
 
@@ -269,7 +283,7 @@ def load():
     except Exception:  # pragma: no cover - torch-less hosts use the system ROCm runtime
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -148,7 +148,25 @@ def _ret(res, stats):
     return res if stats else res[0] if len(res) == 2 else res[:-1]
 
 
-class Context:
+class _DropAnalysisStage:
+    """Context.dropanalysis.  Unlike the raster stages it returns per-threshold arrays, a table text and an optimum, on the host for either side; its
+    entry points are those of include/taudem_amd_dropan.h."""
+
+    def dropanalysis(self, ad8, p, fel, ssa, outlets, *, thresh_min=5.0, thresh_max=500.0, nthresh=10, steptype=0, dx=1.0, dy=1.0, nodata=int(P_NODATA),
+                     ssa_nodata=float(AREA_NODATA), grids=None, stats=False):
+        """thresh, n1, n2, sums, length, total_area, table, optimum = dropanalysis(ad8, p, fel, ssa, outlets)  (src/DropAnalysis.cpp:172).
+
+        For each of nthresh thresholds between thresh_min and thresh_max (steptype 0: log steps, else arithmetic) the stream mask ssa >= thresh is
+        ordered and the elevation drops of its streams are collected: thresh float32, n1 / n2 int64 (first-order / higher-order drops), sums
+        float64 [nthresh][4] (sum and sum of squares of the first-order, then of the higher-order drops), length float64 - numpy arrays on the
+        host; total_area float32; table: the text of the reference's table file; optimum: the first threshold whose |t| < 2, None when there is
+        none.  ssa: any float32 raster that increases downstream (ad8 itself serves); outlets: (columns, rows).  The fp64 sums are taken in a
+        fixed order: the same input gives the same bits.  grids=k (a test hook) also returns, after the optimum, the order (int16, nodata -32768)
+        and the start elevation carried down the stream (float32, nodata -FLT_MAX) of every cell for threshold number k."""
+        return _ret(_dropanalysis(_Call(self), ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids), stats)
+
+
+class Context(_DropAnalysisStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -595,6 +613,61 @@ def _dinftranslimaccum(f, ang, tsup, tc, cs, nodata, tsup_nodata, tc_nodata, cs_
     ox, oy, no = f.outlets(outlets)
     return tla, tdep, ctpt, f.call("tdx_dinftranslimaccum", pa, f.nx, f.ny, float(nodata), pdx, pdy, ps, float(tsup_nodata), pc, float(tc_nodata), pi,
                                    float(cs_nodata), int(bool(contcheck)), ox, oy, no, pt, pd, po)
+
+
+def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids):
+    """Context: (thresh, n1, n2, sums, length, total_area, table, optimum[, order, elevout], stats).  A strip: its own (thresh, n1, n2, sums, length,
+    outlet_term[, order, elevout], stats) - outlet_term float32 per outlet, ad8 of the strip's terminal outlets and 0 elsewhere."""
+    pa = f.raster(ad8, np.float32, "ad8")
+    pp = f.raster(p, np.int16, "p")
+    pf = f.raster(fel, np.float32, "fel")
+    ps = f.raster(ssa, np.float32, "ssa")
+    pdx, pdy = f.cells(dx, dy)
+    if outlets is None:
+        raise ValueError("outlets: dropanalysis needs the outlets (columns, rows)")
+    ox, oy, no = f.outlets(outlets)
+    nt = int(nthresh)
+    if nt < 2:
+        raise ValueError("nthresh: the number of thresholds must be greater than 1")
+    order, po = f.out(None, np.int16, "order") if grids is not None else (None, None)
+    elev, pe = f.out(None, np.float32, "elevout") if grids is not None else (None, None)
+    thresh, n1, n2 = np.zeros(nt, np.float32), np.zeros(nt, np.int64), np.zeros(nt, np.int64)
+    sums, length = np.zeros((nt, 4), np.float64), np.zeros(nt, np.float64)
+    head = (pa, pp, pf, ps, f.nx, f.ny, int(nodata), float(ssa_nodata), pdx, pdy)
+    ladder = (ox, oy, no, float(thresh_min), float(thresh_max), nt, int(steptype), int(grids) if grids is not None else -1, po, pe, _v(thresh), _v(n1), _v(n2), _v(sums),
+              _v(length))
+    extra = () if grids is None else (order, elev)
+    if f.strip:
+        term = np.zeros(max(no, 1), np.float32)
+        st = f.call("tdx_dropanalysis", *head, *ladder, _v(term))
+        return (thresh, n1, n2, sums, length, term[:no]) + extra + (st,)
+    dxc, dyc = f.keep[0], f.keep[1]
+    scal, found = np.zeros(2, np.float32), np.zeros(1, np.int32)
+    text = C.create_string_buffer(256 * nt + 512)
+    st = f.call("tdx_dropanalysis", *head, abs(float(dxc[f.rows // 2])), abs(float(dyc[f.rows // 2])), *ladder, _v(scal[0:1]), _v(scal[1:2]), _v(found),
+                C.cast(text, C.c_void_p), len(text))
+    return (thresh, n1, n2, sums, length, scal[0], text.value.decode(), scal[1] if found[0] else None) + extra + (st,)
+
+
+def dropanalysis_table(thresh, n1, n2, s1, s1sq, s2, s2sq, length, total_area):
+    """table, console, optimum = the table file and the console lines of DropAnalysis (src/DropAnalysis.cpp:597-674) from the float sums of all
+    thresholds, with the reference's own float / double expressions; optimum None when no threshold qualifies.  Host code: needs no GPU."""
+    thresh, s1, s1sq, s2, s2sq = (_flat(a, np.float32) for a in (thresh, s1, s1sq, s2, s2sq))
+    n1, n2, length = _flat(n1, np.int64), _flat(n2, np.int64), _flat(length, np.float64)
+    nt = thresh.size
+    if any(a.size != nt for a in (n1, n2, s1, s1sq, s2, s2sq, length)):
+        raise ValueError("dropanalysis_table: need one entry per threshold in every array")
+    table, console = C.create_string_buffer(256 * nt + 512), C.create_string_buffer(256 * nt + 1024)
+    opt, found = C.c_float(0.0), C.c_int32(0)
+    check(_lib.load().tdx_dropanalysis_table(nt, _v(thresh), _v(n1), _v(n2), _v(s1), _v(s1sq), _v(s2), _v(s2sq), _v(length), float(total_area), C.cast(table, C.c_void_p),
+                                             len(table), C.cast(console, C.c_void_p), len(console), C.byref(opt), C.byref(found)))
+    return table.value.decode(), console.value.decode(), np.float32(opt.value) if found.value else None
+
+
+def dropanalysis(ad8, p, fel, ssa, outlets, device=0, **kw):
+    """Context(device).dropanalysis(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.dropanalysis(ad8, p, fel, ssa, outlets, **kw)
 
 
 def catchhydrogeo(hand, catch, slp, ids, stages, device=0, **kw):

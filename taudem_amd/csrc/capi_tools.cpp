@@ -31,6 +31,7 @@
 //   tdx_tool_slopeavedown        <- sloped()              src/SlopeAveDown.cpp:59-330
 //   tdx_tool_catchhydrogeo       <- catchhydrogeo()       src/CatchHydroGeo.cpp:69-413
 //   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
+//   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -43,6 +44,7 @@
 #include <vector>
 
 #include "context.hpp"
+#include "dropan_table.hpp"
 #include "geotiff.hpp"
 #include "hand_tables.hpp"
 #include "outlets.hpp"
@@ -225,7 +227,8 @@ enum class Footer {
     HeaderTimes,   // PitRemove: a header read time of its own (src/flood.cpp:517-519)
     FlowDir,       // D8FlowDir / DinfFlowDir: slopes and flats apart, the slope raster written in between (src/d8.cpp, src/dinf.cpp)
     CountOnly,     // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
-    ComputeOnly    // CatchHydroGeo / InunDepth: one line, <label>: the whole run in seconds
+    ComputeOnly,   // CatchHydroGeo / InunDepth: one line, <label>: the whole run in seconds
+    NoWrite        // DropAnalysis: <label>: N + read / compute / total (src/DropAnalysis.cpp:690-692)
 };
 
 template <class T> constexpr tdx::DType dtype_of();
@@ -319,6 +322,7 @@ struct ToolRun {
             break;
         case Footer::CountOnly: printf("%s: %d\n", label, nproc); break;
         case Footer::ComputeOnly: printf("%s: %f\n", label, writet - begint); break;
+        case Footer::NoWrite: printf("%s: %d\nRead time: %f\nCompute time: %f\nTotal time: %f\n", label, nproc, readt - begint, writet - readt, writet - begint); break;
         }
         if (stats_name) print_gpu_stats(stats_name, st, grid->info.nx * grid->info.ny);
         return 0;
@@ -1076,6 +1080,100 @@ int tdx_tool_inundepth(const char* handfile, const char* catchfile, const char* 
     }
     t.output(mapfile, map, hand, (double)-3.0e38f);   // felNodata, header of hand (src/InunDepth.cpp:446,521)
     return t.finish("Inundation depth Compute time", "inundepth", Footer::ComputeOnly);
+}
+
+// ssa first, then p and ad8, each compared as the reference compares them (its messages, its codes 4 and 5), the outlets, then fel.  An outlet on a cell
+// without a direction is refused before anything runs (the reference indexes outside its offset table there).  With N GPUs every strip returns its own
+// counts, sums and length, which are added here in strip order; the outlets' terms of the total area are added in file order.
+int tdx_tool_dropanalysis(const char* areafile, const char* dirfile, const char* elevfile, const char* ssafile, const char* dropfile, const char* datasrc,
+                          const char* /*lyrname*/, int /*uselyrname*/, int /*lyrno*/, float threshmin, float threshmax, int nthresh, int steptype, float* threshopt) {
+    ToolRun t("DropAnalysis");
+    Raster ssa, p, ad8, fel;
+    Outlets o;
+    t.input(ssafile, F32, ssa);
+    if (t.rc == TDX_OK) {   // src/DropAnalysis.cpp:207-213
+        const float timeestimate = (2e-7 * ssa.info.nx * ssa.info.ny * nthresh / pow((double)tool_gpus(), 0.65)) / 60 + 1;
+        fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+        fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the "
+                        "computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+        fflush(stderr);
+    }
+    t.input(dirfile, I16, p, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("dir and ssa files not the same size. Exiting \n"); fflush(stdout); return 4; }
+    t.input(areafile, F32, ad8, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("ssa and area files not the same size. Exiting \n"); fflush(stdout); return 4; }
+    t.outlets(datasrc ? datasrc : "", 1, o);
+    t.input(elevfile, F32, fel, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("elev and ssa files not the same size. Exiting \n"); fflush(stdout); return 5; }
+    if (!t.read_done()) return t.rc;
+    if (nthresh < 2) { printf("Number of thresholds must be greater than 1. \n"); fflush(stdout); return 7; }   // src/DropAnalysis.cpp:369-373
+    const int64_t nx = ssa.info.nx, ny = ssa.info.ny, nout = int64_t(o.x.size());
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const float ssa_nd = (float)ssa.info.nodata;
+    for (int64_t i = 0; i < nout; i++) {
+        if (o.x[size_t(i)] < 0 || o.x[size_t(i)] >= nx || o.y[size_t(i)] < 0 || o.y[size_t(i)] >= ny) continue;
+        const int16_t d = p.s[size_t(o.y[size_t(i)]) * size_t(nx) + size_t(o.x[size_t(i)])];
+        if (d == p_nd || d < 0 || d > 8) {
+            fprintf(stderr, "taudem_amd: outlet %lld (column %d, row %d) lies on a cell without a flow direction\n", (long long)i, int(o.x[size_t(i)]), int(o.y[size_t(i)]));
+            return TDX_ERR_ARG;
+        }
+    }
+    struct Part {
+        std::vector<float> thresh, term;
+        std::vector<int64_t> n1, n2;
+        std::vector<double> sums, length;
+        void size(size_t nt, size_t no) { thresh.assign(nt, 0.f); term.assign(no, 0.f); n1.assign(nt, 0); n2.assign(nt, 0); sums.assign(4 * nt, 0.0); length.assign(nt, 0.0); }
+    } total;
+    const size_t nt = size_t(nthresh);
+    total.size(nt, size_t(nout));
+    std::vector<Part> part(size_t(std::max(tool_gpus(), 1)));
+    float total_area = 0.f;
+    const double dxA = ad8.info.dxA(), dyA = ad8.info.dyA();
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_dropanalysis(c, ad8.f.data(), p.s.data(), fel.f.data(), ssa.f.data(), nx, ny, p_nd, ssa_nd, ssa.info.dxc.data(), ssa.info.dyc.data(), dxA, dyA, o.xs(),
+                                    o.ys(), nout, threshmin, threshmax, nthresh, steptype, -1, nullptr, nullptr, total.thresh.data(), total.n1.data(), total.n2.data(),
+                                    total.sums.data(), total.length.data(), &total_area, nullptr, nullptr, nullptr, 0, s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            float *d_a = j.in(ad8.f), *d_f = j.in(fel.f), *d_s = j.in(ssa.f);
+            int16_t* d_p = j.in(p.s);
+            if (j.error) return j.error;
+            const toolstrips::LocalOutlets lo = j.local(o);
+            Part& q = part[size_t(j.rank)];
+            q.size(nt, size_t(nout));
+            return tdx_dropanalysis_strip(j.ctx, j.comm, d_a, d_p, d_f, d_s, j.nx, j.nyl, p_nd, ssa_nd, j.dxs.data(), j.dys.data(), lo.xs(), lo.ys(), nout, threshmin, threshmax,
+                                          nthresh, steptype, -1, nullptr, nullptr, q.thresh.data(), q.n1.data(), q.n2.data(), q.sums.data(), q.length.data(), q.term.data(), s);
+        });
+    if (!ok) return t.rc;
+    if (t.nproc > 1) {
+        total.thresh = part[0].thresh;
+        for (int r = 0; r < t.nproc; r++) {   // strip order: fixed
+            const Part& q = part[size_t(r)];
+            for (size_t i = 0; i < nt; i++) { total.n1[i] += q.n1[i]; total.n2[i] += q.n2[i]; total.length[i] += q.length[i]; }
+            for (size_t i = 0; i < 4 * nt; i++) total.sums[i] += q.sums[i];
+            for (size_t i = 0; i < size_t(nout); i++) total.term[i] += q.term[i];   // one strip owns the outlet, the others say 0
+        }
+        float ta = 0.f;
+        for (size_t i = 0; i < size_t(nout); i++) ta += total.term[i];   // file order (src/DropAnalysis.cpp:313-329)
+        total_area = ta * dxA * dyA;
+    }
+    std::vector<float> f(4 * nt);
+    for (size_t i = 0; i < nt; i++)
+        for (size_t k = 0; k < 4; k++) f[k * nt + i] = float(total.sums[4 * i + k]);
+    const dropan::Sums sm{int64_t(nt), total.thresh.data(), total.n1.data(), total.n2.data(), f.data(), f.data() + nt, f.data() + 2 * nt, f.data() + 3 * nt, total.length.data(),
+                          total_area};
+    std::string table, console;
+    float opt = 0.f;
+    int found = 0;
+    dropan::table(sm, &table, &console, &opt, &found);
+    FILE* fp = fopen(dropfile, "w");
+    if (!fp) { printf("Error opening file %s.\n", dropfile); fflush(stdout); return TDX_ERR_FILE; }
+    fwrite(table.data(), 1, table.size(), fp);
+    fclose(fp);
+    fputs(console.c_str(), stdout);
+    if (threshopt) *threshopt = opt;
+    return t.finish("Processes", "dropanalysis", Footer::NoWrite);
 }
 
 }  // extern "C"

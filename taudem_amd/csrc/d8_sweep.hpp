@@ -186,6 +186,64 @@ struct GridNetAlg {   // src/gridnet.cpp:380-426; record = {plen, tlen, gord (in
     }
 };
 
+// DropAnalysis (src/DropAnalysis.cpp:113-166, 479-531; dropan.hip): record = {order (int bits), elevOut}, 8 bytes, one load / store.  Its info words come from
+// dropan.hip's own set-up (a cell off the stream mask ssa >= thresh has no record at all, where GridNet's unmasked cell completes without a value):
+// [0:8) = [16:24) = the mask neighbours that point at the cell, INFO_PART = the cell is on the mask.  aux: fel.
+struct DropAlg {
+    using Cell = float2;
+    using Aux = float;
+    static constexpr bool HAS_AUX = true;
+    static constexpr bool HAS_DIST = false;
+    static constexpr bool HAS_ROWS = false;
+    static constexpr int kBulkSweeps = BULK_SWEEPS_D8;
+    static constexpr unsigned kBulkUntil = 16;
+    static constexpr int kMinWaves32 = 4;
+    static constexpr int kMaxRelease = 1;
+    static __device__ __forceinline__ unsigned rel_mask(unsigned inf) { const unsigned code = (inf >> 9) & 15u; return (code >= 1u && code <= 8u) ? 1u << (code - 1u) : 0u; }
+    static __device__ __forceinline__ float head(const float2& c) { return c.x; }
+    static __host__ __device__ __forceinline__ float2 outside() { const int m1 = -1; float z; memcpy(&z, &m1, 4); return make_float2(z, 0.f); }
+    // newOrder() (src/DropAnalysis.cpp:113-166) over the inflows `vmask` (bit k - 1: neighbour k) in k order - NOT Strahler's rule: inflow orders
+    // (1,1,2,2) in that order give 2, (2,2,1,1) give 3.  count: the number of inflows; e_last: elevOut of the last one (the only one of a cell that is no junction).
+    static __device__ __forceinline__ int order_of(unsigned vmask, const Cell (&nb)[9], int& count, float& e_last) {
+        int oOut = 1, ordermax = 0;
+        count = 0;
+        e_last = 0.f;
+#pragma unroll
+        for (int k = 1; k <= 8; k++) {
+            if (!((vmask >> (k - 1)) & 1u)) continue;
+            const int o = __float_as_int(nb[k].x);
+            count++;
+            if (count == 1) { oOut = o; ordermax = o; }
+            else if (o > oOut) { ordermax = o; oOut = o; }
+            else if (o == oOut) oOut = ordermax + 1;
+            e_last = nb[k].y;
+        }
+        return oOut;
+    }
+    // the record of a cell from its inflows' final records: a source starts at its own fel, a single inflow hands its elevOut on, a junction takes the elevOut
+    // of the LAST inflow (k order) whose order is >= oOut, or starts a new stream (updateAtJunction, src/DropAnalysis.cpp:67-110, 510-531)
+    static __device__ __forceinline__ Cell record_of(unsigned vmask, const Cell (&nb)[9], float fel) {
+        int count;
+        float e;
+        const int oOut = order_of(vmask, nb, count, e);
+        if (count == 0) e = fel;
+        else if (count > 1) {
+            bool newstream = true;
+#pragma unroll
+            for (int k = 1; k <= 8; k++) {
+                if (!((vmask >> (k - 1)) & 1u)) continue;
+                if (__float_as_int(nb[k].x) >= oOut) { e = nb[k].y; newstream = false; }
+            }
+            if (newstream) e = fel;
+        }
+        return make_float2(__int_as_float(oOut), e);
+    }
+    template <class L>
+    __device__ __forceinline__ void eval(L& S, int c, int cl, int ly, unsigned inf, const Cell (&nb)[9]) const {
+        S.v[cl] = record_of((inf >> 16) & 0xFFu, nb, S.aux[c]);
+    }
+};
+
 constexpr int QFWD = 128;   // forward policies: only a fork whose branches become ready at once uses the queue
 template <class Alg, int TSZ>
 struct Lds {

@@ -293,7 +293,19 @@ def project_critical_path(logs, exchange_us: float = 10.0, vote_us: float = 30.0
                         "note": "projection from one-GPU segment traces (one rank on the device at a time), not an N-GPU measurement"}}
 
 
-class StripPipeline:
+class _StripDropAnalysisStage:
+    """StripPipeline.dropanalysis: a strip's partial counts and sums rather than rasters (include/taudem_amd_dropan.h)."""
+
+    def dropanalysis(self, ad8, p, fel, ssa, outlets, thresh_min=5.0, thresh_max=500.0, nthresh=10, steptype=0, dx=1.0, dy=1.0, nodata=int(P_NODATA),
+                     ssa_nodata=-1.0, grids=None):
+        """thresh, n1, n2, sums, length, outlet_term = dropanalysis(ad8, p, fel, ssa, outlets) on this strip (src/DropAnalysis.cpp:172): the STRIP's own
+        counts, fp64 sums and length per threshold and, per outlet, ad8 of the strip's terminal outlets (0 elsewhere).  Add the strips in strip
+        order and the outlet terms in file order (times the cell area: the total area), then taudem_amd.dropanalysis_table makes the table and the
+        optimum.  outlets: (columns, STRIP-ARRAY rows) as for aread8; the library fills the halo rows of p, fel and ssa."""
+        return api._dropanalysis(self._call(), ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids)
+
+
+class StripPipeline(_StripDropAnalysisStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

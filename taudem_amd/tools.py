@@ -148,6 +148,19 @@ def inundepth(handfile, catchfile, maskfile, fcfile, hpfile, mapfile, depthfile=
                                           _b(depthfile) if depthfile else None)
 
 
+def dropan(areafile, dirfile, elevfile, ssafile, dropfile, datasrc, lyrname="", uselyrname=0, lyrno=0, threshmin=5.0, threshmax=500.0, nthresh=10, steptype=0):
+    """src/DropAnalysis.cpp:172 (DropAnalysis): writes the table dropfile; returns (code, optimum threshold - 0.0 when no threshold qualifies)."""
+    import ctypes
+
+    opt = ctypes.c_float(0.0)
+    rc = _lib.load().tdx_tool_dropanalysis(_b(areafile), _b(dirfile), _b(elevfile), _b(ssafile), _b(dropfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno),
+                                           float(threshmin), float(threshmax), int(nthresh), int(steptype), ctypes.byref(opt))
+    return rc, float(opt.value)
+
+
+dropanalysis = dropan
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
