@@ -650,6 +650,9 @@ int tdx_tool_set_gpus(int ngpus);
  * every program that includes taudem_amd.h sees them */
 #include "taudem_amd_dropan.h"
 
+/* PeukerDouglas (compute entry points and file-level tool function): likewise */
+#include "taudem_amd_peuker.h"
+
 #ifdef __cplusplus
 }
 #endif

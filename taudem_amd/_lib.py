@@ -260,6 +260,16 @@ _DROPAN_SIGNATURES = {
 }
 DROPAN_SYMBOLS = tuple(_DROPAN_SIGNATURES)
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_peuker.h declares, the second extension header
+_PEUKER_SIGNATURES = {
+    # PeukerDouglas: ctx, fel, nx, ny, fel_nodata, w_center, w_side, w_diag, ss, w (optional), stats; the strip form has the comm after the context
+    "tdx_peukerdouglas": (C.c_int, [_P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P]),
+    "tdx_peukerdouglas_dev": (C.c_int, [_P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P]),
+    "tdx_peukerdouglas_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P]),
+    "tdx_tool_peukerdouglas": (C.c_int, [C.c_char_p, C.c_char_p, _P]),
+}
+PEUKER_SYMBOLS = tuple(_PEUKER_SIGNATURES)
+
 _lib = None
 
 
@@ -283,7 +293,7 @@ def load():
     except Exception:  # pragma: no cover - torch-less hosts use the system ROCm runtime
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -166,7 +166,19 @@ class _DropAnalysisStage:
         return _ret(_dropanalysis(_Call(self), ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids), stats)
 
 
-class Context(_DropAnalysisStage):
+class _PeukerDouglasStage:
+    """Context.peukerdouglas; its entry points are those of include/taudem_amd_peuker.h."""
+
+    def peukerdouglas(self, fel, nodata=float(FEL_NODATA), weights=(0.4, 0.1, 0.05), float_weights=False, out=None, stats=False):
+        """ss = peukerdouglas(fel)  (src/PeukerDouglas.cpp:54): int16, 1 on the stream-source cells of the curvature-based stream definition, 0 elsewhere.
+
+        fel is smoothed with weights = (centre, side, diagonal), the reference's -par, and every 2x2 group of the smoothed grid unflags its highest
+        cell (and ties, and all four next to nodata): what stays flagged are the upward-curved cells.  float_weights=True also returns w, the same
+        0 / 1 values as float32, which is what aread8(weights=w) takes: ss, w = peukerdouglas(fel, float_weights=True).  out: ss, or (ss, w)."""
+        return _ret(_peukerdouglas(_Call(self), fel, nodata, weights, float_weights, out), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -615,6 +627,17 @@ def _dinftranslimaccum(f, ang, tsup, tc, cs, nodata, tsup_nodata, tc_nodata, cs_
                                    float(cs_nodata), int(bool(contcheck)), ox, oy, no, pt, pd, po)
 
 
+def _peukerdouglas(f, fel, nodata, weights, float_weights, out):
+    pz = f.raster(fel, np.float32, "fel")
+    if len(weights) != 3:
+        raise ValueError("weights: need (centre, side, diagonal)")
+    o_ss, o_w = (out if float_weights else (out, None)) if out is not None else (None, None)
+    ss, ps = f.out(o_ss, np.int16, "ss")
+    w, pw = f.out(o_w, np.float32, "w") if float_weights else (None, None)
+    st = f.call("tdx_peukerdouglas", pz, f.nx, f.ny, float(nodata), float(weights[0]), float(weights[1]), float(weights[2]), ps, pw)
+    return (ss, w, st) if float_weights else (ss, st)
+
+
 def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids):
     """Context: (thresh, n1, n2, sums, length, total_area, table, optimum[, order, elevout], stats).  A strip: its own (thresh, n1, n2, sums, length,
     outlet_term[, order, elevout], stats) - outlet_term float32 per outlet, ad8 of the strip's terminal outlets and 0 elsewhere."""
@@ -668,6 +691,12 @@ def dropanalysis(ad8, p, fel, ssa, outlets, device=0, **kw):
     """Context(device).dropanalysis(...) for a single call."""
     with Context(device) as ctx:
         return ctx.dropanalysis(ad8, p, fel, ssa, outlets, **kw)
+
+
+def peukerdouglas(fel, device=0, **kw):
+    """Context(device).peukerdouglas(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.peukerdouglas(fel, **kw)
 
 
 def catchhydrogeo(hand, catch, slp, ids, stages, device=0, **kw):

@@ -32,6 +32,7 @@
 //   tdx_tool_catchhydrogeo       <- catchhydrogeo()       src/CatchHydroGeo.cpp:69-413
 //   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
 //   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
+//   tdx_tool_peukerdouglas       <- peukerdouglas()       src/PeukerDouglas.cpp:54-241
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1174,6 +1175,34 @@ int tdx_tool_dropanalysis(const char* areafile, const char* dirfile, const char*
     fputs(console.c_str(), stdout);
     if (threshopt) *threshopt = opt;
     return t.finish("Processes", "dropanalysis", Footer::NoWrite);
+}
+
+// The output takes the input's georeferencing and the reference's nodata tag -2 (src/PeukerDouglas.cpp:101,215), a value the tool never writes.
+int tdx_tool_peukerdouglas(const char* felfile, const char* ssfile, const float* p) {
+    if (!felfile || !ssfile || !p) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_peukerdouglas: bad argument");
+    ToolRun t("PeukerDouglas");
+    Raster fel;
+    t.input(felfile, F32, fel);
+    if (t.rc == TDX_OK) {   // src/PeukerDouglas.cpp:74-80
+        const float timeestimate = (1e-7 * fel.info.nx * fel.info.ny / pow((double)tool_gpus(), 1)) / 60 + 1;
+        fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+        fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the "
+                        "computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+        fflush(stderr);
+    }
+    if (!t.read_done()) return t.rc;
+    std::vector<int16_t> ss(t.cells());
+    const float nd = (float)fel.info.nodata, p0 = p[0], p1 = p[1], p2 = p[2];
+    const bool ok = t.compute([&](tdx_context* c, tdx_stats* s) { return tdx_peukerdouglas(c, fel.f.data(), fel.info.nx, fel.info.ny, nd, p0, p1, p2, ss.data(), nullptr, s); },
+                              [&](RankJob& j, tdx_stats* s) {
+                                  float* d_fel = j.in(fel.f);
+                                  int16_t* d_ss = j.out(ss);
+                                  if (j.error) return j.error;
+                                  return tdx_peukerdouglas_strip(j.ctx, j.comm, d_fel, j.nx, j.nyl, nd, p0, p1, p2, d_ss, nullptr, s);
+                              });
+    if (!ok) return t.rc;
+    t.output(ssfile, ss, fel, -2.0);
+    return t.finish("Processors", "peukerdouglas");
 }
 
 }  // extern "C"

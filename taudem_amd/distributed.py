@@ -305,7 +305,16 @@ class _StripDropAnalysisStage:
         return api._dropanalysis(self._call(), ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids)
 
 
-class StripPipeline(_StripDropAnalysisStage):
+class _StripPeukerDouglasStage:
+    """StripPipeline.peukerdouglas (include/taudem_amd_peuker.h)."""
+
+    def peukerdouglas(self, fel, nodata=float(FEL_NODATA), weights=(0.4, 0.1, 0.05), float_weights=False, out=None):
+        """ss = peukerdouglas(fel) on this strip (src/PeukerDouglas.cpp:54), or ss, w with float_weights: the two kernels with the smoothed grid between
+        them.  The library fills the halo rows of fel and exchanges the smoothed edge rows; the halo rows of ss and w are not written."""
+        return api._peukerdouglas(self._call(), fel, nodata, weights, float_weights, out)
+
+
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

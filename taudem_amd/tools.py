@@ -161,6 +161,14 @@ def dropan(areafile, dirfile, elevfile, ssafile, dropfile, datasrc, lyrname="", 
 dropanalysis = dropan
 
 
+def peukerdouglas(felfile, ssfile, p=(0.4, 0.1, 0.05)):
+    """src/PeukerDouglas.cpp:54 (PeukerDouglas): p = the weights of the centre, the side and the diagonal cells of the smoothing."""
+    import ctypes
+
+    w = (ctypes.c_float * 3)(float(p[0]), float(p[1]), float(p[2]))
+    return _lib.load().tdx_tool_peukerdouglas(_b(felfile), _b(ssfile), ctypes.cast(w, ctypes.c_void_p))
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
