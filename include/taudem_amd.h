@@ -653,6 +653,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* PeukerDouglas (compute entry points and file-level tool function): likewise */
 #include "taudem_amd_peuker.h"
 
+/* AreaD8's tile counters (a diagnostic getter): likewise */
+#include "taudem_amd_ad8.h"
+
 #ifdef __cplusplus
 }
 #endif

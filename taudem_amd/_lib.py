@@ -270,6 +270,12 @@ _PEUKER_SIGNATURES = {
 }
 PEUKER_SYMBOLS = tuple(_PEUKER_SIGNATURES)
 
+# name -> (restype, argtypes): the symbol include/taudem_amd_ad8.h declares, the third extension header
+_AD8_SIGNATURES = {
+    "tdx_context_ad8_tile_counters": (None, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+AD8_SYMBOLS = tuple(_AD8_SIGNATURES)
+
 _lib = None
 
 
@@ -293,7 +299,7 @@ def load():
     except Exception:  # pragma: no cover - torch-less hosts use the system ROCm runtime
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

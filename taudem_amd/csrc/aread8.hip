@@ -22,6 +22,7 @@
 #include "strips.hpp"
 
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 using namespace tdxk;
@@ -267,6 +268,13 @@ __global__ __launch_bounds__(256) void ad8_halo_kernel(const int16_t* __restrict
 //                              participating cell becomes a NODE of the crossing forest; for every
 //                              crossing that enters the tile the lane follows the in-tile path to the
 //                              exit cell and records next(node).
+//   A' ad8_tile_fast_kernel    runs BEFORE A on every tile and finishes the CLEAN ones: all 64 rows valid, the staged 66 x 66 window inside the array and every
+//                              code in it 1 .. 8 (no nodata, no p == 0, no sink, nothing else), no cycle.  There every cell takes part, none is contaminated or
+//                              poisoned, and a cell's count is the size of its in-tile upstream subtree - no in-degrees, no order: pointer doubling (acc = 1,
+//                              nxt = in-tile target; a round adds every live cell's PREVIOUS acc to acc[nxt] and replaces nxt by nxt[nxt]; after round k acc
+//                              counts the cells less than 2^(k+1) hops upstream; at most 12 rounds, a pointer still live after the 12th is a cycle).  It writes
+//                              what A writes for such a tile, byte for byte.  Any other tile writes only its index into a redo list, and A runs right behind
+//                              on the same stream over that list (device-side count, no host synchronisation).  TDX_AD8_LOCAL=kahn: A alone on every tile.
 //   B  ad8_forest_walk_kernel  the walk of ad8_walk_kernel on the crossing forest (nodes = perimeter
 //                              cells, ~1/16 of the cells, paths ~64x shorter), integer packed atomics.
 //   C  ad8_tile_apply_kernel   per tile, in LDS: add the flow of every entering crossing along its
@@ -400,7 +408,9 @@ __device__ unsigned long long g_ad8_dbg[8];   // TDX_AD8_DEBUG=1: phase cycles o
 template <bool DBG, bool FLAT>
 __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
                                                              uint32_t* __restrict__ cellw, unsigned long long* __restrict__ node_acc,
-                                                             uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next) {
+                                                             uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next,
+                                                             const uint32_t* __restrict__ list, const unsigned long long* __restrict__ nlist) {
+    if (list && blockIdx.x >= *nlist) return;   // the redo launch behind ad8_tile_fast_kernel: one workgroup per tile of the raster, the list's length known to the device only
     unsigned long long tcs[6];
 #define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
     AD8_MARK(0);
@@ -412,7 +422,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
     __shared__ unsigned sIn[256];   // crossings that end at each perimeter cell
     __shared__ uint16_t sRing[4 * TH];
     int16_t* const sT = reinterpret_cast<int16_t*>(sO);
-    const int tile = blockIdx.x;
+    const int tile = list ? int(list[blockIdx.x]) : int(blockIdx.x);
     const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
     const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
     const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16;
@@ -578,6 +588,199 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         AD8_MARK(5);
         if (tid == 0)
             for (int i = 0; i < 5; i++) atomicAdd(&g_ad8_dbg[i], tcs[i + 1] - tcs[i]);
+    }
+#undef AD8_MARK
+}
+
+// Stage P (tile + ring) as raw codes, one byte per cell at 66-pitch: the code where it is 1 .. 8 and the cell lies inside the array and is not nodata, 0 otherwise.
+// Returns whether this lane staged a 0: the tile is then not clean.  (Loads in two batches, addresses clamped: as stage_p_onehot.)
+__device__ __forceinline__ bool stage_p_raw(const int16_t* __restrict__ P, int nx, int ny_arr, int x0, int ya0, int16_t nodata, uint8_t* sC) {
+    constexpr int NIT = (TH * TH + 255) / 256, HALF = (NIT + 1) / 2;
+    bool bad = false;
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+        int16_t v[HALF];
+        unsigned ok = 0;
+#pragma unroll
+        for (int i = 0; i < HALF; i++) {
+            const int e = int(threadIdx.x) + (b * HALF + i) * 256, ec = e < TH * TH ? e : TH * TH - 1;
+            const int ly = ec / TH, lx = ec - ly * TH;
+            const int gx = x0 + lx - 1, gy = ya0 + ly - 1;
+            const int gxc = gx < 0 ? 0 : (gx >= nx ? nx - 1 : gx), gyc = gy < 0 ? 0 : (gy >= ny_arr ? ny_arr - 1 : gy);
+            v[i] = P[size_t(gyc) * size_t(nx) + size_t(gxc)];
+            if (gx == gxc && gy == gyc) ok |= 1u << i;
+        }
+#pragma unroll
+        for (int i = 0; i < HALF; i++) {
+            const int e = int(threadIdx.x) + (b * HALF + i) * 256;
+            if (b * HALF + i < NIT && e < TH * TH) {
+                const bool good = ((ok >> i) & 1u) && v[i] != nodata && unsigned(int(v[i]) - 1) < 8u;
+                sC[e] = good ? uint8_t(v[i]) : uint8_t(0);
+                bad |= !good;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return bad;
+}
+
+// TDX_AD8_DEBUG=1: ad8_tile_fast_kernel, summed over the clean tiles (thread 0): [0, 5) phase cycles, [5] doubling rounds, [6] tiles
+__device__ unsigned long long g_ad8_dbg_fast[8];
+constexpr int AD8_MAX_ROUNDS = 12;   // an acyclic in-tile path has at most 4095 hops < 2^12
+// Phase A' (see the block comment above).  25.6 KB of LDS: the staged codes (bytes, 66-pitch) and - once every lane holds the targets of its own 16 cells and the ring
+// lanes their entry cells - the 64-pitch table of pointers share one region.
+template <bool DBG>
+__global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
+                                                            uint32_t* __restrict__ cellw, unsigned long long* __restrict__ node_acc,
+                                                            uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next,
+                                                            uint32_t* __restrict__ redo, unsigned long long* __restrict__ nredo) {
+    unsigned long long tcs[6];
+#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
+    AD8_MARK(0);
+    __shared__ int16_t sT[TS * TS];       // while staging: TH * TH bytes of codes
+    __shared__ unsigned sAcc[TS * TS];
+    __shared__ unsigned sIn[256];         // crossings that end at each perimeter cell
+    __shared__ unsigned sVote[3][4];      // per wave: "staged a cell that is not 1 .. 8", "a pointer is live" of the even / odd rounds
+    static_assert(TH * TH <= int(sizeof(int16_t)) * TS * TS, "the staged codes fit the pointer table");
+    uint8_t* const sC = reinterpret_cast<uint8_t*>(sT);
+    const int tile = blockIdx.x;
+    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
+    const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
+    const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16, wave = tid >> 6;
+    // all rows valid and the window inside the array: uniform, and nothing is staged otherwise
+    bool bad = rv != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr;
+    if (!bad) bad = stage_p_raw(P, g.nx, g.ny_arr, x0, ya0, nodata, sC);
+    sIn[tid] = 0u;
+    const bool wave_bad = __ballot(bad) != 0ull;   // (the ballot by ALL lanes, not under the branch of the lane that stores it)
+    if (lx == 0) sVote[0][wave] = wave_bad ? 1u : 0u;
+    __syncthreads();
+    if ((sVote[0][0] | sVote[0][1] | sVote[0][2] | sVote[0][3]) != 0u) {
+        if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+        return;
+    }
+    AD8_MARK(1);
+    // a lane's own 16 codes -> in-tile target, or -2: the crossing leaves the tile (its target takes part, like everything in the window)
+    unsigned exits = 0, exit_up = 0, exit_down = 0;
+    int16_t ptr[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int ly = ry0 + r;
+        const int p = sC[(ly + 1) * TH + lx + 1];
+        const int tlx = lx + d1(p), tly = ly + d2(p);
+        const bool in = in_tile(tlx, tly, TS);
+        ptr[r] = int16_t(in ? tly * TS + tlx : -2);
+        if (!in) {
+            exits |= 1u << r;
+            if (d2(p) < 0) exit_up |= 1u << r;
+            if (d2(p) > 0) exit_down |= 1u << r;
+        }
+    }
+    // ring cells (ring_cell() order, two per lane at most) whose flow enters the tile: the entry cell, or -1
+    int ent[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int j = tid + 256 * k;
+        int hx, hy;
+        ent[k] = -1;
+        if (j < 4 * TH && ring_cell(j, TS, hx, hy)) {
+            const int ph = sC[(hy + 1) * TH + hx + 1];
+            const int vx = hx + d1(ph), vy = hy + d2(ph);
+            if (in_tile(vx, vy, TS)) ent[k] = vy * TS + vx;
+        }
+    }
+    __syncthreads();   // every lane is done reading codes: the pointer table takes their place
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        sT[(ry0 + r) * TS + lx] = ptr[r];
+        sAcc[(ry0 + r) * TS + lx] = 1u;
+    }
+    __syncthreads();
+    AD8_MARK(2);
+    // Crossings that enter the tile: follow the in-tile path of the entry cell to where it leaves - now, on the table of TARGETS, which the doubling overwrites.
+    // (Bounded by the tile's cell count: on a cycle the walk may end nowhere; the tile is then redone.)  node_next is written once the tile is known to be clean.
+    uint32_t ent_next[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        ent_next[k] = NEXT_NONE;
+        if (ent[k] < 0) continue;
+        int cur = ent[k], hops = 0;
+        while (sT[cur] >= 0 && hops < TS * TS) { cur = sT[cur]; hops++; }
+        if (sT[cur] == -2) {
+            const int pp = perim_pos(cur % TS, cur / TS, TS);
+            atomicAdd(&sIn[pp], 1u);
+            ent_next[k] = uint32_t(tile) * 256u + uint32_t(pp);
+        }
+    }
+    __syncthreads();
+    AD8_MARK(3);
+    // Pointer doubling.  Phase 1 reads nxt[n] and adds the lane's previous acc to acc[n] (non-returning atomics, all independent); phase 2 publishes the new pointers
+    // and re-reads the own acc of the cells that go on.  (Both in one phase would mix pointers of two generations: the invariant needs exact powers of two.)
+    unsigned acc[16];
+    unsigned live = ~exits & 0xFFFFu;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 1u;
+    int rounds = 0;
+    for (;;) {
+        // (the 16 reads without a branch, a dead pointer reading its own cell: under a branch each read was waited for where it was issued - 16 LDS round trips
+        // in a row instead of one)
+        int nn[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) nn[r] = sT[((live >> r) & 1u) ? int(ptr[r]) : (ry0 + r) * TS + lx];
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            if ((live >> r) & 1u) (void)__hip_atomic_fetch_add(&sAcc[ptr[r]], acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+            if ((live >> r) & 1u) {
+                const int c = (ry0 + r) * TS + lx;
+                ptr[r] = int16_t(nn[r]);
+                sT[c] = int16_t(nn[r]);
+                if (nn[r] < 0) live &= ~(1u << r);
+                else acc[r] = sAcc[c];
+            }
+        rounds++;
+        const bool wave_live = __ballot(live != 0u) != 0ull;
+        if (lx == 0) sVote[1 + (rounds & 1)][wave] = wave_live ? 1u : 0u;
+        __syncthreads();   // (the vote of round k + 2 is written behind the first barrier of that round: every wave has read this one by then)
+        const unsigned* v = sVote[1 + (rounds & 1)];
+        if ((v[0] | v[1] | v[2] | v[3]) == 0u) break;
+        if (rounds == AD8_MAX_ROUNDS) {   // a cycle: not clean (nothing has been written to global memory yet)
+            if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+            return;
+        }
+    }
+    AD8_MARK(4);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int j = tid + 256 * k;
+        int hx, hy;
+        if (ent[k] >= 0 && ring_cell(j, TS, hx, hy)) node_next[node_id(g, x0 + hx, ya0 + hy)] = ent_next[k];
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int ly = ry0 + r, c = ly * TS + lx;
+        const int gx = x0 + lx, gy = ya0 + ly;
+        const unsigned cnt = sAcc[c];
+        cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = cw_pack(cnt, false, false);
+        if ((exits >> r) & 1u) {
+            const int pp = perim_pos(lx, ly, TS);
+            const uint32_t nid = uint32_t(tile) * 256u + uint32_t(pp);
+            node_acc[nid] = nw_pack(cnt, 0u, 0u, 0u);
+            node_indeg[nid] = sIn[pp];
+            const int tgy = gy + (((exit_up >> r) & 1u) ? -1 : (((exit_down >> r) & 1u) ? 1 : 0));
+            if (tgy < g.y0) node_next[nid] = NEXT_REMOTE_UP;        // the tile that would record next(node) lives on another rank
+            else if (tgy >= g.y1) node_next[nid] = NEXT_REMOTE_DOWN;
+        }
+    }
+    if (DBG) {
+        __syncthreads();
+        AD8_MARK(5);
+        if (tid == 0) {
+            for (int i = 0; i < 5; i++) atomicAdd(&g_ad8_dbg_fast[i], tcs[i + 1] - tcs[i]);
+            atomicAdd(&g_ad8_dbg_fast[5], (unsigned long long)rounds);
+            atomicAdd(&g_ad8_dbg_fast[6], 1ull);
+        }
     }
 #undef AD8_MARK
 }
@@ -1138,9 +1341,13 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
     uint32_t* biglist = static_cast<uint32_t*>(ctx->scratch(TDX_S_E, bigcap * 4));
     unsigned long long* boxes = static_cast<unsigned long long*>(ctx->scratch(TDX_S_F, size_t(st.nx) * 4 * 8));   // out-box[2nx], in-box[2nx]
     uint8_t* delivered = static_cast<uint8_t*>(ctx->scratch(TDX_S_G, size_t(st.nx) * 2));
-    if (!cellw || !node_acc || !node_indeg || !node_next || !biglist || !boxes || !delivered) return TDX_ERR_NOMEM;
+    uint32_t* redo = static_cast<uint32_t*>(ctx->scratch(TDX_S_K, ntiles * 4));   // tiles that ad8_tile_fast_kernel left to the Kahn sweep
+    if (!cellw || !node_acc || !node_indeg || !node_next || !biglist || !boxes || !delivered || !redo) return TDX_ERR_NOMEM;
+    const char* const ad8_local = getenv("TDX_AD8_LOCAL");   // "kahn": every tile to ad8_tile_local_kernel (A/B hook and witness, read per call)
+    const bool kahn_only = ad8_local && strcmp(ad8_local, "kahn") == 0;
     unsigned long long *outbox = boxes, *inbox = boxes + 2 * size_t(st.nx);
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ctx->d_mail);
+    unsigned long long* nredo = d_cnt + 7;   // (cleared with the other stage counters by ad8_init_kernel)
     ctx->begin_call(stats);
     strip_mark(ctx, st, "aread8");
     int rc = strip_exchange<int16_t>(ctx, st, d_p, p_nodata);   // directions of the neighbours' boundary rows
@@ -1151,19 +1358,36 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
     {
         TdxSpan sp(ctx, TDX_K_STENCIL);
         static const bool ad8_debug = getenv("TDX_AD8_DEBUG") != nullptr;
+        const unsigned nt = unsigned(ntiles);
+        // the clean tiles by pointer doubling, the others - behind it on the stream, from the device-side redo list - by the Kahn sweep
+        const uint32_t* list = kahn_only ? nullptr : redo;
         if (ad8_debug) {
-            unsigned long long z[8] = {};
+            unsigned long long z[8] = {}, zf[8] = {};
             TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg), z, sizeof(z)));
-            hipLaunchKernelGGL((ad8_tile_local_kernel<true, true>), dim3(unsigned(ntiles)), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next);
+            TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg_fast), zf, sizeof(zf)));
+            if (!kahn_only)
+                hipLaunchKernelGGL((ad8_tile_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo);
+            hipLaunchKernelGGL((ad8_tile_local_kernel<true, true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
             TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
             TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_dbg), sizeof(z)));
-            fprintf(stderr, "ad8_tile_local: cycles per tile: stage %.0f, topology %.0f, targets %.0f, Kahn walks %.0f, entry walks %.0f, write-back %.0f\n",
-                    double(z[0]) / double(ntiles), double(z[1]) / double(ntiles) , 0.0, double(z[2]) / double(ntiles), double(z[3]) / double(ntiles), double(z[4]) / double(ntiles));
-        } else if (getenv("TDX_AD8_KAHN_NESTED"))   // (A/B hook, read per call: the walk loop nested in the loop over a lane's sources)
-            hipLaunchKernelGGL((ad8_tile_local_kernel<false, false>), dim3(unsigned(ntiles)), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next);
-        else
-            hipLaunchKernelGGL((ad8_tile_local_kernel<false, true>), dim3(unsigned(ntiles)), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next);
-        if (stats) stats->launches[TDX_K_STENCIL]++;
+            TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(zf, HIP_SYMBOL(g_ad8_dbg_fast), sizeof(zf)));
+            unsigned long long nr = ntiles;
+            if (!kahn_only) TDX_HIP_CHECK(ctx, hipMemcpy(&nr, nredo, sizeof(nr), hipMemcpyDeviceToHost));
+            const double nk = double(nr ? nr : 1), nf = double(zf[6] ? zf[6] : 1);
+            fprintf(stderr, "ad8_tile_local: %llu tiles, cycles per tile: stage %.0f, topology %.0f, targets %.0f, Kahn walks %.0f, entry walks %.0f, write-back %.0f\n", nr,
+                    double(z[0]) / nk, double(z[1]) / nk, 0.0, double(z[2]) / nk, double(z[3]) / nk, double(z[4]) / nk);
+            if (!kahn_only)
+                fprintf(stderr, "ad8_tile_fast: %llu tiles, cycles per tile: stage %.0f, targets %.0f, entry walks %.0f, doubling %.0f, write-back %.0f; %.2f rounds per tile\n", zf[6],
+                        double(zf[0]) / nf, double(zf[1]) / nf, double(zf[2]) / nf, double(zf[3]) / nf, double(zf[4]) / nf, double(zf[5]) / nf);
+        } else {
+            if (!kahn_only)
+                hipLaunchKernelGGL((ad8_tile_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo);
+            if (getenv("TDX_AD8_KAHN_NESTED"))   // (A/B hook, read per call: the walk loop nested in the loop over a lane's sources)
+                hipLaunchKernelGGL((ad8_tile_local_kernel<false, false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
+            else
+                hipLaunchKernelGGL((ad8_tile_local_kernel<false, true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
+        }
+        if (stats) stats->launches[TDX_K_STENCIL] += kahn_only ? 1 : 2;   // the fast kernel and the redo launch behind it
     }
     int64_t outer = 1;
     ctx->phase = "forest";
@@ -1195,9 +1419,11 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
                            big_threshold, d_ad8, biglist, d_cnt);
         if (stats) stats->launches[TDX_K_STENCIL]++;
     }
-    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_mail, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_mail, d_cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // the big cells and, word 7, the redone tiles
     TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
     const unsigned long long nbig = ctx->h_mail[0];
+    ctx->ad8_redo_tiles = kahn_only ? int64_t(ntiles) : int64_t(ctx->h_mail[7]);
+    ctx->ad8_fast_tiles = int64_t(ntiles) - ctx->ad8_redo_tiles;
     if (nbig > bigcap) return tdx_fail(ctx, TDX_ERR_NOMEM, "AreaD8: big-cell list exhausted");
     int64_t nbig_all = int64_t(nbig);
     rc = strip_allreduce(ctx, st, &nbig_all, 1, TDX_OP_SUM);

@@ -163,6 +163,11 @@ void tdx_context_comm_counters(const tdx_context* c, int64_t* exchanges, int64_t
     if (allreduces) *allreduces = c ? c->comm_allreduces_total : 0;
 }
 
+void tdx_context_ad8_tile_counters(const tdx_context* c, int64_t* fast_tiles, int64_t* redone_tiles) {
+    if (fast_tiles) *fast_tiles = c ? c->ad8_fast_tiles : 0;
+    if (redone_tiles) *redone_tiles = c ? c->ad8_redo_tiles : 0;
+}
+
 int64_t tdx_context_segments(tdx_context* c, tdx_segment* out, int64_t capacity) {
     if (!c) return 0;
     const int64_t n = int64_t(c->segments.size());

@@ -66,6 +66,7 @@ struct tdx_context {
     bool comm_ordered = false;   // the call's transport enqueues its collectives on the stream (TDX_COMM_STREAM_ORDERED)
     int64_t comm_exchanges = 0, comm_allreduces = 0;   // of the running call
     int64_t comm_exchanges_total = 0, comm_allreduces_total = 0;   // since the context was created (tdx_context_comm_counters)
+    int64_t ad8_fast_tiles = 0, ad8_redo_tiles = 0;   // of the last tile-contraction AreaD8 call: tiles finished by pointer doubling / by the Kahn sweep (tdx_context_ad8_tile_counters)
 
     // ---- segment trace (option "segment_trace"; scripts/project_8gpu.py): a strip run is a sequence of SEGMENTS of rank-local work, each ended by a
     // collective (halo exchange / all-reduce) or by the end of the call.  Every rank passes through the same sequence (the protocol is rank-symmetric),
