@@ -56,6 +56,20 @@ def parse_table(text):
     return rows, float(lines[-1].split(":")[1])
 
 
+def console_t(console):
+    """the Tval entries of the console lines that have one"""
+    lines = console.decode().split("\n")
+    first = next(i for i, ln in enumerate(lines) if ln.startswith("Threshold DrainDen"))
+    ts = []
+    for ln in lines[first + 1:]:
+        if "Value for optimum" in ln:
+            break
+        last = ln.replace(" - ", " x ").split()[-1]
+        if last != "x":
+            ts.append(float(last))
+    return np.array(ts)
+
+
 def sums_from_drops(d1, d2):
     """s1, s1sq, s2, s2sq: the correctly rounded sums of the drops and of their float squares (math.fsum), as float64"""
     sq = lambda d: (d * d).astype(np.float32)  # noqa: E731  (the float square, as the reference forms it)

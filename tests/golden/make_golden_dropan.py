@@ -1,7 +1,7 @@
 """Golden vectors for DropAnalysis (src/DropAnalysis.cpp): runs the REAL reference tool on the committed cases.  Build container only, after build()
 has left the reference's common objects in oracle/_ref/obj:
 
-    python tests/golden/make_golden_dropan.py
+    python tests/golden/make_golden_dropan.py [--patho-only]      (--patho-only: dropan_patho.npz alone, the five case files are left as they are)
 
 The reference tool is compiled into a temporary directory with make_golden_d8rev.build_tool; nothing is written under oracle/.  The inputs are those of
 case_<case>.npz: p, fel, and ad8 both as the area raster and as ssa (any raster that increases downstream serves).  dropan_<case>.npz holds
@@ -18,6 +18,12 @@ The parameters are chosen so that every run writes at least six rows, `plain`, `
 first row, and exactly one run (`fourway_mask`, arithmetic) has none.  The script asserts that the restatement's table equals the reference's byte for byte
 and that no |t| of the reference lies within 0.01 of 2 (console lines, every threshold): a condition on the inputs - if it fails, pick other parameters.
 The files are named dropan_*.npz, not case_*.npz: conftest.golden_cases() takes every case_*.npz as a case.
+
+dropan_patho.npz: the reference on the rasters of tests/pathological.py, one rank, both step types.  The inputs are not stored: dropan_strips.patho_case
+derives fel, p and ad8 from the generator's raster with the CPU oracle (30 x 30 cells, ssa = ad8), and the tests derive them again.  Per case <name> the
+file holds cols_<name>, rows_<name>, par_<name> and, per step type s, table_<name>_s and console_<name>_s.  A case the reference does not finish on (it is
+given PATHO_TIMEOUT seconds) is left out if no cell of it has a direction 1..8; any other failure stops the script.  Here too the restatement's table must
+equal the reference's byte for byte; rows, optimum and min ||t| - 2| are printed per run, and at the end the cases that were left out.
 """
 import os
 import sys
@@ -37,6 +43,7 @@ from oracle import oracle as O  # noqa: E402
 OUT = os.path.dirname(os.path.abspath(__file__))
 PAR = {"plain": (1, 30, 10), "holes": (3, 60, 10), "rect_dxdy": (2, 40, 14), "geographic": (1, 30, 10), "fourway_mask": (2, 40, 14)}
 NO_OPTIMUM = ("fourway_mask", 1)
+PATHO_TIMEOUT = 120
 
 
 def as_bytes(b):
@@ -55,20 +62,6 @@ def outlets(p, ad8):
                      and abs(int(p[r + R.DY_[k], c + R.DX_[k]]) - k) == 4]
             _, cols[i], rows[i] = max(feeds)
     return cols, rows
-
-
-def console_t(console):
-    """the Tval entries of the console lines that have one"""
-    lines = console.decode().split("\n")
-    first = next(i for i, ln in enumerate(lines) if ln.startswith("Threshold DrainDen"))
-    ts = []
-    for ln in lines[first + 1:]:
-        if "Value for optimum" in ln:
-            break
-        last = ln.replace(" - ", " x ").split()[-1]
-        if last != "x":
-            ts.append(float(last))
-    return np.array(ts)
 
 
 def make(exe, restate, name, ranks3=False):
@@ -105,7 +98,7 @@ def make(exe, restate, name, ranks3=False):
             r_exact, _ = M.parse_table(tab_exact)
             assert r_ref.shape == r_exact.shape and np.array_equal(r_ref[:, :4], r_exact[:, :4])
             res[f"noise_{st}"] = np.max(np.abs(r_ref[:, 4:] - r_exact[:, 4:]), axis=0)
-            ts = console_t(stdout.encode())
+            ts = M.console_t(stdout.encode())
             near = float(np.min(np.abs(np.abs(ts) - 2.0)))
             assert near > 0.01, f"{name} steptype {st}: a |t| within 0.01 of 2 ({near}): pick other parameters"
             assert len(r_ref) >= 6, f"{name} steptype {st}: {len(r_ref)} rows"
@@ -120,10 +113,58 @@ def make(exe, restate, name, ranks3=False):
     np.savez_compressed(os.path.join(OUT, f"dropan_{name}.npz"), **res)
 
 
+def make_patho(exe, restate):
+    import subprocess
+
+    import dropan_strips as S
+    import pathological as PG
+
+    res, left_out = {}, []
+    for name in sorted(PG.CASES):
+        c = S.patho_case(O, name)
+        p, fel, ad8, cols, rows, par = c["p"], c["fel"], c["ad8"], c["cols"], c["rows"], c["par"]
+        ny, nx = p.shape
+        dx, dy = c["dx"], c["dy"]
+        gt = (1000.0, dx, 0.0, 5000.0 + dy * ny, 0.0, -dy)
+        one = {f"cols_{name}": cols, f"rows_{name}": rows, f"par_{name}": np.array(par, np.float64)}
+        with tempfile.TemporaryDirectory() as d:
+            f = lambda s: os.path.join(d, s)  # noqa: E731
+            T.write_raster(f("p.tif"), p, M.P_NODATA, geotransform=gt)
+            T.write_raster(f("fel.tif"), fel, float(T.FEL_NODATA), geotransform=gt)
+            T.write_raster(f("ad8.tif"), ad8, -1.0, geotransform=gt)
+            with open(f("outlets.txt"), "w") as fo:
+                for i, (cx, r) in enumerate(zip(cols, rows)):
+                    fo.write(f"{float(gt[0] + (cx + 0.5) * dx)!r} {float(gt[3] - (r + 0.5) * dy)!r} {i + 1}\n")
+            try:
+                for st in (0, 1):
+                    args = ["-ad8", f("ad8.tif"), "-p", f("p.tif"), "-fel", f("fel.tif"), "-ssa", f("ad8.tif"), "-o", f("outlets.txt"), "-par", repr(par[0]), repr(par[1]), par[2], st]
+                    stdout, _, _ = O.run_ref(exe, args + ["-drp", f(f"drp{st}.txt")], timeout=PATHO_TIMEOUT)
+                    table = open(f(f"drp{st}.txt"), "rb").read()
+                    one[f"table_{name}_{st}"], one[f"console_{name}_{st}"] = as_bytes(table), as_bytes(stdout.encode())
+                    mine = restate.run(ad8, p, fel, ad8, cols, rows, dx, dy, par[0], par[1], par[2], st)
+                    assert mine["table"] == table, f"{name} steptype {st}: the restatement's table differs from the reference's\n{mine['table'].decode()}\n{table.decode()}"
+                    assert mine["console"].decode() in stdout, f"{name} steptype {st}: the restatement's console lines differ from the reference's\n{mine['console'].decode()}\n{stdout}"
+                    r_ref, opt = M.parse_table(table)
+                    ts = M.console_t(stdout.encode())
+                    ts = ts[np.isfinite(ts)]
+                    near = round(float(np.min(np.abs(np.abs(ts) - 2.0))), 4) if ts.size else None
+                    print(name, p.shape, "par", par, "steptype", st, "rows", len(r_ref), "optimum", opt if mine["optimum"] is not None else None, "min ||t| - 2|", near)
+            except (subprocess.TimeoutExpired, RuntimeError) as e:
+                assert not np.any((p >= 1) & (p <= 8)), f"{name}: the reference failed on a raster that has flow directions: {e}"
+                left_out.append(name)
+                print(name, p.shape, "par", par, "the reference did not finish:", type(e).__name__, str(e)[:200].replace("\n", " "))
+                continue
+        res.update(one)
+    print("left out:", left_out)
+    np.savez_compressed(os.path.join(OUT, "dropan_patho.npz"), **res)
+
+
 if __name__ == "__main__":
     O.build()
     with tempfile.TemporaryDirectory() as tmp:
         exe = R.build_tool(tmp, "dropanalysis", ("DropAnalysis", "DropAnalysismn"))
         restate = M.compile(tmp)
         for c in M.CASES:
-            make(exe, restate, c, ranks3=c in ("plain", "geographic"))
+            if "--patho-only" not in sys.argv:
+                make(exe, restate, c, ranks3=c in ("plain", "geographic"))
+        make_patho(exe, restate)

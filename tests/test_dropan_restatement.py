@@ -1,11 +1,14 @@
 """The serial restatement of DropAnalysis (tests/dropan_model.py) against the reference's 1-rank outputs (tests/golden/dropan_*.npz), byte for byte: on one
 rank the reference's queue order makes its float sums, and so its table, reproducible to the last digit.  The product's host formatting
 (tdx_dropanalysis_table: the ladder's thresholds, the reference's float / double expressions, the optimum) is then held to the same bytes, fed the
-restatement's float sums - no GPU.  CPU only."""
+restatement's float sums - no GPU.  The rasters of tests/pathological.py are held the same way: tests/golden/dropan_patho.npz has the reference's table and
+console bytes for inputs that dropan_strips.patho_case derives again here.  CPU only."""
 import numpy as np
 import pytest
 
 import dropan_model as M
+import dropan_strips as S
+import pathological as PG
 import taudem_amd as T
 
 RUNS = [(name, st) for name in M.CASES for st in (0, 1)]
@@ -32,7 +35,7 @@ def test_all_five_cases_have_a_fixture():
     import glob
     import os
 
-    assert sorted(os.path.basename(f)[7:-4] for f in glob.glob(os.path.join(M.GOLDEN, "dropan_*.npz"))) == sorted(M.CASES)
+    assert sorted(os.path.basename(f)[7:-4] for f in glob.glob(os.path.join(M.GOLDEN, "dropan_*.npz"))) == sorted(M.CASES + ("patho",))
 
 
 @pytest.mark.parametrize("name,st", RUNS)
@@ -91,3 +94,30 @@ def test_order_rule_is_not_strahler(restate):
         p, fel, ssa, (jx, jy) = DR.junction(orders)
         q = restate.threshold(p, fel, ssa, 1.0, 1.0, 1.0)
         assert q["order"][jy, jx] == want
+
+
+# ---- the rasters of tests/pathological.py ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def patho():
+    import os
+
+    return dict(np.load(os.path.join(M.GOLDEN, "dropan_patho.npz")))
+
+
+def test_every_pathological_case_has_the_reference_table(patho):
+    """the reference finished on all of them, the rasters without a single flow direction included"""
+    assert sorted(k[6:-2] for k in patho if k.startswith("table_") and k.endswith("_0")) == sorted(PG.CASES)
+
+
+@pytest.mark.parametrize("name", sorted(PG.CASES))
+def test_pathological_table_and_console_equal_reference(restate, oracle, patho, name):
+    c = S.patho_case(oracle, name)
+    assert np.array_equal(c["cols"], patho[f"cols_{name}"]) and np.array_equal(c["rows"], patho[f"rows_{name}"]) and tuple(patho[f"par_{name}"]) == c["par"]
+    for st in (0, 1):
+        r = restate.run(c["ad8"], c["p"], c["fel"], c["ad8"], c["cols"], c["rows"], c["dx"], c["dy"], *c["par"], st)
+        assert r["table"] == M.text_of(patho[f"table_{name}_{st}"]), (name, st)
+        assert r["console"].decode() in M.text_of(patho[f"console_{name}_{st}"]).decode(), (name, st)
+        s = np.array([q["s"] for q in r["per"]], np.float32)
+        table, console, opt = T.dropanalysis_table(r["thresh"], [q["n1"] for q in r["per"]], [q["n2"] for q in r["per"]], s[:, 0], s[:, 1], s[:, 2], s[:, 3],
+                                                   [q["length"] for q in r["per"]], r["total_area"])
+        assert table.encode() == r["table"] and console.encode() == r["console"] and (opt is None) == (r["optimum"] is None), (name, st)

@@ -21,7 +21,8 @@ import pytest
 import dropan_model as M
 import dropan_rasters as DR
 import taudem_amd as T
-from conftest import bits_equal, describe_diff
+from conftest import bits_equal
+from dropan_strips import check as _check, near as _near, outlets as _outlets   # shared with the strip and the pathological tests
 from taudem_amd import tools
 
 pytestmark = pytest.mark.gpu
@@ -77,45 +78,6 @@ def _terrain(ctx, oracle, shape, seed, dx=30.0, dy=30.0, holes=False):
     p, _ = ctx.d8flowdir(fel, float(T.FEL_NODATA), dx, dy)
     ad8 = ctx.aread8(p, contcheck=False)
     return fel, p, ad8
-
-
-def _outlets(p, ad8, n=3):
-    """the n largest-area cells that have a direction, one cell twice and one off the raster"""
-    ny, nx = p.shape
-    a = np.where((p >= 1) & (p <= 8), ad8, -2.0).ravel()
-    idx = np.argsort(-a, kind="stable")[:n]
-    idx = idx[a[idx] > -2.0]
-    cols, rows = list(idx % nx) + [nx + 3], list(idx // nx) + [0]
-    if len(idx):
-        cols.append(cols[0])
-        rows.append(rows[0])
-    return np.array(cols, np.int32), np.array(rows, np.int32)
-
-
-def _check(ctx, restate, ad8, p, fel, ssa, cols, rows, dx, dy, par, st, what, grid_th=1, ssa_nodata=-1.0):
-    """One run against the restatement: everything exact but the four sums and the length, which are held to the fp64 bounds of the docstring."""
-    ny, nx = p.shape
-    dxc, dyc = M._f64(dx, ny), M._f64(dy, ny)
-    thresh, n1, n2, sums, length, area, table, opt, order, elev = ctx.dropanalysis(ad8, p, fel, ssa, (cols, rows), thresh_min=par[0], thresh_max=par[1], nthresh=par[2],
-                                                                                   steptype=st, dx=dx, dy=dy, ssa_nodata=ssa_nodata, grids=grid_th)
-    ref = restate.run(ad8, p, fel, ssa, cols, rows, dxc, dyc, par[0], par[1], par[2], st, ssa_nodata=ssa_nodata)
-    assert bits_equal(thresh, ref["thresh"]), f"{what}: ladder"
-    assert bits_equal(np.float32(area).reshape(1), np.float32(ref["total_area"]).reshape(1)), f"{what}: total area {area} vs {ref['total_area']}"
-    for th, q in enumerate(ref["per"]):
-        assert (int(n1[th]), int(n2[th])) == (q["n1"], q["n2"]), f"{what}: n1, n2 of threshold {th}"
-        exact, mag = M.sums_from_drops(q["drops1"], q["drops2"]), M.abs_sums_from_drops(q["drops1"], q["drops2"])
-        for k, nterms in enumerate((q["n1"], q["n1"], q["n2"], q["n2"])):
-            assert abs(float(sums[th, k]) - exact[k]) <= M.gamma(max(nterms, 1)) * mag[k], f"{what}: sum {k} of threshold {th}: {sums[th, k]!r} vs {exact[k]!r}"
-        want_len, links = M.exact_length(q["order"], p, dxc, dyc)
-        assert abs(float(length[th]) - want_len) <= M.gamma(links + 3 * ny) * want_len, f"{what}: length of threshold {th}: {length[th]!r} vs {want_len!r}"
-    q = ref["per"][grid_th]
-    assert bits_equal(order, q["order"]), describe_diff(order, q["order"], f"{what}: order grid")
-    assert bits_equal(elev, q["elev"]), describe_diff(elev, q["elev"], f"{what}: elevOut grid")
-    # the table from our sums: the rows that appear and the optimum are the restatement's wherever no |t| is near 2
-    got, _ = M.parse_table(table.encode())
-    want, _ = M.parse_table(ref["table"])
-    assert np.array_equal(got[:, [0, 2, 3]], want[:, [0, 2, 3]]), f"{what}: rows of the table"
-    return ref, (thresh, n1, n2, sums, length, area, table, opt)
 
 
 @pytest.mark.parametrize("shape,holes", [((1, 97), False), ((97, 1), False), ((65, 67), False), ((130, 70), False), ((2048, 64), True)])
@@ -294,15 +256,6 @@ def _write_case(tmp_path, g, name="plain"):
         for i, (c, r) in enumerate(zip(g["cols"], g["rows"])):
             fo.write(f"{float(gt[0] + (c + 0.5) * dx)!r} {float(gt[3] - (r + 0.5) * dy)!r} {i + 1}\n")
     return f, gt
-
-
-def _near(got, want, noise):
-    """Tables of two summation orders (two strips add their fp64 sums in strip order): the same rows and optimum, and the printed values as close as the
-    golden test asks of two summation orders - DrainDen 2e-6 relative, the other columns 2 * noise + 2e-6."""
-    a, oa = M.parse_table(got)
-    b, ob = M.parse_table(want)
-    return (oa == ob and a.shape == b.shape and np.array_equal(a[:, [0, 2, 3]], b[:, [0, 2, 3]]) and bool(np.all(np.abs(a[:, 1] - b[:, 1]) <= 2e-6 * np.abs(b[:, 1])))
-            and bool(np.all(np.abs(a[:, 4:] - b[:, 4:]) <= 2.0 * noise + 2e-6)))
 
 
 @pytest.mark.parametrize("name", ["plain", "geographic"])
