@@ -272,13 +272,18 @@ __global__ __launch_bounds__(256) void ad8_halo_kernel(const int16_t* __restrict
 //                              code in it 1 .. 8 (no nodata, no p == 0, no sink, nothing else), no cycle.  There every cell takes part, none is contaminated or
 //                              poisoned, and a cell's count is the size of its in-tile upstream subtree - no in-degrees, no order: pointer doubling (acc = 1,
 //                              nxt = in-tile target; a round adds every live cell's PREVIOUS acc to acc[nxt] and replaces nxt by nxt[nxt]; after round k acc
-//                              counts the cells less than 2^(k+1) hops upstream; at most 12 rounds, a pointer still live after the 12th is a cycle).  It writes
-//                              what A writes for such a tile, byte for byte.  Any other tile writes only its index into a redo list, and A runs right behind
-//                              on the same stream over that list (device-side count, no host synchronisation).  TDX_AD8_LOCAL=kahn: A alone on every tile.
+//                              counts the cells less than 2^(k+1) hops upstream; at most 12 rounds, a pointer still live after the 12th is a cycle).  Nothing is
+//                              staged: the codes come straight into registers.  A dead pointer holds the exit cell of its path (the root), so next(node) of an
+//                              entering crossing is one read of its entry cell after the last round - no walk.  It writes what A writes for such a tile, and into
+//                              the per-cell word also the cell's direction code above the count (CW_CODE_SHIFT): the mark "finished here".  Any other tile writes
+//                              only its index into a redo list, and A runs right behind on the same stream over that list (device-side count, no host
+//                              synchronisation).  TDX_AD8_LOCAL=kahn: A alone on every tile, C on every tile.
 //   B  ad8_forest_walk_kernel  the walk of ad8_walk_kernel on the crossing forest (nodes = perimeter
 //                              cells, ~1/16 of the cells, paths ~64x shorter), integer packed atomics.
 //   C  ad8_tile_apply_kernel   per tile, in LDS: add the flow of every entering crossing along its
-//                              in-tile path, convert to float32, apply contamination, write ad8.
+//                              in-tile path, convert to float32, apply contamination, write ad8.  It serves the redo list of A'.
+//   C' ad8_tile_apply_fast_kernel  the same for the tiles that A' finished, from their marked words alone: targets from the code in the word, no staged
+//                              window, no read of p's tile interior.  TDX_AD8_APPLY=full: A' writes plain words and C serves every tile.
 //   D  big cells (count > 2^24, where float32 adds round and the k order of src/aread8.cpp:239-256
 //                              matters) are re-evaluated with the exact k-ordered pull of ad8_evaluate in
 //                              dependency order (ad8_big_* kernels): the main stems - a few thousand cells
@@ -336,6 +341,13 @@ __device__ __forceinline__ unsigned nw_con(unsigned long long w) { return unsign
 __device__ __forceinline__ unsigned nw_poi(unsigned long long w) { return unsigned(w >> 52) & 1023u; }
 // per-cell word between phases A and C: cnt[0:30) contam[30] poison[31]
 __device__ __forceinline__ uint32_t cw_pack(unsigned cnt, bool con, bool poi) { return cnt | (con ? 1u << 30 : 0u) | (poi ? 1u << 31 : 0u); }
+// A word of a tile that ad8_tile_fast_kernel finished also carries the cell's direction code 1 .. 8 above its count (at most 4096: bits 0 .. 12), so that
+// ad8_tile_apply_fast_kernel needs no p.  ad8_tile_local_kernel's counts are 13 bits wide as well (lw_cnt) and leave the field zero: a non-zero field says
+// "finished by the fast kernel", for all cells of a tile alike.  A big cell's word is the plain exact count again (the sort key of ad8_big_keys_kernel).
+constexpr int CW_CODE_SHIFT = 13;
+constexpr uint32_t CW_CODE_MASK = 15u << CW_CODE_SHIFT, CW_FAST_CNT_MASK = (1u << CW_CODE_SHIFT) - 1u;
+static_assert((CW_CODE_MASK & (CW_FAST_CNT_MASK | (1u << 30) | (1u << 31))) == 0u && CW_FAST_CNT_MASK >= 4096u, "the code field touches neither a clean tile's count nor the flags");
+__device__ __forceinline__ unsigned cw_code(uint32_t w) { return (w & CW_CODE_MASK) >> CW_CODE_SHIFT; }
 
 // position of a perimeter cell (lx, ly) of a tile with rv valid rows in its 256-entry node block
 __device__ __forceinline__ int perim_pos(int lx, int ly, int rv) {
@@ -592,65 +604,66 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
 #undef AD8_MARK
 }
 
-// Stage P (tile + ring) as raw codes, one byte per cell at 66-pitch: the code where it is 1 .. 8 and the cell lies inside the array and is not nodata, 0 otherwise.
-// Returns whether this lane staged a 0: the tile is then not clean.  (Loads in two batches, addresses clamped: as stage_p_onehot.)
-__device__ __forceinline__ bool stage_p_raw(const int16_t* __restrict__ P, int nx, int ny_arr, int x0, int ya0, int16_t nodata, uint8_t* sC) {
-    constexpr int NIT = (TH * TH + 255) / 256, HALF = (NIT + 1) / 2;
-    bool bad = false;
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-        int16_t v[HALF];
-        unsigned ok = 0;
-#pragma unroll
-        for (int i = 0; i < HALF; i++) {
-            const int e = int(threadIdx.x) + (b * HALF + i) * 256, ec = e < TH * TH ? e : TH * TH - 1;
-            const int ly = ec / TH, lx = ec - ly * TH;
-            const int gx = x0 + lx - 1, gy = ya0 + ly - 1;
-            const int gxc = gx < 0 ? 0 : (gx >= nx ? nx - 1 : gx), gyc = gy < 0 ? 0 : (gy >= ny_arr ? ny_arr - 1 : gy);
-            v[i] = P[size_t(gyc) * size_t(nx) + size_t(gxc)];
-            if (gx == gxc && gy == gyc) ok |= 1u << i;
-        }
-#pragma unroll
-        for (int i = 0; i < HALF; i++) {
-            const int e = int(threadIdx.x) + (b * HALF + i) * 256;
-            if (b * HALF + i < NIT && e < TH * TH) {
-                const bool good = ((ok >> i) & 1u) && v[i] != nodata && unsigned(int(v[i]) - 1) < 8u;
-                sC[e] = good ? uint8_t(v[i]) : uint8_t(0);
-                bad |= !good;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return bad;
+// a code of a clean window: not nodata and 1 .. 8
+__device__ __forceinline__ bool ad8_code_good(int16_t v, int16_t nodata) { return v != nodata && unsigned(int(v) - 1) < 8u; }
+// ring cell (ring_cell() order) of a lane's slot k of a whole tile.  The ring has 260 cells: a lane without a second one gets the last cell again and `false`,
+// so that its address is one of the window's all the same.
+__device__ __forceinline__ bool ring_slot(int tid, int k, int& hx, int& hy) {
+    const int j = tid + 256 * k;
+    const bool has = j < 2 * TH + 2 * TS;
+    (void)ring_cell(has ? j : 2 * TH + 2 * TS - 1, TS, hx, hy);
+    return has;
 }
 
 // TDX_AD8_DEBUG=1: ad8_tile_fast_kernel, summed over the clean tiles (thread 0): [0, 5) phase cycles, [5] doubling rounds, [6] tiles
 __device__ unsigned long long g_ad8_dbg_fast[8];
 constexpr int AD8_MAX_ROUNDS = 12;   // an acyclic in-tile path has at most 4095 hops < 2^12
-// Phase A' (see the block comment above).  25.6 KB of LDS: the staged codes (bytes, 66-pitch) and - once every lane holds the targets of its own 16 cells and the ring
-// lanes their entry cells - the 64-pitch table of pointers share one region.
+// Phase A' (see the block comment above).  25.9 KB of LDS: six tiles per CU.  Nothing is staged: a lane reads the codes of its own 16 cells (a wave row of the tile is one aligned
+// 128-byte line of p) and of its ring cells - ring_cell() order, two per lane at most - straight into registers, all loads back to back; the "clean" vote, the
+// targets and the entry cells come from those registers, and the 64-pitch pointer table is written once.
+//
+// A pointer is LIVE (>= 0: the cell 2^k hops downstream) or DEAD (< 0: ~root, root = the exit cell of the cell's path; an exit starts dead with itself as root).
+// A live cell whose pointer reads a dead entry dies and takes that entry over, root included: the roots travel up the paths with the deaths, one round behind -
+// by the round in which a cell reads an entry as dead, that entry's root is final.  (The cell that a dying pointer held is NOT the root: three hops above an
+// exit, the pointer spans two hops after round 1 and dies in round 2 on the cell ONE hop above the exit.)  After the last round the table holds the root of
+// every cell, so the exit of an entering crossing is one read of its entry cell's word - no walk.
+// mark: the words carry the direction code (CW_CODE_SHIFT) for ad8_tile_apply_fast_kernel; 0 (TDX_AD8_APPLY=full): plain words.
 template <bool DBG>
 __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
                                                             uint32_t* __restrict__ cellw, unsigned long long* __restrict__ node_acc,
                                                             uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next,
-                                                            uint32_t* __restrict__ redo, unsigned long long* __restrict__ nredo) {
+                                                            uint32_t* __restrict__ redo, unsigned long long* __restrict__ nredo, unsigned mark) {
     unsigned long long tcs[6];
 #define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
     AD8_MARK(0);
-    __shared__ int16_t sT[TS * TS];       // while staging: TH * TH bytes of codes
+    __shared__ int16_t sT[TS * TS];
     __shared__ unsigned sAcc[TS * TS];
     __shared__ unsigned sIn[256];         // crossings that end at each perimeter cell
-    __shared__ unsigned sVote[3][4];      // per wave: "staged a cell that is not 1 .. 8", "a pointer is live" of the even / odd rounds
-    static_assert(TH * TH <= int(sizeof(int16_t)) * TS * TS, "the staged codes fit the pointer table");
-    uint8_t* const sC = reinterpret_cast<uint8_t*>(sT);
+    __shared__ unsigned sVote[3][4];      // per wave: "read a code that is not 1 .. 8", "a pointer is live" of the even / odd rounds
+    __shared__ uint8_t sRc[256];          // per lane: the codes of its two ring cells, four bits each
     const int tile = blockIdx.x;
     const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
     const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
-    const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16, wave = tid >> 6;
-    // all rows valid and the window inside the array: uniform, and nothing is staged otherwise
-    bool bad = rv != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr;
-    if (!bad) bad = stage_p_raw(P, g.nx, g.ny_arr, x0, ya0, nodata, sC);
+    // (the wave's number as a scalar: the rows of a lane's 16 cells are then scalars too - row addresses and cell indices take no vector registers)
+    const int tid = threadIdx.x, lx = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ry0 = wave * 16;
+    // all rows valid and the window inside the array: uniform for the workgroup, and nothing is read otherwise
+    if (rv != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr) {
+        if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+        return;
+    }
+    int16_t pc[16], pr[2];
+#pragma unroll
+    for (int r = 0; r < 16; r++) pc[r] = (P + (size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0)))[unsigned(lx)];   // (a scalar row address and the lane's column)
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        int hx, hy;
+        (void)ring_slot(tid, k, hx, hy);
+        pr[k] = P[size_t(ya0 + hy) * size_t(g.nx) + size_t(x0 + hx)];
+    }
     sIn[tid] = 0u;
+    bool bad = !ad8_code_good(pr[0], nodata) || !ad8_code_good(pr[1], nodata);
+#pragma unroll
+    for (int r = 0; r < 16; r++) bad |= !ad8_code_good(pc[r], nodata);
     const bool wave_bad = __ballot(bad) != 0ull;   // (the ballot by ALL lanes, not under the branch of the lane that stores it)
     if (lx == 0) sVote[0][wave] = wave_bad ? 1u : 0u;
     __syncthreads();
@@ -659,60 +672,27 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
         return;
     }
     AD8_MARK(1);
-    // a lane's own 16 codes -> in-tile target, or -2: the crossing leaves the tile (its target takes part, like everything in the window)
-    unsigned exits = 0, exit_up = 0, exit_down = 0;
+    // a lane's own 16 codes -> in-tile target, or ~(own cell): the crossing leaves the tile (its target takes part, like everything in the window)
+    // The rounds have no register to spare at six tiles per CU, so the codes are not kept in any: a cell's code rides in its sAcc word above the count, where
+    // the per-cell word has it (CW_CODE_SHIFT; an acyclic tile's counts stay below 2^13 in every round, and a cyclic tile writes nothing), and what the write-back
+    // needs again - exits, their row steps, the ring cells - is derived from the codes once more.
+    unsigned exits = 0;
     int16_t ptr[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int ly = ry0 + r;
-        const int p = sC[(ly + 1) * TH + lx + 1];
+        const int p = pc[r];
         const int tlx = lx + d1(p), tly = ly + d2(p);
         const bool in = in_tile(tlx, tly, TS);
-        ptr[r] = int16_t(in ? tly * TS + tlx : -2);
-        if (!in) {
-            exits |= 1u << r;
-            if (d2(p) < 0) exit_up |= 1u << r;
-            if (d2(p) > 0) exit_down |= 1u << r;
-        }
+        ptr[r] = int16_t(in ? tly * TS + tlx : ~(ly * TS + lx));
+        if (!in) exits |= 1u << r;
+        sT[ly * TS + lx] = ptr[r];
+        sAcc[ly * TS + lx] = 1u | (unsigned(p) << CW_CODE_SHIFT);
     }
-    // ring cells (ring_cell() order, two per lane at most) whose flow enters the tile: the entry cell, or -1
-    int ent[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int j = tid + 256 * k;
-        int hx, hy;
-        ent[k] = -1;
-        if (j < 4 * TH && ring_cell(j, TS, hx, hy)) {
-            const int ph = sC[(hy + 1) * TH + hx + 1];
-            const int vx = hx + d1(ph), vy = hy + d2(ph);
-            if (in_tile(vx, vy, TS)) ent[k] = vy * TS + vx;
-        }
-    }
-    __syncthreads();   // every lane is done reading codes: the pointer table takes their place
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        sT[(ry0 + r) * TS + lx] = ptr[r];
-        sAcc[(ry0 + r) * TS + lx] = 1u;
-    }
+    sRc[tid] = uint8_t(unsigned(pr[0]) | (unsigned(pr[1]) << 4));   // the ring cells' codes wait in LDS as well
     __syncthreads();
     AD8_MARK(2);
-    // Crossings that enter the tile: follow the in-tile path of the entry cell to where it leaves - now, on the table of TARGETS, which the doubling overwrites.
-    // (Bounded by the tile's cell count: on a cycle the walk may end nowhere; the tile is then redone.)  node_next is written once the tile is known to be clean.
-    uint32_t ent_next[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        ent_next[k] = NEXT_NONE;
-        if (ent[k] < 0) continue;
-        int cur = ent[k], hops = 0;
-        while (sT[cur] >= 0 && hops < TS * TS) { cur = sT[cur]; hops++; }
-        if (sT[cur] == -2) {
-            const int pp = perim_pos(cur % TS, cur / TS, TS);
-            atomicAdd(&sIn[pp], 1u);
-            ent_next[k] = uint32_t(tile) * 256u + uint32_t(pp);
-        }
-    }
-    __syncthreads();
-    AD8_MARK(3);
+    AD8_MARK(3);   // (the entry walks that stood here are gone: their clock reads 0)
     // Pointer doubling.  Phase 1 reads nxt[n] and adds the lane's previous acc to acc[n] (non-returning atomics, all independent); phase 2 publishes the new pointers
     // and re-reads the own acc of the cells that go on.  (Both in one phase would mix pointers of two generations: the invariant needs exact powers of two.)
     unsigned acc[16];
@@ -737,7 +717,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
                 ptr[r] = int16_t(nn[r]);
                 sT[c] = int16_t(nn[r]);
                 if (nn[r] < 0) live &= ~(1u << r);
-                else acc[r] = sAcc[c];
+                else acc[r] = sAcc[c] & CW_FAST_CNT_MASK;
             }
         rounds++;
         const bool wave_live = __ballot(live != 0u) != 0ull;
@@ -751,24 +731,37 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
         }
     }
     AD8_MARK(4);
+    // crossings that enter the tile end at the root of their entry cell (every pointer is dead: the vote's barrier stands behind the last publication)
+    int tid_again = tid;   // (opaque: the ring cells' coordinates and the column's neighbours are derived again here, not carried through the rounds)
+    asm volatile("" : "+v"(tid_again));
+    const int lxw = tid_again & 63;
+    const unsigned rcodes = sRc[tid_again];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-        const int j = tid + 256 * k;
         int hx, hy;
-        if (ent[k] >= 0 && ring_cell(j, TS, hx, hy)) node_next[node_id(g, x0 + hx, ya0 + hy)] = ent_next[k];
+        const bool has = ring_slot(tid_again, k, hx, hy);
+        const int ph = int((rcodes >> (4 * k)) & 15u);
+        const int vx = hx + d1(ph), vy = hy + d2(ph);
+        if (!has || !in_tile(vx, vy, TS)) continue;   // no ring cell, or its flow does not enter the tile
+        const int root = ~int(sT[vy * TS + vx]);
+        const int pp = perim_pos(root % TS, root / TS, TS);
+        atomicAdd(&sIn[pp], 1u);
+        node_next[node_id(g, x0 + hx, ya0 + hy)] = uint32_t(tile) * 256u + uint32_t(pp);
     }
+    __syncthreads();
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int ly = ry0 + r, c = ly * TS + lx;
+        const int lx = lxw, ly = ry0 + r, c = ly * TS + lx;
         const int gx = x0 + lx, gy = ya0 + ly;
-        const unsigned cnt = sAcc[c];
-        cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = cw_pack(cnt, false, false);
-        if ((exits >> r) & 1u) {
+        const unsigned w = sAcc[c], cnt = w & CW_FAST_CNT_MASK;   // count and code as the per-cell word holds them
+        const int p = int(cw_code(w));
+        cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = mark ? w : cw_pack(cnt, false, false);
+        if (!in_tile(lx + d1(p), ly + d2(p), TS)) {
             const int pp = perim_pos(lx, ly, TS);
             const uint32_t nid = uint32_t(tile) * 256u + uint32_t(pp);
             node_acc[nid] = nw_pack(cnt, 0u, 0u, 0u);
             node_indeg[nid] = sIn[pp];
-            const int tgy = gy + (((exit_up >> r) & 1u) ? -1 : (((exit_down >> r) & 1u) ? 1 : 0));
+            const int tgy = gy + d2(p);
             if (tgy < g.y0) node_next[nid] = NEXT_REMOTE_UP;        // the tile that would record next(node) lives on another rank
             else if (tgy >= g.y1) node_next[nid] = NEXT_REMOTE_DOWN;
         }
@@ -846,11 +839,22 @@ __global__ __launch_bounds__(256) void ad8_forest_deliver_kernel(Ad8Geom g, cons
 
 // LDS word of the apply pass: cnt[0:32) contam[32:44) poison[44:56)
 // (93 VGPRs: five tiles per CU.  Held to 80 - six tiles, as the LDS allows - it spills 15 registers in the first phase and is 13 % slower: profiles/r05l_*)
+// list / nlist: the redo list of ad8_tile_fast_kernel and its device-side length (one workgroup per tile of the raster, as the redo launch of ad8_tile_local_kernel);
+// null: every tile
+// TDX_AD8_DEBUG=1: phase cycles of ad8_tile_apply_kernel ([0, 4): stage, topology, entry walks, write-back; [4] tiles) and, from [8], of ad8_tile_apply_fast_kernel
+// ([8, 12): load, targets, entry walks, write-back; [12] tiles), summed over the tiles (thread 0)
+__device__ unsigned long long g_ad8_dbg_apply[16];
+template <bool DBG>
 __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
                                                              uint32_t* __restrict__ cellw, const unsigned long long* __restrict__ node_acc,
                                                              const uint32_t* __restrict__ node_indeg, int contcheck, unsigned big_threshold,
                                                              float* __restrict__ A, uint32_t* __restrict__ biglist,
-                                                             unsigned long long* __restrict__ nbig) {
+                                                             unsigned long long* __restrict__ nbig,
+                                                             const uint32_t* __restrict__ list, const unsigned long long* __restrict__ nlist) {
+    if (list && blockIdx.x >= *nlist) return;
+    unsigned long long tcs[5];
+#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
+    AD8_MARK(0);
     // 26 KB of LDS per tile: counts (32 bit), the two flags as a bit set, and the staged tile of one-hot direction codes, which the 64-pitch table of
     // in-tile targets replaces once the topology has been derived (the ring's codes set aside in sRing) - as in ad8_tile_local_kernel
     __shared__ uint16_t sO[TH * TH];
@@ -858,13 +862,14 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
     __shared__ unsigned sFlag[TS * TS / 16];   // 2 bits per cell: contaminated, not evaluated
     __shared__ uint16_t sRing[4 * TH];
     int16_t* const sT = reinterpret_cast<int16_t*>(sO);
-    const int tile = blockIdx.x;
+    const int tile = list ? int(list[blockIdx.x]) : int(blockIdx.x);
     const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
     const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
     const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16;
     stage_p_onehot(P, g.nx, g.ny_arr, x0, ya0, nodata, sO);
     sFlag[tid] = 0u;
     __syncthreads();
+    AD8_MARK(1);
     for (int j = tid; j < 4 * TH; j += 256) {
         int hx, hy;
         sRing[j] = ring_cell(j, rv, hx, hy) ? sO[(hy + 1) * TH + hx + 1] : uint16_t(0);
@@ -918,6 +923,7 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
         if (ry0 + r < rv) sT[(ry0 + r) * TS + lx] = (tgt[r] >= 0) ? tgt[r] : (((partmask >> r) & 1u) ? int16_t(-3) : int16_t(-1));
     }
     __syncthreads();
+    AD8_MARK(2);
     for (int j = tid; j < 4 * TH; j += 256) {
         int hx, hy;
         if (!ring_cell(j, rv, hx, hy)) continue;
@@ -942,6 +948,7 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
         }
     }
     __syncthreads();
+    AD8_MARK(3);
     unsigned bigmask = 0;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -965,6 +972,113 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
 #pragma unroll
     for (int r = 0; r < 16; r++)
         if (bigmask & (1u << r)) biglist[pos++] = uint32_t(size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0 + lx));
+    if (DBG) {
+        __syncthreads();
+        AD8_MARK(4);
+        if (tid == 0) {
+            for (int i = 0; i < 4; i++) atomicAdd(&g_ad8_dbg_apply[i], tcs[i + 1] - tcs[i]);
+            atomicAdd(&g_ad8_dbg_apply[4], 1ull);
+        }
+    }
+#undef AD8_MARK
+}
+
+// Phase C of the tiles that ad8_tile_fast_kernel finished: their words are marked (cw_code != 0) and carry each cell's direction, so nothing of p's tile interior
+// is read and nothing is staged - the words and the ring cells' codes come straight into registers, all loads back to back.  Launched over every tile; a tile
+// whose words are not marked leaves at once (ad8_tile_apply_kernel serves it from the redo list).  In a clean window every cell takes part and every code is
+// 1 .. 8: no participation tests, a target is in the tile or it is not.  What enters from upstream may be contaminated, not evaluated or never delivered, like
+// anywhere else.  25 KB of LDS: six tiles per CU.
+template <bool DBG>
+__global__ __launch_bounds__(256, 6) void ad8_tile_apply_fast_kernel(const int16_t* __restrict__ P, Ad8Geom g, uint32_t* __restrict__ cellw,
+                                                                  const unsigned long long* __restrict__ node_acc, const uint32_t* __restrict__ node_indeg,
+                                                                  int contcheck, unsigned big_threshold, float* __restrict__ A, uint32_t* __restrict__ biglist,
+                                                                  unsigned long long* __restrict__ nbig) {
+    unsigned long long tcs[5];
+#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
+    AD8_MARK(0);
+    __shared__ int16_t sT[TS * TS];
+    __shared__ unsigned sCnt[TS * TS];
+    __shared__ unsigned sFlag[TS * TS / 16];   // 2 bits per cell: contaminated, not evaluated
+    const int tile = blockIdx.x;
+    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
+    const int x0 = tx * TS, ya0 = g.y0 + ty * TS;
+    const int tid = threadIdx.x, lx = tid & 63, ry0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 16;   // (a scalar: as in ad8_tile_fast_kernel)
+    // (the fast kernel's uniform test: no other tile holds marked words, and with it every address below lies in the array)
+    if (rows_valid(g, ty) != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr) return;
+    uint32_t cw[16];
+    int16_t pr[2];
+    int rhx[2], rhy[2];
+    bool rhas[2];
+#pragma unroll
+    for (int r = 0; r < 16; r++) cw[r] = (cellw + (size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0)))[unsigned(lx)];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        rhas[k] = ring_slot(tid, k, rhx[k], rhy[k]);
+        pr[k] = P[size_t(ya0 + rhy[k]) * size_t(g.nx) + size_t(x0 + rhx[k])];
+    }
+    if (cw_code(cw[0]) == 0u) return;   // not finished by the fast kernel; all words of a tile are marked alike, so the workgroup leaves as one
+    AD8_MARK(1);
+    sFlag[tid] = 0u;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int ly = ry0 + r;
+        const int p = int(cw_code(cw[r]));
+        const int tlx = lx + d1(p), tly = ly + d2(p);
+        sT[ly * TS + lx] = int16_t(in_tile(tlx, tly, TS) ? tly * TS + tlx : -1);
+        sCnt[ly * TS + lx] = cw[r] & CW_FAST_CNT_MASK;
+    }
+    __syncthreads();
+    AD8_MARK(2);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int ph = pr[k];   // 1 .. 8: the window is clean
+        const int vx = rhx[k] + d1(ph), vy = rhy[k] + d2(ph);
+        if (!rhas[k] || !in_tile(vx, vy, TS)) continue;
+        int cur = vy * TS + vx, hops = 0;
+        const uint32_t nid = node_id(g, x0 + rhx[k], ya0 + rhy[k]);
+        const uint32_t ind = node_indeg[nid];
+        const unsigned long long w = node_acc[nid];
+        unsigned addc = 0, addf = 2u;     // a crossing that never delivers leaves everything below it unevaluated
+        if (ind < NODE_DEAD && nw_arr(w) == ind) { addc = unsigned(w); addf = (nw_con(w) ? 1u : 0u) | (nw_poi(w) ? 2u : 0u); }
+        for (;;) {
+            if (addc) __hip_atomic_fetch_add(&sCnt[cur], addc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (addf) atomicOr(&sFlag[cur >> 4], addf << (2 * (cur & 15)));
+            const int t = sT[cur];
+            if (t < 0 || ++hops >= TS * TS) break;
+            cur = t;
+        }
+    }
+    __syncthreads();
+    AD8_MARK(3);
+    unsigned bigmask = 0;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int ly = ry0 + r, c = ly * TS + lx;
+        const size_t idx = size_t(ya0 + ly) * size_t(g.nx) + size_t(x0 + lx);
+        const unsigned cnt = sCnt[c];
+        const unsigned fl = (sFlag[c >> 4] >> (2 * (c & 15))) & 3u;
+        const bool con = (fl & 1u) != 0u, poi = (fl & 2u) != 0u;
+        float a = TDX_AREA_NODATA;
+        if (!poi && !(con && contcheck == 1)) {
+            if (cnt > big_threshold) { a = BIG_MARK; bigmask |= 1u << r; cellw[idx] = cnt; }   // the plain count: ad8_big_keys_kernel sorts by this word
+            else a = (float)cnt;   // exact: cnt <= 2^24
+        }
+        A[idx] = a;
+    }
+    const unsigned long long pos0 = block_reserve(unsigned(__popc(bigmask)), nbig);
+    unsigned long long pos = pos0;
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        if (bigmask & (1u << r)) biglist[pos++] = uint32_t(size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0 + lx));
+    if (DBG) {
+        __syncthreads();
+        AD8_MARK(4);
+        if (tid == 0) {
+            for (int i = 0; i < 4; i++) atomicAdd(&g_ad8_dbg_apply[8 + i], tcs[i + 1] - tcs[i]);
+            atomicAdd(&g_ad8_dbg_apply[12], 1ull);
+        }
+    }
+#undef AD8_MARK
 }
 
 // ---- big cells: exact k-ordered float32 re-evaluation in dependency order ----
@@ -1345,6 +1459,9 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
     if (!cellw || !node_acc || !node_indeg || !node_next || !biglist || !boxes || !delivered || !redo) return TDX_ERR_NOMEM;
     const char* const ad8_local = getenv("TDX_AD8_LOCAL");   // "kahn": every tile to ad8_tile_local_kernel (A/B hook and witness, read per call)
     const bool kahn_only = ad8_local && strcmp(ad8_local, "kahn") == 0;
+    const char* const ad8_apply = getenv("TDX_AD8_APPLY");   // "full": plain words from the fast kernel, ad8_tile_apply_kernel on every tile (A/B hook, read per call)
+    const bool apply_fast = !kahn_only && !(ad8_apply && strcmp(ad8_apply, "full") == 0);
+    const unsigned mark = apply_fast ? 1u : 0u;
     unsigned long long *outbox = boxes, *inbox = boxes + 2 * size_t(st.nx);
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ctx->d_mail);
     unsigned long long* nredo = d_cnt + 7;   // (cleared with the other stage counters by ad8_init_kernel)
@@ -1366,7 +1483,7 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
             TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg), z, sizeof(z)));
             TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg_fast), zf, sizeof(zf)));
             if (!kahn_only)
-                hipLaunchKernelGGL((ad8_tile_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo);
+                hipLaunchKernelGGL((ad8_tile_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo, mark);
             hipLaunchKernelGGL((ad8_tile_local_kernel<true, true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
             TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
             TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_dbg), sizeof(z)));
@@ -1377,11 +1494,11 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
             fprintf(stderr, "ad8_tile_local: %llu tiles, cycles per tile: stage %.0f, topology %.0f, targets %.0f, Kahn walks %.0f, entry walks %.0f, write-back %.0f\n", nr,
                     double(z[0]) / nk, double(z[1]) / nk, 0.0, double(z[2]) / nk, double(z[3]) / nk, double(z[4]) / nk);
             if (!kahn_only)
-                fprintf(stderr, "ad8_tile_fast: %llu tiles, cycles per tile: stage %.0f, targets %.0f, entry walks %.0f, doubling %.0f, write-back %.0f; %.2f rounds per tile\n", zf[6],
+                fprintf(stderr, "ad8_tile_fast: %llu tiles, cycles per tile: load and vote %.0f, targets %.0f, entry walks %.0f, doubling %.0f, roots and write-back %.0f; %.2f rounds per tile\n", zf[6],
                         double(zf[0]) / nf, double(zf[1]) / nf, double(zf[2]) / nf, double(zf[3]) / nf, double(zf[4]) / nf, double(zf[5]) / nf);
         } else {
             if (!kahn_only)
-                hipLaunchKernelGGL((ad8_tile_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo);
+                hipLaunchKernelGGL((ad8_tile_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo, mark);
             if (getenv("TDX_AD8_KAHN_NESTED"))   // (A/B hook, read per call: the walk loop nested in the loop over a lane's sources)
                 hipLaunchKernelGGL((ad8_tile_local_kernel<false, false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
             else
@@ -1415,9 +1532,33 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
     ctx->phase = "apply";
     {
         TdxSpan sp(ctx, TDX_K_STENCIL);
-        hipLaunchKernelGGL(ad8_tile_apply_kernel, dim3(unsigned(ntiles)), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck,
-                           big_threshold, d_ad8, biglist, d_cnt);
-        if (stats) stats->launches[TDX_K_STENCIL]++;
+        // the tiles with marked words by ad8_tile_apply_fast_kernel, the redo list of the fast kernel (untouched since: nothing else uses its scratch slot or
+        // stage counter 7 in this call) by ad8_tile_apply_kernel right behind it; without marks - TDX_AD8_LOCAL=kahn, TDX_AD8_APPLY=full - the latter on every tile
+        static const bool ad8_debug = getenv("TDX_AD8_DEBUG") != nullptr;
+        const unsigned nt = unsigned(ntiles);
+        const uint32_t* list = apply_fast ? redo : nullptr;
+        if (ad8_debug) {
+            unsigned long long z[16] = {};
+            TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg_apply), z, sizeof(z)));
+            if (apply_fast)
+                hipLaunchKernelGGL((ad8_tile_apply_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist, d_cnt);
+            hipLaunchKernelGGL((ad8_tile_apply_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist,
+                               d_cnt, list, nredo);
+            TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
+            TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_dbg_apply), sizeof(z)));
+            const double na = double(z[4] ? z[4] : 1), nf = double(z[12] ? z[12] : 1);
+            fprintf(stderr, "ad8_tile_apply: %llu tiles, cycles per tile: stage %.0f, topology %.0f, entry walks %.0f, write-back %.0f\n", z[4], double(z[0]) / na, double(z[1]) / na,
+                    double(z[2]) / na, double(z[3]) / na);
+            if (apply_fast)
+                fprintf(stderr, "ad8_tile_apply_fast: %llu tiles, cycles per tile: load %.0f, targets %.0f, entry walks %.0f, write-back %.0f\n", z[12], double(z[8]) / nf,
+                        double(z[9]) / nf, double(z[10]) / nf, double(z[11]) / nf);
+        } else {
+            if (apply_fast)
+                hipLaunchKernelGGL((ad8_tile_apply_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist, d_cnt);
+            hipLaunchKernelGGL((ad8_tile_apply_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist,
+                               d_cnt, list, nredo);
+        }
+        if (stats) stats->launches[TDX_K_STENCIL] += apply_fast ? 2 : 1;
     }
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_mail, d_cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // the big cells and, word 7, the redone tiles
     TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
