@@ -69,6 +69,7 @@ using namespace tdxk;
 // Per flat cell: seeds (lvl = 1 "low", 2 quirk source; rq = 1 "higher neighbour"), the eligibility
 // masks of both relaxations (bit k-1 = neighbour k may hand its level to this cell) and the
 // activation flag of the cell's tile.  Flat cells are interior cells, so all 8 neighbours exist.
+// rmask may be null (here and in classify_stream_kernel): no incrise tile decodes its masks (every one is plain), the byte is not stored.
 constexpr int CLASSIFY_ITEMS = 4;
 template <class Traits, class LV>
 __global__ __launch_bounds__(256) void classify_kernel(Traits tr, const float* __restrict__ Z, int nx, int tiles_x,
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void classify_kernel(Traits tr, const float* _
             else if (quirk) lvl[c] = 2;
             if (higher) rq[c] = 1;
             fmask[c] = uint8_t(low ? 0u : fm);     // a level-1 cell can never improve
-            rmask[c] = uint8_t(higher ? 0u : rm);
+            if (rmask != nullptr) rmask[c] = uint8_t(higher ? 0u : rm);
             const unsigned y = unsigned(c / size_t(nx)), x = unsigned(c - size_t(y) * size_t(nx));
             const unsigned tile = (y / tilek::TS) * unsigned(tiles_x) + x / tilek::TS;
             tile_flags[tile] = tilek::FLAG_FULL;
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(256) void classify_stream_kernel(const float* __res
             lvl[idx] = l;
             rq[idx] = q;
             fmask[idx] = uint8_t(fm);
-            rmask[idx] = uint8_t(rm);
+            if (rmask != nullptr) rmask[idx] = uint8_t(rm);
             fall_all &= fm;
             rise_all &= rm;
         }
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void classify_stream_kernel(const float* __res
     }
 }
 
-// level field in the marker convention above: values <= 0 read as +inf; only cells with a mask move.  S = storage type of the field in
+// level field in the marker convention above: values <= 0 read as +inf; only cells with a mask move (plain tiles: only cells in the queue).  S = storage type of the field in
 // HBM (the values in registers are 32-bit either way): int16 for the two level fields, where a candidate level saturates at LVL_SAT -
 // the fixed point of the saturating operator is min(level, LVL_SAT) per cell, i.e. the exact field whenever every level fits, and
 // flats_bfs turns a saturated maximum into the error the reference's overflowing int16 counters stand for; int32 for the plain marks.
@@ -243,30 +244,31 @@ __global__ __launch_bounds__(256) void classify_stream_kernel(const float* __res
 // marks the tiles that own such a cell in TM.)  Unmarked tiles run LevelPlainT: the nine-way minimum as min3 + six DPP-fused v_min_i32, the lock
 // as one v_med3_i32 - 12 VALU instructions per 64-cell row instead of 38 - and the int16 saturation moves to the store (the fixed point of
 // "saturate when stored" is the same min(level, LVL_SAT): a stored LVL_SAT never improves a neighbour below LVL_SAT).
+//
+// A plain tile reads NO mask byte (no CellRaw: tile_relax.hpp issues no second load per cell).  Whether a cell may move is in its marker: it is in the queue
+// (raw >= 0).  The in-queue cells whose mask byte is 0 are left alone by the operator itself: a seed (level 1 or 2) is never undercut, since every neighbour
+// value and the cell's own are >= 1 and min(m + 1, own) = own; and on a plain tile a non-seed cell with mask 0 has rm == fm == 0, no neighbour in the queue, so
+// all eight read +inf for good and the cell keeps its +inf (an unfilled one-cell pit: has_pits).
 template <class S>
 struct LevelPlainT {
     using T = int;
     static constexpr int kUniform = 8;
     S* G;
-    const uint8_t* M;
     static __device__ __forceinline__ int inf() { return 0x3fffffff; }
     using Raw = S;
-    using CellRaw = uint8_t;
     __device__ __forceinline__ S load_raw(size_t idx) const { return G[idx]; }
     static __device__ __forceinline__ int decode(S g) { return g > 0 ? int(g) : inf(); }
-    static __device__ __forceinline__ bool raw_can_move(S g) { return g >= 0; }   // a negative marker = outside the queue: its mask byte may be stale (flats_bfs)
+    static __device__ __forceinline__ bool raw_can_move(S g) { return g >= 0; }   // a negative marker = outside the queue
     __device__ __forceinline__ void store(size_t idx, int v) const { G[idx] = S(sizeof(S) == 2 && v > LVL_SAT ? LVL_SAT : v); }
-    __device__ __forceinline__ uint8_t cell_raw(size_t idx) const { return M[idx]; }
-    static __device__ __forceinline__ void cell_decode(uint8_t m, int& lock, unsigned& mask) { lock = m ? 0 : inf(); mask = m; }
-    // The constant of a cell is 0 where it may move and THE VALUE IT WAS LOADED WITH where it may not (mask 0: seeds, cells outside the queue,
+    static __device__ __forceinline__ void cell_decode(int& lock, unsigned& mask) { lock = 0; mask = 0xFFu; }   // (a cell that raw_can_move admits)
+    // The constant of a cell is 0 where it may move and THE VALUE IT WAS LOADED WITH where it may not (cells outside the queue,
     // cells of other strips): median(m + 1, 0, own) = min(m + 1, own) (both positive), median(m + 1, own, own) = own.
     static __device__ __forceinline__ int cell_floor(int lock, int v) { return lock == 0 ? 0 : v; }
     static __device__ __forceinline__ int apply(int lock, int own, int m) { return tilek::med3_raw(m + 1, lock, own); }
     static __device__ __forceinline__ bool settled(int, int v) { return v <= 1; }
-    // activation filter (tile_relax.hpp): a halo cell that may move (mask != 0) improves from a neighbour value below its own level - 1
+    // activation filter (tile_relax.hpp): a halo cell in the queue improves from a neighbour value below its own level - 1; the value alone says so:
+    // -1 = outside the queue, a seed's level (1, 2) is below every new value
     static __device__ __forceinline__ int act_never() { return int(0x80000000u); }
-    static __device__ __forceinline__ int act_threshold(uint8_t m, int v) { return m ? v - 1 : act_never(); }
-    // ... and the value alone says as much: -1 = outside the queue, a seed's level (1, 2) is below every new value
     static __device__ __forceinline__ int act_threshold_raw(S g) { return g >= 0 ? decode(g) - 1 : act_never(); }
 };
 
@@ -393,7 +395,7 @@ struct LevelOpT {
     const uint8_t* TM = nullptr;   // INC 1 only: per tile, 1 = a cell of the tile needs its mask (null: no tile does)
     static constexpr bool kHasPlain = INC == 1;
     using Plain = LevelPlainT<S>;
-    __device__ __forceinline__ Plain plain() const { return Plain{G, M}; }
+    __device__ __forceinline__ Plain plain() const { return Plain{G}; }
     __device__ __forceinline__ bool tile_masked(int tile) const { return TM != nullptr && TM[tile] != 0; }
     static __device__ __forceinline__ int inf() { return 0x3fffffff; }
     using Raw = S;
@@ -969,16 +971,21 @@ static int flats_bfs(tdx_context* ctx, Traits tr, const float* Z, const Strip& s
     const int ntiles = geom.tiles_x * geom.tiles_y;
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ctx->d_mail);
     uint8_t* fmask = static_cast<uint8_t*>(ctx->scratch(TDX_S_E, n));
-    uint8_t* rmask = static_cast<uint8_t*>(ctx->scratch(TDX_S_F, n));
     uint32_t* flags0 = static_cast<uint32_t*>(ctx->scratch(TDX_S_G, size_t(ntiles) * 4 * 2 + size_t(ntiles)));
     uint32_t* list = static_cast<uint32_t*>(ctx->scratch(TDX_S_H, size_t(ntiles) * 4 * tilek::SCHED_LIST_WORDS));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_K, size_t(tilek::COUNT_RING) * 16));
-    if (!fmask || !rmask || !flags0 || !list || !counts) return TDX_ERR_NOMEM;
+    if (!fmask || !flags0 || !list || !counts) return TDX_ERR_NOMEM;
     uint32_t* flags = flags0 + ntiles;
     uint8_t* tmask = reinterpret_cast<uint8_t*>(flags0 + 2 * size_t(ntiles));   // incfall: tiles that are not plain
     const char* e_masked = getenv("TDX_FLATS_MASKED");   // A/B and test hook (read per call): 1 = every tile on the masked form, 2 = the first half of the tiles
     const bool no_plain = e_masked && e_masked[0] == '1';
     const bool half_plain = e_masked && e_masked[0] == '2';
+    // The incrise masks as a raster only for the forms that decode them: every incrise tile is plain and reads no mask (LevelPlainT) unless the hook puts all
+    // tiles on the masked form; the LDS-resident tile kernel and the worklist schedule (test hooks) decode masks without the marker.  Otherwise the byte is not
+    // stored and its scratch slot not asked for (read per call: the hooks are).
+    const bool clear_masks = getenv("TDX_RELAX_LDS") != nullptr || getenv("TDX_RELAX_ASYNC") != nullptr || getenv("TDX_FLATS_CLEAR_MASKS") != nullptr;
+    uint8_t* rmask = (no_plain || clear_masks) ? static_cast<uint8_t*>(ctx->scratch(TDX_S_F, n)) : nullptr;
+    if ((no_plain || clear_masks) && !rmask) return TDX_ERR_NOMEM;
     TdxSpan sp(ctx, TDX_K_BFS);
     static const bool no_pair = getenv("TDX_FLATS_SEQUENTIAL") != nullptr;
     static const bool strips_sequential = getenv("TDX_FLATS_STRIPS_SEQUENTIAL") != nullptr;   // (A/B hook: one field after the other in a multi-strip run)
@@ -1013,8 +1020,7 @@ static int flats_bfs(tdx_context* ctx, Traits tr, const float* Z, const Strip& s
     else {
         // The list classification writes the masks of the QUEUE's cells only.  The register tile kernel reads a mask byte only where the level marker says
         // "in the queue" (LevelOpT::raw_can_move), so what other cells hold - a mask of an earlier iteration, or nothing yet - is never looked at; only the
-        // LDS-resident tile kernel and the worklist schedule (test hooks), which decode masks without the marker, need the two rasters cleared (read per call: the hooks are).
-        const bool clear_masks = getenv("TDX_RELAX_LDS") != nullptr || getenv("TDX_RELAX_ASYNC") != nullptr || getenv("TDX_FLATS_CLEAR_MASKS") != nullptr;
+        // LDS-resident tile kernel and the worklist schedule (test hooks), which decode masks without the marker, need the two rasters cleared.
         if (clear_masks) {
             TDX_HIP_CHECK(ctx, hipMemsetAsync(fmask, 0, n, s));
             TDX_HIP_CHECK(ctx, hipMemsetAsync(rmask, 0, n, s));

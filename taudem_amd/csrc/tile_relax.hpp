@@ -82,8 +82,7 @@ static inline TileGeom make_geom(int nx, int ny, int y_own0, int y_own1) {
     static const int cm = getenv("TDX_SOLO_CHAIN") ? atoi(getenv("TDX_SOLO_CHAIN")) : 256;
     g.chain_max = cm;
     g.cnt_host = nullptr; g.cnt_dev = nullptr; g.cnt_tag = 0ull;
-    static const int af = getenv("TDX_ACT_FILTER_OFF") ? 0 : 1;
-    g.act_filter = af;
+    g.act_filter = getenv("TDX_ACT_FILTER_OFF") ? 0 : 1;   // (test hook: read per call)
     g.remap = nullptr; g.blk_k = nullptr;
     return g;
 }
@@ -126,6 +125,8 @@ __device__ __forceinline__ T uniform_min(bool fourway, T e, T ne, T n, T nw, T w
 //   void store(size_t idx, T v) const;   changed cell
 //   CellRaw cell_raw(size_t idx) const; static void cell_decode(CellRaw, T& cst, unsigned& mask);
 //                                        per-cell constant + neighbour mask (0 = never updated)
+//                                        (register tiles: an operator WITHOUT CellRaw has no per-cell raster - no load is issued and a cell that
+//                                        raw_can_move() admits gets its constant and mask from static void cell_decode(T& cst, unsigned& mask))
 //   static T cell_floor(T cst, T v);     register tiles only: the constant apply() gets, given the value v the cell is loaded with
 //                                        (lets an operator fold "a settled cell never moves" into the constant)
 //   static T apply(T cst, T own, T m);   new value (must be <= own)
@@ -606,6 +607,13 @@ template <class Op, class = void>
 struct has_raw_can_move : std::false_type {};
 template <class Op>
 struct has_raw_can_move<Op, std::void_t<decltype(Op::raw_can_move(typename Op::Raw()))>> : std::true_type {};
+// Op::CellRaw (optional): the type of the per-cell constant / mask raster.  An operator without it says everything through its values (raw_can_move): the
+// register tile issues no second load per cell (LevelPlainT, flats.hpp: 18 loads per lane instead of 34).
+struct NoCellRaw {};
+template <class Op, class = void>
+struct cell_raw_of { using type = NoCellRaw; static constexpr bool value = false; };
+template <class Op>
+struct cell_raw_of<Op, std::void_t<typename Op::CellRaw>> { using type = typename Op::CellRaw; static constexpr bool value = true; };
 
 // Same contract as relax_tile (sV must hold REG_LDS_WORDS words).
 template <class Op>
@@ -628,7 +636,8 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
     const int gxc = col_ok ? gx : g.nx - 1;
     const long long row_pitch = (long long)g.nx;
     typename Op::Raw raw[RPW], raw_edge, raw_side;
-    typename Op::CellRaw craw[RPW], craw_edge = {};
+    constexpr bool kCellRaw = cell_raw_of<Op>::value;
+    typename cell_raw_of<Op>::type craw[RPW], craw_edge = {};
     {
         int gy = y0 + ry0;
 #pragma unroll
@@ -636,7 +645,7 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
             const int gyc = gy >= g.ny ? g.ny - 1 : gy;
             const size_t idx = size_t((long long)gyc * row_pitch + gxc);
             raw[r] = op.load_raw(idx);
-            craw[r] = op.cell_raw(idx);
+            if constexpr (kCellRaw) craw[r] = op.cell_raw(idx);
             gy++;
         }
     }
@@ -664,7 +673,10 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
         unsigned m = 0;
         bool movable = col_ok && gy >= g.y_own0 && gy < g.y_own1;
         if constexpr (has_raw_can_move<Op>::value) movable = movable && Op::raw_can_move(raw[r]);
-        if (movable) Op::cell_decode(craw[r], c, m);
+        if (movable) {
+            if constexpr (kCellRaw) Op::cell_decode(craw[r], c, m);
+            else Op::cell_decode(c, m);
+        }
         if (m && !Op::settled(c, v[r])) live |= 1u << r;
         cst[r] = Op::cell_floor(c, v[r]);
         mk[r >> 2] |= (m & 0xFFu) << (8 * (r & 3));
@@ -767,37 +779,63 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
     }
     const unsigned long long tc2 = dbg ? __builtin_readcyclecounter() : 0ull;
     if (any_change) {   // uniform
-        int rim = 0;
+        // Which neighbours are told (res bits 0-7: N S W E NW NE SW SE): with an activation filter (has_act_threshold) only if a cell of the neighbour that the
+        // moved rim cell touches can still be improved by the new value; g.act_filter == 0: whenever a rim cell moved.
+        if constexpr (has_act_threshold_raw<Op>::value) {
+            // The level fields.  Nothing but the store stands under a row's "moved" bit; the flags are formed outside the row loop, wave-uniform: only row 0 of
+            // the first band and row TS - 1 of the last touch the tiles above / below, only lanes 0 and TS - 1 the tiles beside and at the corners.  (Per row -
+            // the form below - every row carried a nest of exec-mask branches in which two lanes read their thresholds from LDS and compared: longer than both
+            // sweep bodies together, and the level kernels spilled six registers for it.)
+            int rim = 0;
+            const int wvu = __builtin_amdgcn_readfirstlane(wv);
+            const bool all = g.act_filter == 0;
+            if (wvu == 0 && __ballot((moved & 1u) != 0u && (all || v[0] < sEdgeT[lx])) != 0ull) rim |= 1;
+            if (wvu == NWAVE - 1 && __ballot(((moved >> (RPW - 1)) & 1u) != 0u && (all || v[RPW - 1] < sEdgeT[TS + lx])) != 0ull) rim |= 2;
+            // lanes 0 and TS - 1 park the new value of every moved row in an LDS column (+inf for a row that did not move: below no threshold); then one thread
+            // per side and row compares it with the largest threshold of the three cells beside it, rows 0 and TS - 1 also with the corner cell's.
+            T* sCol = sRow;   // [left, right][TS]: the band rows are not read again after the last sweep's barrier
+            if (lx == 0 || lx == TS - 1) {
+                T* col = sCol + (lx ? TS : 0) + ry0;
 #pragma unroll
-        for (int r = 0; r < RPW; r++) {
-            const int ly = ry0 + r;
-            if ((moved >> r) & 1u) {
-                op.store(size_t(y0 + ly) * size_t(g.nx) + size_t(gx), v[r]);   // changed cells are in-grid and owned
-                const bool top = (ly == 0), bot = (ly == TS - 1), lef = (lx == 0), rig = (lx == TS - 1);
-                if constexpr (has_act_threshold<Op>::value) {
-                    // a neighbour is told only if a cell of it that this cell touches can still be improved by the new value
-                    const bool all = g.act_filter == 0;
-                    if ((top || bot) && (all || v[r] < sEdgeT[(bot ? TS : 0) + lx])) rim |= top ? 1 : 2;
-                    if constexpr (has_act_threshold_raw<Op>::value) {
-                        if (lef || rig) {
-                            const T* st = sSideT + (rig ? LH : 0);   // window rows ly .. ly + 2 = the cells beside rows ly - 1 .. ly + 1
-                            if (all || v[r] < max_t(st[ly], max_t(st[ly + 1], st[ly + 2]))) rim |= lef ? 4 : 8;
-                            if (top && (all || v[r] < st[0])) rim |= lef ? 16 : 32;
-                            if (bot && (all || v[r] < st[LH - 1])) rim |= lef ? 64 : 128;
-                        }
-                    } else {
+                for (int r = 0; r < RPW; r++) col[r] = ((moved >> r) & 1u) ? v[r] : Op::inf();
+            }
+            __syncthreads();   // (no global access is in flight here: the stores follow)
+            size_t idx = size_t(y0 + ry0) * size_t(g.nx) + size_t(gx);   // changed cells are in-grid and owned
+#pragma unroll
+            for (int r = 0; r < RPW; r++) {
+                if ((moved >> r) & 1u) op.store(idx, v[r]);
+                idx += size_t(g.nx);
+            }
+            if (wvu < 2) {   // wave 0: the left column, wave 1: the right one; lane = row
+                const T val = sCol[wvu * TS + lx];
+                const T* st = sSideT + wvu * LH;   // window rows lx .. lx + 2 = the cells beside rows lx - 1 .. lx + 1
+                const bool mv = val < Op::inf();
+                const bool side = all ? mv : val < max_t(st[lx], max_t(st[lx + 1], st[lx + 2]));
+                const bool c_top = lx == 0 && (all ? mv : val < st[0]);
+                const bool c_bot = lx == TS - 1 && (all ? mv : val < st[LH - 1]);
+                if (__ballot(side) != 0ull) rim |= 4 << wvu;
+                if (__ballot(c_top) != 0ull) rim |= 16 << wvu;
+                if (__ballot(c_bot) != 0ull) rim |= 64 << wvu;
+            }
+            if (rim && lx == 0) atomicOr(&L.rim, rim);
+        } else {
+            // Every other operator, per row.  (The form above, with ballots of the moved masks of lanes 0 and TS - 1 for the sides, costs PitOp<8> - at its
+            // register limit of 96 - a spilled register in the load phase, and with an address per row sixteen: docs/experiments_r07.md section 3.)
+            int rim = 0;
+#pragma unroll
+            for (int r = 0; r < RPW; r++) {
+                const int ly = ry0 + r;
+                if ((moved >> r) & 1u) {
+                    op.store(size_t(y0 + ly) * size_t(g.nx) + size_t(gx), v[r]);   // changed cells are in-grid and owned
+                    const bool top = (ly == 0), bot = (ly == TS - 1), lef = (lx == 0), rig = (lx == TS - 1);
+                    if constexpr (has_act_threshold<Op>::value) {
                         // (an operator whose threshold needs the cell's constant: the tiles beside and at the corners are told whenever their rim cell moves -
                         // their thresholds would be one more strided column load per activation, which costs what the withheld activations save: measured)
-                        if (lef) rim |= 4;
-                        if (rig) rim |= 8;
-                        if (top && lef) rim |= 16;
-                        if (top && rig) rim |= 32;
-                        if (bot && lef) rim |= 64;
-                        if (bot && rig) rim |= 128;
+                        if ((top || bot) && (g.act_filter == 0 || v[r] < sEdgeT[(bot ? TS : 0) + lx])) rim |= top ? 1 : 2;
+                    } else {
+                        if (top) rim |= 1;
+                        if (bot) rim |= 2;
                     }
-                } else {
-                    if (top) rim |= 1;
-                    if (bot) rim |= 2;
                     if (lef) rim |= 4;
                     if (rig) rim |= 8;
                     if (top && lef) rim |= 16;
@@ -806,8 +844,8 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
                     if (bot && rig) rim |= 128;
                 }
             }
+            if (rim) atomicOr(&L.rim, rim);
         }
-        if (rim) atomicOr(&L.rim, rim);
     }
     __syncthreads();
     if (dbg && tid == 0) {   // phase cycles: load, sweeps, write-back
