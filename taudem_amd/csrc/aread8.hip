@@ -23,6 +23,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 using namespace tdxk;
@@ -292,10 +293,14 @@ __global__ __launch_bounds__(256) void ad8_halo_kernel(const int16_t* __restrict
 //
 // "not evaluated" (the reference leaves -1): cells fed by the p == 0 north-west quirk, cells on / below
 // a cycle, and everything downstream of them - carried as a flag next to the contamination flag.
+//
+// Each rule that more than one tile kernel needs stands ONCE: tile_origin / tile_window_whole (where a tile lies; the uniform half of "clean", one predicate
+// for A' and C'), redo_append, ring_set_aside (A, C), perimeter_node_write (A, A'), apply_entering_crossing and apply_write_back (C, C'), Ad8Clock (the
+// TDX_AD8_DEBUG phase clocks of all four).  The host reads its switches into one Ad8Options per call and writes each tile launch once (ad8_clocked_launches).
 // =====================================================================================================
 constexpr int TS = 64;
 constexpr int TH = TS + 2;
-static_assert(TS == 64, "S_TGT() shifts by 6");
+static_assert(TS == 64, "lane = column: the tile kernels split a thread index into a 64-wide column and a wave");
 // node_indeg == 0xFFFFFFFF: perimeter / halo cell that is not (yet) a node
 constexpr uint32_t NODE_DEAD = 0xFFFFFFFEu;      // node whose cell never completes (cycle / poisoned): never fires
 constexpr uint32_t NEXT_NONE = 0xFFFFFFFFu;
@@ -416,16 +421,70 @@ __device__ __forceinline__ bool ring_cell(int j, int rv, int& hx, int& hy) {
     return false;
 }
 
-__device__ unsigned long long g_ad8_dbg[8];   // TDX_AD8_DEBUG=1: phase cycles of ad8_tile_local_kernel summed over the tiles (thread 0)
+// ---- what the four tile kernels share ----
+// A tile's place in the strip: array column / row of its first cell and the number of its rows that the strip owns.
+struct Ad8Tile { int x0, ya0, rv; };
+__device__ __forceinline__ Ad8Tile tile_origin(const Ad8Geom& g, int tile) {
+    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
+    return Ad8Tile{tx * TS, g.y0 + ty * TS, rows_valid(g, ty)};
+}
+// All 64 rows valid and the 66 x 66 window inside the array: the first half of "clean" (uniform for the workgroup).  ad8_tile_fast_kernel marks words only behind
+// this test and ad8_tile_apply_fast_kernel reads without bounds only behind it: one predicate for both.
+__device__ __forceinline__ bool tile_window_whole(const Ad8Geom& g, const Ad8Tile& t) {
+    return t.rv == TS && t.x0 >= 1 && t.x0 + TS < g.nx && t.ya0 >= 1 && t.ya0 + TS < g.ny_arr;
+}
+// ad8_tile_fast_kernel leaves the tile to the Kahn sweep (called by the whole workgroup)
+__device__ __forceinline__ void redo_append(uint32_t* __restrict__ redo, unsigned long long* __restrict__ nredo, int tile) {
+    if (threadIdx.x == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+}
+// The ring cells' codes of a staged tile, set aside in ring_cell() order before the table of in-tile targets takes the tile's place.
+__device__ __forceinline__ void ring_set_aside(const uint16_t* sO, uint16_t* sRing, int rv) {
+    for (int j = int(threadIdx.x); j < 4 * TH; j += 256) {
+        int hx, hy;
+        sRing[j] = ring_cell(j, rv, hx, hy) ? sO[(hy + 1) * TH + hx + 1] : uint16_t(0);
+    }
+}
+// Phases A and A': the node of the perimeter cell (lx, ly) whose flow leaves the tile towards array row tgy.  `dead`: the cell never completes (never in a clean tile,
+// whose flags are zero as well).  A crossing into a halo row is recorded here, because the tile that would record next(node) lives on another rank.
+__device__ __forceinline__ void perimeter_node_write(const Ad8Geom& g, int tile, int lx, int ly, int rv, unsigned cnt, unsigned con, unsigned poi, bool dead, int tgy,
+                                                     const unsigned* sIn, unsigned long long* __restrict__ node_acc, uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next) {
+    const int pp = perim_pos(lx, ly, rv);
+    const uint32_t nid = uint32_t(tile) * 256u + uint32_t(pp);
+    node_acc[nid] = nw_pack(cnt, 0u, con, poi);
+    node_indeg[nid] = dead ? NODE_DEAD : sIn[pp];
+    if (tgy < g.y0) node_next[nid] = NEXT_REMOTE_UP;
+    else if (tgy >= g.y1) node_next[nid] = NEXT_REMOTE_DOWN;
+}
+// TDX_AD8_DEBUG=1: the phase clocks of a tile kernel.  mark(i) reads the clock at the end of phase i - 1; flush() - by the whole workgroup, at the end of the kernel -
+// reads the last one behind a barrier and has thread 0 add the tile's N - 1 phases to the kernel's row of g_ad8_clk: [0, N - 1) phase cycles, [7] tiles in the
+// low and `extra` (the doubling rounds of ad8_tile_fast_kernel) in the high 32 bits.  Without DBG it holds nothing and emits nothing.
+enum { AD8_CLK_LOCAL = 0, AD8_CLK_FAST, AD8_CLK_APPLY, AD8_CLK_APPLY_FAST, AD8_CLK_KERNELS };
+__device__ unsigned long long g_ad8_clk[AD8_CLK_KERNELS][8];
+template <bool DBG, int N>
+struct Ad8Clock {
+    static_assert(N >= 2 && N <= 8, "N - 1 phases in front of the row's counter word");
+    unsigned long long t[N];
+    __device__ __forceinline__ void mark(int i) { t[i] = clock64(); }
+    __device__ __forceinline__ void flush(int slot, unsigned extra = 0u) {
+        __syncthreads();
+        mark(N - 1);
+        if (threadIdx.x != 0) return;
+#pragma unroll
+        for (int i = 0; i + 1 < N; i++) atomicAdd(&g_ad8_clk[slot][i], t[i + 1] - t[i]);
+        atomicAdd(&g_ad8_clk[slot][7], ((unsigned long long)extra << 32) | 1ull);   // (one atomic for both: the clock array is what a clocked kernel waits for)
+    }
+};
+template <int N>
+struct Ad8Clock<false, N> { __device__ void mark(int) {} __device__ void flush(int, unsigned = 0u) {} };
+
 template <bool DBG, bool FLAT>
 __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
                                                              uint32_t* __restrict__ cellw, unsigned long long* __restrict__ node_acc,
                                                              uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next,
                                                              const uint32_t* __restrict__ list, const unsigned long long* __restrict__ nlist) {
     if (list && blockIdx.x >= *nlist) return;   // the redo launch behind ad8_tile_fast_kernel: one workgroup per tile of the raster, the list's length known to the device only
-    unsigned long long tcs[6];
-#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
-    AD8_MARK(0);
+    Ad8Clock<DBG, 6> clk;
+    clk.mark(0);
     // 26.7 KB of LDS per tile (six workgroups per CU use 160 of its 163.8 KB).  The staged tile holds ONE-HOT direction codes, 66-pitch with the ring; once every
     // lane has derived its topology from it, the table of in-tile targets takes its place at 64-pitch - a hop addresses the table and sAcc with the same cell
     // index, two shifts - so the ring cells' codes, which the entry search needs afterwards, are set aside first: sRing, in ring_cell() order.
@@ -435,17 +494,14 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
     __shared__ uint16_t sRing[4 * TH];
     int16_t* const sT = reinterpret_cast<int16_t*>(sO);
     const int tile = list ? int(list[blockIdx.x]) : int(blockIdx.x);
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
-    const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
+    const Ad8Tile to = tile_origin(g, tile);
+    const int x0 = to.x0, ya0 = to.ya0, rv = to.rv;
     const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16;
     stage_p_onehot(P, g.nx, g.ny_arr, x0, ya0, nodata, sO);
     sIn[tid] = 0u;
     __syncthreads();
-    AD8_MARK(1);
-    for (int j = tid; j < 4 * TH; j += 256) {
-        int hx, hy;
-        sRing[j] = ring_cell(j, rv, hx, hy) ? sO[(hy + 1) * TH + hx + 1] : uint16_t(0);
-    }
+    clk.mark(1);
+    ring_set_aside(sO, sRing, rv);
     unsigned src = 0;       // rows of this lane that start a walk
     unsigned exit_up = 0, exit_down = 0;   // rows whose crossing leaves towards the row above / below the cell
     int16_t tgt[16];
@@ -506,12 +562,11 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         }
     }
     __syncthreads();   // every lane is done reading directions: the target table takes the tile's place
-#define S_TGT(c) sT[c]
 #pragma unroll
     for (int r = 0; r < 16; r++)
         if (ry0 + r < rv) sT[(ry0 + r) * TS + lx] = tgt[r];
     __syncthreads();
-    AD8_MARK(2);
+    clk.mark(2);
     // Kahn sweep of the in-tile flows: one returning 32-bit LDS atomic per hop; the target of the NEXT hop is read alongside the
     // atomic (both only need the current target), so a hop is one LDS round trip, not two
     if (FLAT) {
@@ -529,7 +584,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
                 t = (ry0 + r) * TS + lx;
                 add = 0u;
             }
-            const int tn = S_TGT(t);
+            const int tn = sT[t];
             const unsigned nw = __hip_atomic_fetch_add(&sAcc[t], add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + add;
             // what this cell hands on: its count, one arrival, "contaminated" / "not evaluated" as 0 / 1 (min(field, 1 << shift): the fields count contributors)
             add = (nw & 0x1FFFu) | (1u << 13) | min(nw & (15u << 17), 1u << 17) | min(nw & (15u << 21), 1u << 21);
@@ -541,9 +596,9 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         src &= src - 1u;
         const int c = (ry0 + r) * TS + lx;
         unsigned w = sAcc[c];
-        int t = S_TGT(c);
+        int t = sT[c];
         while (t >= 0) {
-            const int tn = S_TGT(t);
+            const int tn = sT[t];
             const unsigned add = lw_pack(lw_cnt(w), 1u, lw_con(w) ? 1u : 0u, lw_poi(w) ? 1u : 0u, 0u);
             const unsigned nw = __hip_atomic_fetch_add(&sAcc[t], add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + add;
             if (lw_arr(nw) != lw_indeg(nw)) break;   // someone else will be the last contributor
@@ -552,7 +607,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
     }
     }
     __syncthreads();
-    AD8_MARK(3);
+    clk.mark(3);
     // crossings that enter the tile: follow the in-tile path of the entry cell to where it leaves
     for (int j = tid; j < 4 * TH; j += 256) {
         int hx, hy;
@@ -564,9 +619,9 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         if (!in_tile(vx, vy, rv)) continue;
         int cur = vy * TS + vx, hops = 0;
         if (lw_indeg(sAcc[cur]) == 15u) continue;        // the entry cell does not participate
-        while (S_TGT(cur) >= 0 && hops < TS * TS) { cur = S_TGT(cur); hops++; }
+        while (sT[cur] >= 0 && hops < TS * TS) { cur = sT[cur]; hops++; }
         uint32_t nxt = NEXT_NONE;
-        if (S_TGT(cur) == -2) {
+        if (sT[cur] == -2) {
             const int pp = perim_pos(cur % TS, cur / TS, rv);
             atomicAdd(&sIn[pp], 1u);
             nxt = uint32_t(tile) * 256u + uint32_t(pp);
@@ -574,7 +629,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         node_next[node_id(g, x0 + hx, ya0 + hy)] = nxt;
     }
     __syncthreads();
-    AD8_MARK(4);
+    clk.mark(4);
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int ly = ry0 + r, c = ly * TS + lx;
@@ -585,23 +640,11 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_local_kernel(const int16_t* _
         const bool complete = part && lw_arr(w) == lw_indeg(w);
         cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = part ? cw_pack(lw_cnt(w), lw_con(w) != 0u, lw_poi(w) != 0u || !complete) : 0u;
         if (part && tgt[r] == -2) {
-            const int pp = perim_pos(lx, ly, rv);
-            const uint32_t nid = uint32_t(tile) * 256u + uint32_t(pp);
-            node_acc[nid] = nw_pack(lw_cnt(w), 0u, lw_con(w) ? 1u : 0u, lw_poi(w) ? 1u : 0u);
-            node_indeg[nid] = complete ? sIn[pp] : NODE_DEAD;
             const int tgy = gy + (((exit_up >> r) & 1u) ? -1 : (((exit_down >> r) & 1u) ? 1 : 0));
-            if (tgy < g.y0) node_next[nid] = NEXT_REMOTE_UP;        // the tile that would record next(node) lives on another rank
-            else if (tgy >= g.y1) node_next[nid] = NEXT_REMOTE_DOWN;
+            perimeter_node_write(g, tile, lx, ly, rv, lw_cnt(w), lw_con(w) ? 1u : 0u, lw_poi(w) ? 1u : 0u, !complete, tgy, sIn, node_acc, node_indeg, node_next);
         }
     }
-#undef S_TGT
-    if (DBG) {
-        __syncthreads();
-        AD8_MARK(5);
-        if (tid == 0)
-            for (int i = 0; i < 5; i++) atomicAdd(&g_ad8_dbg[i], tcs[i + 1] - tcs[i]);
-    }
-#undef AD8_MARK
+    clk.flush(AD8_CLK_LOCAL);
 }
 
 // a code of a clean window: not nodata and 1 .. 8
@@ -615,8 +658,6 @@ __device__ __forceinline__ bool ring_slot(int tid, int k, int& hx, int& hy) {
     return has;
 }
 
-// TDX_AD8_DEBUG=1: ad8_tile_fast_kernel, summed over the clean tiles (thread 0): [0, 5) phase cycles, [5] doubling rounds, [6] tiles
-__device__ unsigned long long g_ad8_dbg_fast[8];
 constexpr int AD8_MAX_ROUNDS = 12;   // an acyclic in-tile path has at most 4095 hops < 2^12
 // Phase A' (see the block comment above).  25.9 KB of LDS: six tiles per CU.  Nothing is staged: a lane reads the codes of its own 16 cells (a wave row of the tile is one aligned
 // 128-byte line of p) and of its ring cells - ring_cell() order, two per lane at most - straight into registers, all loads back to back; the "clean" vote, the
@@ -633,22 +674,21 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
                                                             uint32_t* __restrict__ cellw, unsigned long long* __restrict__ node_acc,
                                                             uint32_t* __restrict__ node_indeg, uint32_t* __restrict__ node_next,
                                                             uint32_t* __restrict__ redo, unsigned long long* __restrict__ nredo, unsigned mark) {
-    unsigned long long tcs[6];
-#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
-    AD8_MARK(0);
+    Ad8Clock<DBG, 5> clk;
+    clk.mark(0);
     __shared__ int16_t sT[TS * TS];
     __shared__ unsigned sAcc[TS * TS];
     __shared__ unsigned sIn[256];         // crossings that end at each perimeter cell
     __shared__ unsigned sVote[3][4];      // per wave: "read a code that is not 1 .. 8", "a pointer is live" of the even / odd rounds
     __shared__ uint8_t sRc[256];          // per lane: the codes of its two ring cells, four bits each
     const int tile = blockIdx.x;
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
-    const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
+    const Ad8Tile to = tile_origin(g, tile);
+    const int x0 = to.x0, ya0 = to.ya0;
     // (the wave's number as a scalar: the rows of a lane's 16 cells are then scalars too - row addresses and cell indices take no vector registers)
     const int tid = threadIdx.x, lx = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ry0 = wave * 16;
-    // all rows valid and the window inside the array: uniform for the workgroup, and nothing is read otherwise
-    if (rv != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr) {
-        if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+    // nothing is read of a tile whose window is not whole
+    if (!tile_window_whole(g, to)) {
+        redo_append(redo, nredo, tile);
         return;
     }
     int16_t pc[16], pr[2];
@@ -668,10 +708,10 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
     if (lx == 0) sVote[0][wave] = wave_bad ? 1u : 0u;
     __syncthreads();
     if ((sVote[0][0] | sVote[0][1] | sVote[0][2] | sVote[0][3]) != 0u) {
-        if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+        redo_append(redo, nredo, tile);
         return;
     }
-    AD8_MARK(1);
+    clk.mark(1);
     // a lane's own 16 codes -> in-tile target, or ~(own cell): the crossing leaves the tile (its target takes part, like everything in the window)
     // The rounds have no register to spare at six tiles per CU, so the codes are not kept in any: a cell's code rides in its sAcc word above the count, where
     // the per-cell word has it (CW_CODE_SHIFT; an acyclic tile's counts stay below 2^13 in every round, and a cyclic tile writes nothing), and what the write-back
@@ -691,8 +731,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
     }
     sRc[tid] = uint8_t(unsigned(pr[0]) | (unsigned(pr[1]) << 4));   // the ring cells' codes wait in LDS as well
     __syncthreads();
-    AD8_MARK(2);
-    AD8_MARK(3);   // (the entry walks that stood here are gone: their clock reads 0)
+    clk.mark(2);
     // Pointer doubling.  Phase 1 reads nxt[n] and adds the lane's previous acc to acc[n] (non-returning atomics, all independent); phase 2 publishes the new pointers
     // and re-reads the own acc of the cells that go on.  (Both in one phase would mix pointers of two generations: the invariant needs exact powers of two.)
     unsigned acc[16];
@@ -726,11 +765,11 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
         const unsigned* v = sVote[1 + (rounds & 1)];
         if ((v[0] | v[1] | v[2] | v[3]) == 0u) break;
         if (rounds == AD8_MAX_ROUNDS) {   // a cycle: not clean (nothing has been written to global memory yet)
-            if (tid == 0) redo[atomicAdd(nredo, 1ull)] = uint32_t(tile);
+            redo_append(redo, nredo, tile);
             return;
         }
     }
-    AD8_MARK(4);
+    clk.mark(3);
     // crossings that enter the tile end at the root of their entry cell (every pointer is dead: the vote's barrier stands behind the last publication)
     int tid_again = tid;   // (opaque: the ring cells' coordinates and the column's neighbours are derived again here, not carried through the rounds)
     asm volatile("" : "+v"(tid_again));
@@ -756,26 +795,10 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_fast_kernel(const int16_t* __
         const unsigned w = sAcc[c], cnt = w & CW_FAST_CNT_MASK;   // count and code as the per-cell word holds them
         const int p = int(cw_code(w));
         cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = mark ? w : cw_pack(cnt, false, false);
-        if (!in_tile(lx + d1(p), ly + d2(p), TS)) {
-            const int pp = perim_pos(lx, ly, TS);
-            const uint32_t nid = uint32_t(tile) * 256u + uint32_t(pp);
-            node_acc[nid] = nw_pack(cnt, 0u, 0u, 0u);
-            node_indeg[nid] = sIn[pp];
-            const int tgy = gy + d2(p);
-            if (tgy < g.y0) node_next[nid] = NEXT_REMOTE_UP;        // the tile that would record next(node) lives on another rank
-            else if (tgy >= g.y1) node_next[nid] = NEXT_REMOTE_DOWN;
-        }
+        if (!in_tile(lx + d1(p), ly + d2(p), TS))
+            perimeter_node_write(g, tile, lx, ly, TS, cnt, 0u, 0u, false, gy + d2(p), sIn, node_acc, node_indeg, node_next);
     }
-    if (DBG) {
-        __syncthreads();
-        AD8_MARK(5);
-        if (tid == 0) {
-            for (int i = 0; i < 5; i++) atomicAdd(&g_ad8_dbg_fast[i], tcs[i + 1] - tcs[i]);
-            atomicAdd(&g_ad8_dbg_fast[5], (unsigned long long)rounds);
-            atomicAdd(&g_ad8_dbg_fast[6], 1ull);
-        }
-    }
-#undef AD8_MARK
+    clk.flush(AD8_CLK_FAST, unsigned(rounds));
 }
 
 // Walk the crossing forest from the completed node u (word w): the last arrival at a node continues.
@@ -837,13 +860,58 @@ __global__ __launch_bounds__(256) void ad8_forest_deliver_kernel(Ad8Geom g, cons
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(ndelivered, (unsigned long long)__popcll(m));
 }
 
-// LDS word of the apply pass: cnt[0:32) contam[32:44) poison[44:56)
-// (93 VGPRs: five tiles per CU.  Held to 80 - six tiles, as the LDS allows - it spills 15 registers in the first phase and is 13 % slower: profiles/r05l_*)
+// ---- what the two apply kernels share.  Their LDS: sCnt, a count per cell (32 bit); sFlag, 2 bits per cell (contaminated, not evaluated); sT, the in-tile target
+// of a cell or < 0 ----
+// The crossing of node nid enters the tile at cell `cur`: its count and flags go to every cell of the in-tile path below it.  A crossing that never delivers (dead
+// node, or arrivals short of the in-degree) adds no count and leaves everything below it unevaluated.
+__device__ __forceinline__ void apply_entering_crossing(uint32_t nid, int cur, const unsigned long long* __restrict__ node_acc, const uint32_t* __restrict__ node_indeg,
+                                                        unsigned* sCnt, unsigned* sFlag, const int16_t* sT) {
+    const uint32_t ind = node_indeg[nid];
+    const unsigned long long w = node_acc[nid];
+    unsigned addc = 0, addf = 2u;
+    if (ind < NODE_DEAD && nw_arr(w) == ind) { addc = unsigned(w); addf = (nw_con(w) ? 1u : 0u) | (nw_poi(w) ? 2u : 0u); }
+    for (int hops = 0;;) {
+        if (addc) __hip_atomic_fetch_add(&sCnt[cur], addc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (addf) atomicOr(&sFlag[cur >> 4], addf << (2 * (cur & 15)));
+        const int t = sT[cur];
+        if (t < 0 || ++hops >= TS * TS) break;   // (the bound ends a walk on an in-tile cycle)
+        cur = t;
+    }
+}
+// Write-back of a lane's 16 cells (column lx, rows ry0 ..): float32 count, or nodata for a cell that takes no part, is not evaluated or - under contcheck - is
+// contaminated; a count above big_threshold gets BIG_MARK, the plain exact count back into its word (the sort key of ad8_big_keys_kernel) and a place in biglist.
+// role(r) says of row r whether its cell is stored at all and whether it takes part.
+struct Ad8RowRole { bool store, part; };
+template <class Role>
+__device__ __forceinline__ void apply_write_back(const Ad8Geom& g, int x0, int ya0, int lx, int ry0, const unsigned* sCnt, const unsigned* sFlag, int contcheck,
+                                                 unsigned big_threshold, uint32_t* __restrict__ cellw, float* __restrict__ A, uint32_t* __restrict__ biglist,
+                                                 unsigned long long* __restrict__ nbig, Role role) {
+    unsigned bigmask = 0;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int ly = ry0 + r, c = ly * TS + lx;
+        const Ad8RowRole ro = role(r);
+        if (!ro.store) continue;
+        const size_t idx = size_t(ya0 + ly) * size_t(g.nx) + size_t(x0 + lx);
+        const unsigned cnt = sCnt[c];
+        const unsigned fl = (sFlag[c >> 4] >> (2 * (c & 15))) & 3u;
+        const bool con = (fl & 1u) != 0u, poi = (fl & 2u) != 0u;
+        float a = TDX_AREA_NODATA;
+        if (ro.part && !poi && !(con && contcheck == 1)) {
+            if (cnt > big_threshold) { a = BIG_MARK; bigmask |= 1u << r; cellw[idx] = cnt; }
+            else a = (float)cnt;   // exact: cnt <= 2^24
+        }
+        A[idx] = a;
+    }
+    unsigned long long pos = block_reserve(unsigned(__popc(bigmask)), nbig);
+#pragma unroll
+    for (int r = 0; r < 16; r++)
+        if (bigmask & (1u << r)) biglist[pos++] = uint32_t(size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0 + lx));
+}
+
+// Phase C.  (93 VGPRs: five tiles per CU.  Held to 80 - six tiles, as the LDS allows - it spills 15 registers in the first phase and is 13 % slower: profiles/r05l_*)
 // list / nlist: the redo list of ad8_tile_fast_kernel and its device-side length (one workgroup per tile of the raster, as the redo launch of ad8_tile_local_kernel);
 // null: every tile
-// TDX_AD8_DEBUG=1: phase cycles of ad8_tile_apply_kernel ([0, 4): stage, topology, entry walks, write-back; [4] tiles) and, from [8], of ad8_tile_apply_fast_kernel
-// ([8, 12): load, targets, entry walks, write-back; [12] tiles), summed over the tiles (thread 0)
-__device__ unsigned long long g_ad8_dbg_apply[16];
 template <bool DBG>
 __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __restrict__ P, Ad8Geom g, int16_t nodata,
                                                              uint32_t* __restrict__ cellw, const unsigned long long* __restrict__ node_acc,
@@ -852,9 +920,8 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
                                                              unsigned long long* __restrict__ nbig,
                                                              const uint32_t* __restrict__ list, const unsigned long long* __restrict__ nlist) {
     if (list && blockIdx.x >= *nlist) return;
-    unsigned long long tcs[5];
-#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
-    AD8_MARK(0);
+    Ad8Clock<DBG, 5> clk;
+    clk.mark(0);
     // 26 KB of LDS per tile: counts (32 bit), the two flags as a bit set, and the staged tile of one-hot direction codes, which the 64-pitch table of
     // in-tile targets replaces once the topology has been derived (the ring's codes set aside in sRing) - as in ad8_tile_local_kernel
     __shared__ uint16_t sO[TH * TH];
@@ -863,17 +930,14 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
     __shared__ uint16_t sRing[4 * TH];
     int16_t* const sT = reinterpret_cast<int16_t*>(sO);
     const int tile = list ? int(list[blockIdx.x]) : int(blockIdx.x);
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
-    const int x0 = tx * TS, ya0 = g.y0 + ty * TS, rv = rows_valid(g, ty);
+    const Ad8Tile to = tile_origin(g, tile);
+    const int x0 = to.x0, ya0 = to.ya0, rv = to.rv;
     const int tid = threadIdx.x, lx = tid & 63, ry0 = (tid >> 6) * 16;
     stage_p_onehot(P, g.nx, g.ny_arr, x0, ya0, nodata, sO);
     sFlag[tid] = 0u;
     __syncthreads();
-    AD8_MARK(1);
-    for (int j = tid; j < 4 * TH; j += 256) {
-        int hx, hy;
-        sRing[j] = ring_cell(j, rv, hx, hy) ? sO[(hy + 1) * TH + hx + 1] : uint16_t(0);
-    }
+    clk.mark(1);
+    ring_set_aside(sO, sRing, rv);
     int16_t tgt[16];
     unsigned partmask = 0;
     {
@@ -915,7 +979,6 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
         }
     }
     __syncthreads();   // every lane is done reading directions: the target table takes the tile's place
-#define S_TGT(c) sT[c]
     // (entry cells are looked up through the ring's codes in sRing)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -923,7 +986,7 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
         if (ry0 + r < rv) sT[(ry0 + r) * TS + lx] = (tgt[r] >= 0) ? tgt[r] : (((partmask >> r) & 1u) ? int16_t(-3) : int16_t(-1));
     }
     __syncthreads();
-    AD8_MARK(2);
+    clk.mark(2);
     for (int j = tid; j < 4 * TH; j += 256) {
         int hx, hy;
         if (!ring_cell(j, rv, hx, hy)) continue;
@@ -932,55 +995,15 @@ __global__ __launch_bounds__(256) void ad8_tile_apply_kernel(const int16_t* __re
         const int ph = __ffs(int(dirs)) - 1;
         const int vx = hx + d1(ph), vy = hy + d2(ph);
         if (!in_tile(vx, vy, rv)) continue;
-        int cur = vy * TS + vx, hops = 0;
-        if (S_TGT(cur) == -1) continue;   // the entry cell does not participate
-        const uint32_t nid = node_id(g, x0 + hx, ya0 + hy);
-        const uint32_t ind = node_indeg[nid];
-        const unsigned long long w = node_acc[nid];
-        unsigned addc = 0, addf = 2u;     // a crossing that never delivers leaves everything below it unevaluated
-        if (ind < NODE_DEAD && nw_arr(w) == ind) { addc = unsigned(w); addf = (nw_con(w) ? 1u : 0u) | (nw_poi(w) ? 2u : 0u); }
-        for (;;) {
-            if (addc) __hip_atomic_fetch_add(&sCnt[cur], addc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (addf) atomicOr(&sFlag[cur >> 4], addf << (2 * (cur & 15)));
-            const int t = S_TGT(cur);
-            if (t < 0 || ++hops >= TS * TS) break;
-            cur = t;
-        }
+        const int cur = vy * TS + vx;
+        if (sT[cur] == -1) continue;   // the entry cell does not participate
+        apply_entering_crossing(node_id(g, x0 + hx, ya0 + hy), cur, node_acc, node_indeg, sCnt, sFlag, sT);
     }
     __syncthreads();
-    AD8_MARK(3);
-    unsigned bigmask = 0;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int ly = ry0 + r, c = ly * TS + lx;
-        const int gx = x0 + lx, gy = ya0 + ly;
-        if (gx >= g.nx || ly >= rv) continue;
-        const unsigned cnt = sCnt[c];
-        const unsigned fl = (sFlag[c >> 4] >> (2 * (c & 15))) & 3u;
-        const bool part = (partmask >> r) & 1u;
-        const bool con = (fl & 1u) != 0u, poi = (fl & 2u) != 0u;
-        float a = TDX_AREA_NODATA;
-        if (part && !poi && !(con && contcheck == 1)) {
-            if (cnt > big_threshold) { a = BIG_MARK; bigmask |= 1u << r; cellw[size_t(gy) * size_t(g.nx) + size_t(gx)] = cnt; }
-            else a = (float)cnt;   // exact: cnt <= 2^24
-        }
-        A[size_t(gy) * size_t(g.nx) + size_t(gx)] = a;
-    }
-#undef S_TGT
-    const unsigned long long pos0 = block_reserve(unsigned(__popc(bigmask)), nbig);
-    unsigned long long pos = pos0;
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-        if (bigmask & (1u << r)) biglist[pos++] = uint32_t(size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0 + lx));
-    if (DBG) {
-        __syncthreads();
-        AD8_MARK(4);
-        if (tid == 0) {
-            for (int i = 0; i < 4; i++) atomicAdd(&g_ad8_dbg_apply[i], tcs[i + 1] - tcs[i]);
-            atomicAdd(&g_ad8_dbg_apply[4], 1ull);
-        }
-    }
-#undef AD8_MARK
+    clk.mark(3);
+    apply_write_back(g, x0, ya0, lx, ry0, sCnt, sFlag, contcheck, big_threshold, cellw, A, biglist, nbig,
+                     [&](int r) { return Ad8RowRole{x0 + lx < g.nx && ry0 + r < rv, ((partmask >> r) & 1u) != 0u}; });
+    clk.flush(AD8_CLK_APPLY);
 }
 
 // Phase C of the tiles that ad8_tile_fast_kernel finished: their words are marked (cw_code != 0) and carry each cell's direction, so nothing of p's tile interior
@@ -993,18 +1016,16 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_apply_fast_kernel(const int16
                                                                   const unsigned long long* __restrict__ node_acc, const uint32_t* __restrict__ node_indeg,
                                                                   int contcheck, unsigned big_threshold, float* __restrict__ A, uint32_t* __restrict__ biglist,
                                                                   unsigned long long* __restrict__ nbig) {
-    unsigned long long tcs[5];
-#define AD8_MARK(i) do { if (DBG) tcs[i] = clock64(); } while (0)
-    AD8_MARK(0);
+    Ad8Clock<DBG, 5> clk;
+    clk.mark(0);
     __shared__ int16_t sT[TS * TS];
     __shared__ unsigned sCnt[TS * TS];
     __shared__ unsigned sFlag[TS * TS / 16];   // 2 bits per cell: contaminated, not evaluated
-    const int tile = blockIdx.x;
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
-    const int x0 = tx * TS, ya0 = g.y0 + ty * TS;
+    const Ad8Tile to = tile_origin(g, int(blockIdx.x));
+    const int x0 = to.x0, ya0 = to.ya0;
     const int tid = threadIdx.x, lx = tid & 63, ry0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 16;   // (a scalar: as in ad8_tile_fast_kernel)
-    // (the fast kernel's uniform test: no other tile holds marked words, and with it every address below lies in the array)
-    if (rows_valid(g, ty) != TS || x0 < 1 || x0 + TS >= g.nx || ya0 < 1 || ya0 + TS >= g.ny_arr) return;
+    // (the fast kernel's test: no other tile holds marked words, and with it every address below lies in the array)
+    if (!tile_window_whole(g, to)) return;
     uint32_t cw[16];
     int16_t pr[2];
     int rhx[2], rhy[2];
@@ -1017,7 +1038,7 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_apply_fast_kernel(const int16
         pr[k] = P[size_t(ya0 + rhy[k]) * size_t(g.nx) + size_t(x0 + rhx[k])];
     }
     if (cw_code(cw[0]) == 0u) return;   // not finished by the fast kernel; all words of a tile are marked alike, so the workgroup leaves as one
-    AD8_MARK(1);
+    clk.mark(1);
     sFlag[tid] = 0u;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
@@ -1028,57 +1049,18 @@ __global__ __launch_bounds__(256, 6) void ad8_tile_apply_fast_kernel(const int16
         sCnt[ly * TS + lx] = cw[r] & CW_FAST_CNT_MASK;
     }
     __syncthreads();
-    AD8_MARK(2);
+    clk.mark(2);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const int ph = pr[k];   // 1 .. 8: the window is clean
         const int vx = rhx[k] + d1(ph), vy = rhy[k] + d2(ph);
         if (!rhas[k] || !in_tile(vx, vy, TS)) continue;
-        int cur = vy * TS + vx, hops = 0;
-        const uint32_t nid = node_id(g, x0 + rhx[k], ya0 + rhy[k]);
-        const uint32_t ind = node_indeg[nid];
-        const unsigned long long w = node_acc[nid];
-        unsigned addc = 0, addf = 2u;     // a crossing that never delivers leaves everything below it unevaluated
-        if (ind < NODE_DEAD && nw_arr(w) == ind) { addc = unsigned(w); addf = (nw_con(w) ? 1u : 0u) | (nw_poi(w) ? 2u : 0u); }
-        for (;;) {
-            if (addc) __hip_atomic_fetch_add(&sCnt[cur], addc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (addf) atomicOr(&sFlag[cur >> 4], addf << (2 * (cur & 15)));
-            const int t = sT[cur];
-            if (t < 0 || ++hops >= TS * TS) break;
-            cur = t;
-        }
+        apply_entering_crossing(node_id(g, x0 + rhx[k], ya0 + rhy[k]), vy * TS + vx, node_acc, node_indeg, sCnt, sFlag, sT);
     }
     __syncthreads();
-    AD8_MARK(3);
-    unsigned bigmask = 0;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int ly = ry0 + r, c = ly * TS + lx;
-        const size_t idx = size_t(ya0 + ly) * size_t(g.nx) + size_t(x0 + lx);
-        const unsigned cnt = sCnt[c];
-        const unsigned fl = (sFlag[c >> 4] >> (2 * (c & 15))) & 3u;
-        const bool con = (fl & 1u) != 0u, poi = (fl & 2u) != 0u;
-        float a = TDX_AREA_NODATA;
-        if (!poi && !(con && contcheck == 1)) {
-            if (cnt > big_threshold) { a = BIG_MARK; bigmask |= 1u << r; cellw[idx] = cnt; }   // the plain count: ad8_big_keys_kernel sorts by this word
-            else a = (float)cnt;   // exact: cnt <= 2^24
-        }
-        A[idx] = a;
-    }
-    const unsigned long long pos0 = block_reserve(unsigned(__popc(bigmask)), nbig);
-    unsigned long long pos = pos0;
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-        if (bigmask & (1u << r)) biglist[pos++] = uint32_t(size_t(ya0 + ry0 + r) * size_t(g.nx) + size_t(x0 + lx));
-    if (DBG) {
-        __syncthreads();
-        AD8_MARK(4);
-        if (tid == 0) {
-            for (int i = 0; i < 4; i++) atomicAdd(&g_ad8_dbg_apply[8 + i], tcs[i + 1] - tcs[i]);
-            atomicAdd(&g_ad8_dbg_apply[12], 1ull);
-        }
-    }
-#undef AD8_MARK
+    clk.mark(3);
+    apply_write_back(g, x0, ya0, lx, ry0, sCnt, sFlag, contcheck, big_threshold, cellw, A, biglist, nbig, [](int) { return Ad8RowRole{true, true}; });
+    clk.flush(AD8_CLK_APPLY_FAST);
 }
 
 // ---- big cells: exact k-ordered float32 re-evaluation in dependency order ----
@@ -1436,7 +1418,46 @@ __global__ __launch_bounds__(64) void ad8_big_fold_kernel(int contcheck, int sca
 int tdx_sort_pairs_u32(tdx_context* ctx, int scratch_slot, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
                        size_t n);   // sort_pairs.hip
 
+// The switches of the tile-contraction path (docs/environment_switches.md), read at the top of EVERY call: the tests set them per call inside one process.
+struct Ad8Options {
+    bool kahn_only, apply_fast, kahn_nested, big_one_wave;
+    unsigned big_threshold, big_ring;
+    int big_scan;
+    Ad8Options() {
+        const auto is = [](const char* name, const char* value) { const char* v = getenv(name); return v && strcmp(v, value) == 0; };
+        kahn_only = is("TDX_AD8_LOCAL", "kahn");                  // every tile to ad8_tile_local_kernel and ad8_tile_apply_kernel (A/B hook and witness)
+        apply_fast = !kahn_only && !is("TDX_AD8_APPLY", "full");  // full: plain words from the fast kernel, ad8_tile_apply_kernel on every tile (A/B hook)
+        kahn_nested = getenv("TDX_AD8_KAHN_NESTED") != nullptr;   // the walk loop nested in the loop over a lane's sources (A/B hook)
+        big_threshold = getenv("TDX_AD8_BIG_THRESHOLD") ? unsigned(atol(getenv("TDX_AD8_BIG_THRESHOLD"))) : (1u << 24);   // counts above it are big cells (test hook)
+        big_one_wave = getenv("TDX_AD8_BIG_ONE_WAVE") != nullptr;   // one wave folds the whole big-cell list in count order (A/B hook)
+        // in-chunk dependencies of the count-order fold by pointer jumping when at least this many cells of a 64-entry chunk wait for another cell of the chunk
+        // (0: always one after the other - A/B hook)
+        big_scan = getenv("TDX_AD8_BIG_SCAN") ? std::max(0, atoi(getenv("TDX_AD8_BIG_SCAN"))) : 4;
+        // entries of the fold's LDS ring (test hook, rounded to a multiple of 64 in [64, BIG_LDS]: trees longer than that at test sizes)
+        big_ring = getenv("TDX_AD8_BIG_RING") ? std::min(BIG_LDS, std::max(64u, unsigned(atoi(getenv("TDX_AD8_BIG_RING"))) / 64u * 64u)) : BIG_LDS;
+    }
+};
+
+// The tile launches of one phase: launches(std::bool_constant<DBG>) enqueues them with that instantiation.  Under TDX_AD8_DEBUG=1 (read once per process) the clock
+// rows are zeroed in front of them and read behind them, and print(rows) writes the "cycles per tile" lines (the profile scripts grep their wording and field order).
+using Ad8ClockRows = unsigned long long[AD8_CLK_KERNELS][8];
+static unsigned long long ad8_tiles(const unsigned long long* row) { return row[7] & 0xFFFFFFFFull; }
+static double ad8_per_tile(const unsigned long long* row, unsigned long long sum) { return double(sum) / double(std::max(ad8_tiles(row), 1ull)); }
+template <class Launches, class Print>
+static int ad8_clocked_launches(tdx_context* ctx, Launches launches, Print print) {
+    static const bool debug = getenv("TDX_AD8_DEBUG") != nullptr;
+    if (!debug) { launches(std::false_type{}); return TDX_OK; }
+    Ad8ClockRows z = {};
+    TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_clk), z, sizeof(z)));
+    launches(std::true_type{});
+    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_clk), sizeof(z)));
+    print(z);
+    return TDX_OK;
+}
+
 static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, int contcheck, float* d_ad8, tdx_stats* stats) {
+    const Ad8Options opt;
     hipStream_t s = ctx->stream;
     const int inx = st.nx;
     const size_t n = size_t(st.nx) * size_t(st.ny_arr);
@@ -1450,18 +1471,15 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
     unsigned long long* node_acc = static_cast<unsigned long long*>(ctx->scratch(TDX_S_B, nnodes * 8));
     uint32_t* node_indeg = static_cast<uint32_t*>(ctx->scratch(TDX_S_C, nnodes * 4));
     uint32_t* node_next = static_cast<uint32_t*>(ctx->scratch(TDX_S_D, nnodes * 4));
-    const unsigned big_threshold = getenv("TDX_AD8_BIG_THRESHOLD") ? unsigned(atol(getenv("TDX_AD8_BIG_THRESHOLD"))) : (1u << 24);   // test hook
+    const unsigned big_threshold = opt.big_threshold;
+    const bool kahn_only = opt.kahn_only, apply_fast = opt.apply_fast;
     const size_t bigcap = big_threshold < (1u << 24) ? n : n / 8 + 4096;
     uint32_t* biglist = static_cast<uint32_t*>(ctx->scratch(TDX_S_E, bigcap * 4));
     unsigned long long* boxes = static_cast<unsigned long long*>(ctx->scratch(TDX_S_F, size_t(st.nx) * 4 * 8));   // out-box[2nx], in-box[2nx]
     uint8_t* delivered = static_cast<uint8_t*>(ctx->scratch(TDX_S_G, size_t(st.nx) * 2));
     uint32_t* redo = static_cast<uint32_t*>(ctx->scratch(TDX_S_K, ntiles * 4));   // tiles that ad8_tile_fast_kernel left to the Kahn sweep
     if (!cellw || !node_acc || !node_indeg || !node_next || !biglist || !boxes || !delivered || !redo) return TDX_ERR_NOMEM;
-    const char* const ad8_local = getenv("TDX_AD8_LOCAL");   // "kahn": every tile to ad8_tile_local_kernel (A/B hook and witness, read per call)
-    const bool kahn_only = ad8_local && strcmp(ad8_local, "kahn") == 0;
-    const char* const ad8_apply = getenv("TDX_AD8_APPLY");   // "full": plain words from the fast kernel, ad8_tile_apply_kernel on every tile (A/B hook, read per call)
-    const bool apply_fast = !kahn_only && !(ad8_apply && strcmp(ad8_apply, "full") == 0);
-    const unsigned mark = apply_fast ? 1u : 0u;
+    const unsigned mark = apply_fast ? 1u : 0u, nt = unsigned(ntiles);
     unsigned long long *outbox = boxes, *inbox = boxes + 2 * size_t(st.nx);
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ctx->d_mail);
     unsigned long long* nredo = d_cnt + 7;   // (cleared with the other stage counters by ad8_init_kernel)
@@ -1474,36 +1492,26 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
                        delivered, size_t(st.nx));
     {
         TdxSpan sp(ctx, TDX_K_STENCIL);
-        static const bool ad8_debug = getenv("TDX_AD8_DEBUG") != nullptr;
-        const unsigned nt = unsigned(ntiles);
         // the clean tiles by pointer doubling, the others - behind it on the stream, from the device-side redo list - by the Kahn sweep
         const uint32_t* list = kahn_only ? nullptr : redo;
-        if (ad8_debug) {
-            unsigned long long z[8] = {}, zf[8] = {};
-            TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg), z, sizeof(z)));
-            TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg_fast), zf, sizeof(zf)));
-            if (!kahn_only)
-                hipLaunchKernelGGL((ad8_tile_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo, mark);
-            hipLaunchKernelGGL((ad8_tile_local_kernel<true, true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
-            TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-            TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_dbg), sizeof(z)));
-            TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(zf, HIP_SYMBOL(g_ad8_dbg_fast), sizeof(zf)));
-            unsigned long long nr = ntiles;
-            if (!kahn_only) TDX_HIP_CHECK(ctx, hipMemcpy(&nr, nredo, sizeof(nr), hipMemcpyDeviceToHost));
-            const double nk = double(nr ? nr : 1), nf = double(zf[6] ? zf[6] : 1);
-            fprintf(stderr, "ad8_tile_local: %llu tiles, cycles per tile: stage %.0f, topology %.0f, targets %.0f, Kahn walks %.0f, entry walks %.0f, write-back %.0f\n", nr,
-                    double(z[0]) / nk, double(z[1]) / nk, 0.0, double(z[2]) / nk, double(z[3]) / nk, double(z[4]) / nk);
-            if (!kahn_only)
-                fprintf(stderr, "ad8_tile_fast: %llu tiles, cycles per tile: load and vote %.0f, targets %.0f, entry walks %.0f, doubling %.0f, roots and write-back %.0f; %.2f rounds per tile\n", zf[6],
-                        double(zf[0]) / nf, double(zf[1]) / nf, double(zf[2]) / nf, double(zf[3]) / nf, double(zf[4]) / nf, double(zf[5]) / nf);
-        } else {
-            if (!kahn_only)
-                hipLaunchKernelGGL((ad8_tile_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo, mark);
-            if (getenv("TDX_AD8_KAHN_NESTED"))   // (A/B hook, read per call: the walk loop nested in the loop over a lane's sources)
-                hipLaunchKernelGGL((ad8_tile_local_kernel<false, false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
-            else
-                hipLaunchKernelGGL((ad8_tile_local_kernel<false, true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
-        }
+        rc = ad8_clocked_launches(
+            ctx,
+            [&](auto dbg) {
+                constexpr bool DBG = decltype(dbg)::value;
+                if (!kahn_only)
+                    hipLaunchKernelGGL((ad8_tile_fast_kernel<DBG>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, redo, nredo, mark);
+                const auto local = opt.kahn_nested ? ad8_tile_local_kernel<DBG, false> : ad8_tile_local_kernel<DBG, true>;
+                hipLaunchKernelGGL(local, dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, node_next, list, nredo);
+            },
+            [&](const Ad8ClockRows& z) {   // ("targets" of the Kahn sweep and "entry walks" of the doubling are phases that are gone: 0, so that old and new profiles compare)
+                const unsigned long long *k = z[AD8_CLK_LOCAL], *f = z[AD8_CLK_FAST];
+                fprintf(stderr, "ad8_tile_local: %llu tiles, cycles per tile: stage %.0f, topology %.0f, targets %.0f, Kahn walks %.0f, entry walks %.0f, write-back %.0f\n", ad8_tiles(k),
+                        ad8_per_tile(k, k[0]), ad8_per_tile(k, k[1]), 0.0, ad8_per_tile(k, k[2]), ad8_per_tile(k, k[3]), ad8_per_tile(k, k[4]));
+                if (!kahn_only)
+                    fprintf(stderr, "ad8_tile_fast: %llu tiles, cycles per tile: load and vote %.0f, targets %.0f, entry walks %.0f, doubling %.0f, roots and write-back %.0f; %.2f rounds per tile\n", ad8_tiles(f),
+                            ad8_per_tile(f, f[0]), ad8_per_tile(f, f[1]), 0.0, ad8_per_tile(f, f[2]), ad8_per_tile(f, f[3]), ad8_per_tile(f, f[7] >> 32));
+            });
+        if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_STENCIL] += kahn_only ? 1 : 2;   // the fast kernel and the redo launch behind it
     }
     int64_t outer = 1;
@@ -1534,30 +1542,25 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
         TdxSpan sp(ctx, TDX_K_STENCIL);
         // the tiles with marked words by ad8_tile_apply_fast_kernel, the redo list of the fast kernel (untouched since: nothing else uses its scratch slot or
         // stage counter 7 in this call) by ad8_tile_apply_kernel right behind it; without marks - TDX_AD8_LOCAL=kahn, TDX_AD8_APPLY=full - the latter on every tile
-        static const bool ad8_debug = getenv("TDX_AD8_DEBUG") != nullptr;
-        const unsigned nt = unsigned(ntiles);
         const uint32_t* list = apply_fast ? redo : nullptr;
-        if (ad8_debug) {
-            unsigned long long z[16] = {};
-            TDX_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_ad8_dbg_apply), z, sizeof(z)));
-            if (apply_fast)
-                hipLaunchKernelGGL((ad8_tile_apply_fast_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist, d_cnt);
-            hipLaunchKernelGGL((ad8_tile_apply_kernel<true>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist,
-                               d_cnt, list, nredo);
-            TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-            TDX_HIP_CHECK(ctx, hipMemcpyFromSymbol(z, HIP_SYMBOL(g_ad8_dbg_apply), sizeof(z)));
-            const double na = double(z[4] ? z[4] : 1), nf = double(z[12] ? z[12] : 1);
-            fprintf(stderr, "ad8_tile_apply: %llu tiles, cycles per tile: stage %.0f, topology %.0f, entry walks %.0f, write-back %.0f\n", z[4], double(z[0]) / na, double(z[1]) / na,
-                    double(z[2]) / na, double(z[3]) / na);
-            if (apply_fast)
-                fprintf(stderr, "ad8_tile_apply_fast: %llu tiles, cycles per tile: load %.0f, targets %.0f, entry walks %.0f, write-back %.0f\n", z[12], double(z[8]) / nf,
-                        double(z[9]) / nf, double(z[10]) / nf, double(z[11]) / nf);
-        } else {
-            if (apply_fast)
-                hipLaunchKernelGGL((ad8_tile_apply_fast_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist, d_cnt);
-            hipLaunchKernelGGL((ad8_tile_apply_kernel<false>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist,
-                               d_cnt, list, nredo);
-        }
+        rc = ad8_clocked_launches(
+            ctx,
+            [&](auto dbg) {
+                constexpr bool DBG = decltype(dbg)::value;
+                if (apply_fast)
+                    hipLaunchKernelGGL((ad8_tile_apply_fast_kernel<DBG>), dim3(nt), dim3(256), 0, s, d_p, g, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist, d_cnt);
+                hipLaunchKernelGGL((ad8_tile_apply_kernel<DBG>), dim3(nt), dim3(256), 0, s, d_p, g, p_nodata, cellw, node_acc, node_indeg, contcheck, big_threshold, d_ad8, biglist,
+                                   d_cnt, list, nredo);
+            },
+            [&](const Ad8ClockRows& z) {
+                const unsigned long long *a = z[AD8_CLK_APPLY], *f = z[AD8_CLK_APPLY_FAST];
+                fprintf(stderr, "ad8_tile_apply: %llu tiles, cycles per tile: stage %.0f, topology %.0f, entry walks %.0f, write-back %.0f\n", ad8_tiles(a), ad8_per_tile(a, a[0]),
+                        ad8_per_tile(a, a[1]), ad8_per_tile(a, a[2]), ad8_per_tile(a, a[3]));
+                if (apply_fast)
+                    fprintf(stderr, "ad8_tile_apply_fast: %llu tiles, cycles per tile: load %.0f, targets %.0f, entry walks %.0f, write-back %.0f\n", ad8_tiles(f), ad8_per_tile(f, f[0]),
+                            ad8_per_tile(f, f[1]), ad8_per_tile(f, f[2]), ad8_per_tile(f, f[3]));
+            });
+        if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_STENCIL] += apply_fast ? 2 : 1;
     }
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_mail, d_cnt, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // the big cells and, word 7, the redone tiles
@@ -1580,15 +1583,8 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
         uint32_t *keys_sorted = keys + nb1, *sorted = keys_sorted + nb1, *rootA = sorted + nb1, *rootB = rootA + nb1, *grouped = rootB + nb1, *listB = grouped + nb1,
                  *segbeg = listB + nb1;
         uint32_t* pos = cellw;   // list position of every big cell (the per-cell words are no longer needed once the keys are out)
-        const bool no_trees = getenv("TDX_AD8_BIG_ONE_WAVE") != nullptr;                   // (A/B hook, read per call: one wave folds the whole list in count order)
         // count order, one wave per tree.  (Round 5 also built the fold in LEVEL order - distance to the tree's root, no serial step inside a chunk: bit-identical and
         // 3 - 5 x slower, a level step is a chain of dependent LDS round trips where this fold hands a value on in registers; docs/experiments_r05.md section 1.  Retired in round 6.)
-        static const bool no_incremental = getenv("TDX_AD8_BIG_FULL_ROUNDS") != nullptr;   // (A/B hook: every outer round on the whole list)
-        // in-chunk dependencies of the count-order fold by pointer jumping when at least this many cells of a 64-entry chunk wait for another cell of the chunk
-        // (TDX_AD8_BIG_SCAN=0: always one after the other - A/B hook; read per call)
-        const int big_scan = getenv("TDX_AD8_BIG_SCAN") ? std::max(0, atoi(getenv("TDX_AD8_BIG_SCAN"))) : 4;
-        // entries of the fold's LDS ring (TDX_AD8_BIG_RING: test hook, rounded to a multiple of 64 in [64, BIG_LDS]: trees longer than that at test sizes)
-        const unsigned big_ring = getenv("TDX_AD8_BIG_RING") ? std::min(BIG_LDS, std::max(64u, unsigned(atoi(getenv("TDX_AD8_BIG_RING"))) / 64u * 64u)) : BIG_LDS;
         uint32_t *cur = sorted, *cur_root = rootA, *other = listB, *other_root = rootB;
         unsigned long long* n_cur = d_cnt;            // the apply pass's counter = the first list's length
         const unsigned gb = tdx_blocks_for(nb1, 256);
@@ -1596,7 +1592,7 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
             hipLaunchKernelGGL(ad8_big_keys_kernel, dim3(gb), dim3(256), 0, s, biglist, nbig, cellw, keys);
             rc = tdx_sort_pairs_u32(ctx, TDX_S_I, keys, keys_sorted, biglist, sorted, size_t(nbig));
             if (rc != TDX_OK) return rc;
-            if (!no_trees) {
+            if (!opt.big_one_wave) {
                 hipLaunchKernelGGL(ad8_big_pos_kernel, dim3(gb), dim3(256), 0, s, sorted, n_cur, pos);
                 hipLaunchKernelGGL(ad8_big_next_kernel, dim3(gb), dim3(256), 0, s, d_p, inx, st.y0, st.y1, sorted, nbig, pos, d_ad8, rootA);
                 uint32_t *ra = rootA, *rb = rootB;
@@ -1627,15 +1623,15 @@ static int aread8_tiled(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t
                 hipLaunchKernelGGL(ad8_big_pos_kernel, dim3(gb), dim3(256), 0, s, cur, n_cur, pos);
                 hipLaunchKernelGGL(ad8_big_gather_kernel, dim3(gb), dim3(256), 0, s, d_p, inx, st.ny_arr, st.y0, st.y1, p_nodata, cur, n_cur, pos, d_ad8, big_vals,
                                    big_deps, big_flags, big_val);
-                if (no_trees)
-                    hipLaunchKernelGGL(ad8_big_fold_kernel, dim3(1), dim3(64), 0, s, contcheck, big_scan, big_ring, cur, n_cur, static_cast<const uint32_t*>(nullptr),
+                if (opt.big_one_wave)
+                    hipLaunchKernelGGL(ad8_big_fold_kernel, dim3(1), dim3(64), 0, s, contcheck, opt.big_scan, opt.big_ring, cur, n_cur, static_cast<const uint32_t*>(nullptr),
                                        static_cast<const unsigned long long*>(nullptr), big_vals, big_deps, big_flags, big_val, d_ad8, d_cnt + 2);
                 else {
                     hipLaunchKernelGGL(ad8_big_segments_kernel, dim3(1), dim3(1024), 0, s, cur_root, n_cur, segbeg, d_cnt + 6);
-                    hipLaunchKernelGGL(ad8_big_fold_kernel, dim3(unsigned(std::min<unsigned long long>(nbig, 2ull * unsigned(ctx->num_cus)))), dim3(64), 0, s, contcheck, big_scan, big_ring, cur,
+                    hipLaunchKernelGGL(ad8_big_fold_kernel, dim3(unsigned(std::min<unsigned long long>(nbig, 2ull * unsigned(ctx->num_cus)))), dim3(64), 0, s, contcheck, opt.big_scan, opt.big_ring, cur,
                                        n_cur, segbeg, d_cnt + 6, big_vals, big_deps, big_flags, big_val, d_ad8, d_cnt + 2);
                 }
-                if (st.multi() && !no_incremental) {
+                if (st.multi()) {
                     unsigned long long* n_next = d_cnt + 4 + flip;
                     hipLaunchKernelGGL(ad8_big_compact_kernel, dim3(1), dim3(1024), 0, s, cur, cur_root, n_cur, d_ad8, other, other_root, n_next);
                     std::swap(cur, other);

@@ -349,3 +349,60 @@ def test_single_strip_form(ctx, oracle, monkeypatch):
             _set_mode(monkeypatch, {})
             assert bits_equal(got, ref), describe_diff(got, ref, f"single strip, {mode}, contcheck={cc}")
             assert _counters(ctx) == ((0, 9) if mode == "kahn" else (1, 8)), f"single strip, {mode}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# TDX_AD8_DEBUG=1: the clocked instantiations of the four tile kernels
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+_DEBUG_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import taudem_amd
+with taudem_amd.Context(0) as ctx:
+    np.save(sys.argv[3], ctx.aread8(np.load(sys.argv[2]), -32768))
+"""
+_CLOCK_FIELDS = {"ad8_tile_local": 6, "ad8_tile_fast": 6, "ad8_tile_apply": 4, "ad8_tile_apply_fast": 4}   # (the fast kernel's sixth: rounds per tile)
+
+
+def test_debug_clocks_in_a_child_process(tmp_path):
+    """TDX_AD8_DEBUG is read once per process, so the clocked (<true>) instantiations run in a child process and the baseline in a second one, which never saw the switch.
+    192 x 192 draining east: of the 3 x 3 tiles only the middle one is clean, and its left ring column enters it.  Same bits with and without the clocks, one
+    "cycles per tile" line per tile kernel, tile counts (redone, clean, redone, clean) as ad8_tiles.clean_tiles gives them, every figure a non-negative number."""
+    import os
+    import re
+    import subprocess
+    import sys
+
+    p = np.full((192, 192), T.E, dtype=np.int16)
+    clean = _clean_tiles(p)
+    assert clean == {(1, 1)} and len(T.ring_entry_cells(p, TS, TS)) >= 1
+    redone = 9 - len(clean)
+    np.save(tmp_path / "p.npy", p)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {}
+    for name, debug in (("plain", False), ("clocked", True)):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("TDX_AD8_")}
+        if debug:
+            env["TDX_AD8_DEBUG"] = "1"
+        r = subprocess.run([sys.executable, "-c", _DEBUG_CHILD, root, str(tmp_path / "p.npy"), str(tmp_path / f"{name}.npy")], env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, f"{name}\n--- stdout\n{r.stdout[-3000:]}\n--- stderr\n{r.stderr[-6000:]}"
+        runs[name] = (np.load(tmp_path / f"{name}.npy"), r.stderr)
+    assert bits_equal(runs["clocked"][0], runs["plain"][0]), describe_diff(runs["clocked"][0], runs["plain"][0], "TDX_AD8_DEBUG=1 against a process without it")
+    assert not any(l.startswith("ad8_tile_") for l in runs["plain"][1].splitlines()), "no clock line without the switch"
+    lines = [l for l in runs["clocked"][1].splitlines() if l.startswith("ad8_tile_")]
+    print("\n".join(lines))
+    want_tiles = {"ad8_tile_local": redone, "ad8_tile_fast": len(clean), "ad8_tile_apply": redone, "ad8_tile_apply_fast": len(clean)}
+    for kernel, nfields in _CLOCK_FIELDS.items():
+        mine = [l for l in lines if l.startswith(kernel + ":")]
+        assert len(mine) == 1, f"exactly one line of {kernel}: {lines}"
+        m = re.fullmatch(rf"{kernel}: (\d+) tiles, cycles per tile: (.*)", mine[0])
+        assert m, mine[0]
+        assert int(m.group(1)) == want_tiles[kernel], mine[0]
+        fields = re.split(r"[,;]", m.group(2))
+        assert len(fields) == nfields, mine[0]
+        for f in fields:
+            numbers = [w for w in f.split() if re.fullmatch(r"\d+(\.\d+)?", w)]
+            assert len(numbers) == 1 and float(numbers[0]) >= 0.0, f"{mine[0]}: field {f!r}"
+    assert len(lines) == 4, lines
