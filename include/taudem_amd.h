@@ -656,6 +656,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* AreaD8's tile counters (a diagnostic getter): likewise */
 #include "taudem_amd_ad8.h"
 
+/* StreamNet (compute entry points, the link rows and file-level tool function): likewise */
+#include "taudem_amd_streamnet.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ Layers: ``csrc/`` hand-written HIP kernels + the C ABI of ``include/taudem_amd.h
 file-level tool functions; ``dist`` row-strip multi-GPU orchestration over torch.distributed (RCCL).
 """
 from ._lib import LIB_PATH, TdxError, load  # noqa: F401
-from .api import (ANG_NODATA, AREA_NODATA, FEL_NODATA, P_NODATA, SLOPE_NODATA, Context, catchhydrogeo, dropanalysis, dropanalysis_table, inundepth, peukerdouglas, raster_info,  # noqa: F401
+from .api import (ANG_NODATA, AREA_NODATA, FEL_NODATA, P_NODATA, SLOPE_NODATA, Context, StreamNetLinks, catchhydrogeo, dropanalysis, dropanalysis_table, inundepth, peukerdouglas, raster_info, streamnet, streamnet_text,  # noqa: F401
                   read_raster, synth_base_wavelength, write_raster)
 
 __version__ = "0.1.0"

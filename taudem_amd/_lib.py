@@ -276,6 +276,30 @@ _AD8_SIGNATURES = {
 }
 AD8_SYMBOLS = tuple(_AD8_SIGNATURES)
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_streamnet.h declares, the fourth extension header
+_STREAMNET_HEAD = [_P, _P, _P, _P, _P, _I64, _I64, _I16, C.c_int32, _P, _P, _D, _D, _P, _P, _P, _P, _I64, _INT, _P, _P, C.POINTER(_P), _P]
+_STREAMNET_SIGNATURES = {
+    # StreamNet: ctx, p, src, fel, ad8, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, single_watershed, ord, w,
+    # &links, stats
+    "tdx_streamnet": (C.c_int, _STREAMNET_HEAD),
+    "tdx_streamnet_dev": (C.c_int, _STREAMNET_HEAD),
+    "tdx_streamnet_links_count": (_I64, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "tdx_streamnet_links_copy": (None, [_P, _P, _P, _P]),
+    "tdx_streamnet_links_free": (None, [_P]),
+    # strips: ctx, comm, p, src, fel, ad8, nx, ny_local, row0, p_nodata, src_nodata, dxc, dyc, &part, stats
+    "tdx_streamnet_compact_strip": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I16, C.c_int32, _P, _P, C.POINTER(_P), _P]),
+    "tdx_streamnet_compact_count": (_I64, [_P]),
+    "tdx_streamnet_compact_free": (None, [_P]),
+    # parts, n_parts, nx, ny, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, &links
+    "tdx_streamnet_links_build": (C.c_int, [_P, _I64, _I64, _I64, _D, _D, _P, _P, _P, _P, _I64, C.POINTER(_P)]),
+    # ctx, comm, p, src, nx, ny_local, p_nodata, src_nodata, part, links, first_cell, single_watershed, ord, w, stats
+    "tdx_streamnet_label_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I16, C.c_int32, _P, _P, _I64, _INT, _P, _P, _P]),
+    "tdx_streamnet_write_text": (C.c_int, [_P, C.c_char_p, C.c_char_p]),
+    "tdx_tool_streamnet": (C.c_int, [C.c_char_p] * 9 + [C.c_int, C.c_int] + [C.c_char_p] * 3 + [C.c_long, C.c_long, C.c_int]),
+}
+STREAMNET_SYMBOLS = tuple(_STREAMNET_SIGNATURES)
+STREAMNET_PHASES = ("setup", "length", "compact", "links", "scatter", "label", "total")
+
 _lib = None
 
 
@@ -299,7 +323,7 @@ def load():
     except Exception:  # pragma: no cover - torch-less hosts use the system ROCm runtime
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

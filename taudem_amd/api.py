@@ -178,7 +178,26 @@ class _PeukerDouglasStage:
         return _ret(_peukerdouglas(_Call(self), fel, nodata, weights, float_weights, out), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage):
+class _StreamNetStage:
+    """Context.streamnet; its entry points are those of include/taudem_amd_streamnet.h."""
+
+    def streamnet(self, p, src, fel, ad8, outlets=None, single_watershed=False, *, dx=1.0, dy=1.0, geotransform=None, nodata=int(P_NODATA),
+                  src_nodata=int(P_NODATA), out=None, phases=False, stats=False):
+        """ord, w, tree, coord = streamnet(p, src, fel, ad8)  (src/streamnet.cpp:372): the stream network of the stream raster src on the D8 directions p.
+
+        ord int16: the Strahler order on the stream cells (src not nodata, src > 0, p not nodata), 0 elsewhere.  w int32: the id of the link that
+        drains each cell, the catchment grid catchhydrogeo and inundepth take; -2147483647 where no stream is reached; single_watershed (-sw): 1
+        instead of the ids.  tree int64 (links, 9): link, first and last row of its points in coord, downstream link, the two upstream links,
+        order, outlet id, magnitude.  coord float64 (points, 5): x, y, distance to the outlet along the stream, elevation, contributing area
+        (ad8 times the middle row's cell area) - the rows of the reference's -tree and -coord files on one rank, in its order.
+        src int32, fel / ad8 float32 (read without a nodata test).  outlets: (columns, rows[, ids]) in file order: an outlet on a stream cell ends a
+        link there.  geotransform: GDAL's six numbers of the raster file (default: left edge 0, top edge 0, cells of dx x dy of the middle row).
+        tree and coord are numpy arrays on the host for either side; phases=True also returns, after coord, the wall milliseconds of the call's
+        phases as a dict (setup, length, compact, links, scatter, label, total).  out: (ord, w)."""
+        return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -670,6 +689,124 @@ def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh,
     st = f.call("tdx_dropanalysis", *head, abs(float(dxc[f.rows // 2])), abs(float(dyc[f.rows // 2])), *ladder, _v(scal[0:1]), _v(scal[1:2]), _v(found),
                 C.cast(text, C.c_void_p), len(text))
     return (thresh, n1, n2, sums, length, scal[0], text.value.decode(), scal[1] if found[0] else None) + extra + (st,)
+
+
+def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases):
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    pf = f.raster(fel, np.float32, "fel")
+    pa = f.raster(ad8, np.float32, "ad8")
+    pdx, pdy = f.cells(dx, dy)
+    dxc, dyc = f.keep[0], f.keep[1]
+    dxa, dya = abs(float(dxc[f.rows // 2])), abs(float(dyc[f.rows // 2]))
+    gt = (0.0, dxa, 0.0, 0.0, 0.0, -dya) if geotransform is None else tuple(float(v) for v in geotransform)
+    if len(gt) != 6:
+        raise ValueError("geotransform: need GDAL's six numbers")
+    g4 = np.array([gt[0], abs(gt[1]), gt[3], abs(gt[5])], np.float64)   # src/tiffIO.cpp:96-99
+    if outlets is None:
+        ox = oy = ids = np.zeros(0, np.int32)
+    else:
+        ox, oy = _flat(outlets[0], np.int32), _flat(outlets[1], np.int32)
+        ids = _flat(outlets[2], np.int32) if len(outlets) > 2 else np.arange(1, ox.size + 1, dtype=np.int32)
+        if ox.shape != oy.shape or ox.shape != ids.shape:
+            raise ValueError("outlets: need equal-length 1-D arrays (columns, rows[, ids])")
+    o_ord, o_w = out if out is not None else (None, None)
+    ordg, po = f.out(o_ord, np.int16, "ord")
+    w, pw = f.out(o_w, np.int32, "w")
+    links = C.c_void_p()
+    lib = f.ctx._lib
+    st = f.call("tdx_streamnet", pp, ps, pf, pa, f.nx, f.ny, int(nodata), int(src_nodata), pdx, pdy, dxa, dya, _v(g4), _v(ox) if ox.size else None,
+                _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), int(bool(single_watershed)), po, pw, C.byref(links))
+    try:
+        tree, coord, ms = _links_rows(lib, links, phases=True)
+    finally:
+        lib.tdx_streamnet_links_free(links)
+    res = (ordg, w, tree, coord)
+    if phases:
+        res += (ms,)
+    return res + (st,)
+
+
+def _links_rows(lib, links, phases=False):
+    """(tree, coord[, phase dict]) of a tdx_streamnet_links handle."""
+    npts = C.c_int64(0)
+    nl = int(lib.tdx_streamnet_links_count(links, C.byref(npts), None))
+    tree, coord, ms = np.empty((nl, 9), np.int64), np.empty((npts.value, 5), np.float64), np.zeros(len(_lib.STREAMNET_PHASES), np.float64)
+    lib.tdx_streamnet_links_copy(links, _v(tree), _v(coord), _v(ms))
+    return (tree, coord, dict(zip(_lib.STREAMNET_PHASES, ms.tolist()))) if phases else (tree, coord)
+
+
+def _streamnet_compact(f, p, src, fel, ad8, row0, dx, dy, nodata, src_nodata):
+    """A strip's part of the stream cells (a handle: StreamNetLinks takes the parts of all strips) after the length sweep on the strip."""
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    pf = f.raster(fel, np.float32, "fel")
+    pa = f.raster(ad8, np.float32, "ad8")
+    pdx, pdy = f.cells(dx, dy)
+    part = C.c_void_p()
+    st = f.call("tdx_streamnet_compact", pp, ps, pf, pa, f.nx, f.ny, int(row0), int(nodata), int(src_nodata), pdx, pdy, C.byref(part))
+    return part, st
+
+
+def _streamnet_label(f, p, src, part, links, first_cell, single_watershed, nodata, src_nodata):
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    ordg, po = f.out(None, np.int16, "ord")
+    w, pw = f.out(None, np.int32, "w")
+    st = f.call("tdx_streamnet_label", pp, ps, f.nx, f.ny, int(nodata), int(src_nodata), part, links, int(first_cell), int(bool(single_watershed)), po, pw)
+    return ordg, w, st
+
+
+class StreamNetLinks:
+    """The links of a raster from the parts of ALL its strips in strip order (StripPipeline.streamnet_compact): host code, no device.  tree / coord as
+    Context.streamnet returns them; first_cell[k] is what strip k hands to StripPipeline.streamnet_label.  Owns the parts: close() frees them too."""
+
+    def __init__(self, parts, nx, ny, dx, dy, geotransform=None, outlets=None):
+        self._lib = _lib.load()
+        self.parts = list(parts)
+        counts = [int(self._lib.tdx_streamnet_compact_count(p)) for p in self.parts]
+        self.first_cell = [int(v) for v in np.concatenate([[0], np.cumsum(counts)[:-1]])]
+        dxc, dyc = _f64(dx, ny), _f64(dy, ny)
+        dxa, dya = abs(float(dxc[ny // 2])), abs(float(dyc[ny // 2]))
+        gt = (0.0, dxa, 0.0, 0.0, 0.0, -dya) if geotransform is None else tuple(float(v) for v in geotransform)
+        g4 = np.array([gt[0], abs(gt[1]), gt[3], abs(gt[5])], np.float64)
+        if outlets is None:
+            ox = oy = ids = np.zeros(0, np.int32)
+        else:
+            ox, oy = _flat(outlets[0], np.int32), _flat(outlets[1], np.int32)
+            ids = _flat(outlets[2], np.int32) if len(outlets) > 2 else np.arange(1, ox.size + 1, dtype=np.int32)
+        arr = (C.c_void_p * len(self.parts))(*[p.value for p in self.parts])
+        self.handle = C.c_void_p()
+        check(self._lib.tdx_streamnet_links_build(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), dxa, dya, _v(g4), _v(ox) if ox.size else None,
+                                                  _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), C.byref(self.handle)))
+        self.tree, self.coord = _links_rows(self._lib, self.handle)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.tdx_streamnet_links_free(self.handle)
+            self.handle = None
+            for p in self.parts:
+                self._lib.tdx_streamnet_compact_free(p)
+            self.parts = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def streamnet_text(tree, coord):
+    """The bytes of the reference's -tree and -coord files (src/streamnet.cpp:1165, :1177) from Context.streamnet's rows."""
+    t = "".join("\t" + "\t".join(str(int(v)) for v in row) + "\n" for row in np.asarray(tree, np.int64).reshape(-1, 9))
+    c = "".join("\t%f\t%f\t%f\t%f\t%f\n" % tuple(float(v) for v in row) for row in np.asarray(coord, np.float64).reshape(-1, 5))
+    return t.encode(), c.encode()
+
+
+def streamnet(p, src, fel, ad8, outlets=None, single_watershed=False, device=0, **kw):
+    """Context(device).streamnet(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.streamnet(p, src, fel, ad8, outlets, single_watershed, **kw)
 
 
 def dropanalysis_table(thresh, n1, n2, s1, s1sq, s2, s2sq, length, total_area):

@@ -33,7 +33,10 @@
 //   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
 //   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
 //   tdx_tool_peukerdouglas       <- peukerdouglas()       src/PeukerDouglas.cpp:54-241
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <mutex>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -850,6 +853,118 @@ int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* d
     if (!ok) return t.rc;
     t.output(distfile, dist, p, (double)TDX_ANG_NODATA);   // MISSINGFLOAT (src/D8HDistToStrm.cpp:223-225)
     return t.finish("Processors", "d8hdisttostrm");
+}
+
+// StreamNet (src/streamnet.cpp:372-1508): reads src, p, ad8, fel in the reference's order with its own words for a raster that does not match (it
+// aborts with 4), then the outlets.  -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  The -net layer is not written: every
+// one of its fields is a host function of the tree and coord rows (reachshape, :244-365), and there is no OGR writer here to hold one against.
+int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfile, const char* ad8file, const char* elevfile, const char* treefile,
+                       const char* coordfile, const char* outletsds, const char* /*lyrname*/, int /*uselayername*/, int /*lyrno*/, const char* wfile,
+                       const char* streamnetsrc, const char* streamnetlyr, long useOutlets, long ordert, int verbose) {
+    if ((streamnetsrc && *streamnetsrc) || (streamnetlyr && *streamnetlyr)) {
+        fprintf(stderr, "taudem_amd: streamnet -net / -netlyr are not supported (the stream network layer is not written)\n");
+        g_tdx_thread_error = "streamnet: -net is not supported";
+        return TDX_ERR_ARG;
+    }
+    ToolRun t("StreamNet");
+    Raster src, p, ad8, fel;
+    Outlets o;
+    t.input(srcfile, I16, src);
+    if (t.rc == TDX_OK) {
+        const float timeestimate = float(1e-4 * double(src.info.nx) * double(src.info.ny) / 60 + 1);   // the reference's words and its estimate for one rank (:408-410)
+        fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+        fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+        fflush(stderr);
+    }
+    const struct { const char* path; tdx::DType type; Raster* r; const char* what; } more[3] = {
+        {pfile, I16, &p, "pfile"}, {ad8file, F32, &ad8, "ad8file"}, {elevfile, F32, &fel, "elevfile"}};
+    for (const auto& m : more) {
+        t.input(m.path, m.type, *m.r, Mismatch::Silent);
+        if (t.rc == TDX_ERR_MISMATCH) { printf("%s and src files not the same size. Exiting \n", m.what); fflush(stdout); return 4; }
+    }
+    if (useOutlets == 1) {
+        t.outlets(outletsds, 1, o);
+        if (t.rc == TDX_ERR_OUTLETS) { printf("Read outlets error. Exiting \n"); fflush(stdout); return t.rc; }
+    }
+    if (!t.read_done()) return t.rc;
+    const int64_t nx = src.info.nx, ny = src.info.ny, nout = useOutlets == 1 ? o.n() : 0;
+    if (verbose) {
+        printf("Files read\nProcess: 0, TotalX: %ld, TotalY: %ld\nProcess: 0, nx: %d, ny: %d\nProcess: 0, xstart: 0, ystart: 0\nProcess: 0, numOutlets: %d\n", long(nx), long(ny),
+               int(nx), int(ny), int(nout));
+        fflush(stdout);
+    }
+    fprintf(stderr, "Evaluating distances to outlet\nCreating links\n");   // (one call makes both: the reference's progress lines, ahead of it)
+    fflush(stderr);
+    std::vector<int32_t> src32(src.s.begin(), src.s.end()), w(t.cells());
+    std::vector<int16_t> ord(t.cells());
+    const double gt[4] = {src.info.xleftedge, src.info.dlon, src.info.ytopedge, src.info.dlat};
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t src_nd = (int32_t)(int16_t)src.info.nodata;
+    const int sw = ordert == 0;
+    tdx_streamnet_links* links = nullptr;
+    // --gpus N: every rank compacts its strip, the ranks meet, rank 0 builds the links of the whole raster on the host, they meet again, every rank labels
+    // its strip.  A rank that fails still comes to both meetings, so that nobody waits there for it.
+    const int nranks = int(std::min<int64_t>(tool_gpus(), ny));
+    std::vector<tdx_streamnet_compact*> parts(size_t(std::max(nranks, 1)), nullptr);
+    struct Meet {
+        std::mutex m; std::condition_variable cv; int n = 1, here = 0, round = 0;
+        void wait() {
+            std::unique_lock<std::mutex> lk(m);
+            const int r = round;
+            if (++here == n) { here = 0; round++; cv.notify_all(); } else cv.wait(lk, [&] { return round != r; });
+        }
+    } meet;
+    meet.n = std::max(nranks, 1);
+    std::atomic<int> failed{0};
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_streamnet(c, p.s.data(), src32.data(), fel.f.data(), ad8.f.data(), nx, ny, p_nd, src_nd, src.info.dxc.data(), src.info.dyc.data(), src.info.dxA(),
+                                 src.info.dyA(), gt, nout ? o.xs() : nullptr, nout ? o.ys() : nullptr, nout ? o.ids.data() : nullptr, nout, sw, ord.data(), w.data(), &links, s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_s = j.in(src32);
+            float *d_f = j.in(fel.f), *d_a = j.in(ad8.f);
+            int16_t* d_o = j.out(ord);
+            int32_t* d_w = j.out(w);
+            int e = j.error;
+            if (e == TDX_OK) e = tdx_streamnet_compact_strip(j.ctx, j.comm, d_p, d_s, d_f, d_a, j.nx, j.nyl, j.y0, p_nd, src_nd, j.dxs.data(), j.dys.data(), &parts[size_t(j.rank)], s);
+            if (e != TDX_OK) failed = e;
+            meet.wait();
+            if (failed == 0 && j.rank == 0) {
+                const int eb = tdx_streamnet_links_build(parts.data(), j.size, nx, ny, src.info.dxA(), src.info.dyA(), gt, nout ? o.xs() : nullptr, nout ? o.ys() : nullptr,
+                                                         nout ? o.ids.data() : nullptr, nout, &links);
+                if (eb != TDX_OK) failed = eb;
+            }
+            meet.wait();
+            if (failed != 0) return e != TDX_OK ? e : int(failed);
+            int64_t first_cell = 0;
+            for (int k = 0; k < j.rank; k++) first_cell += tdx_streamnet_compact_count(parts[size_t(k)]);
+            return tdx_streamnet_label_strip(j.ctx, j.comm, d_p, d_s, j.nx, j.nyl, p_nd, src_nd, parts[size_t(j.rank)], links, first_cell, sw, d_o, d_w, s);
+        });
+    for (tdx_streamnet_compact* part : parts) tdx_streamnet_compact_free(part);
+    if (!ok) { tdx_streamnet_links_free(links); return t.rc; }
+    double phase[TDX_STREAMNET_PHASES];
+    tdx_streamnet_links_copy(links, nullptr, nullptr, phase);
+    int wrc = tdx_streamnet_write_text(links, treefile, nullptr);
+    const char* failed_file = treefile;
+    if (wrc == TDX_OK) { wrc = tdx_streamnet_write_text(links, nullptr, coordfile); failed_file = coordfile; }
+    tdx_streamnet_links_free(links);
+    if (wrc != TDX_OK) { printf("Error opening file %s.\n", failed_file); fflush(stdout); return wrc; }
+    const double linkwt = now_s();
+    fprintf(stderr, "\n Calculating watersheds\n");
+    fflush(stderr);
+    t.output(wfile, w, ad8, -2147483647.0);    // MISSINGLONG, written like ad8 (:1450-1453)
+    t.output(ordfile, ord, ad8, -32768.0);     // MISSINGSHORT (:1473)
+    if (t.rc != TDX_OK) return t.rc;
+    const double writet = now_s();
+    const double lengthc = (phase[TDX_STREAMNET_SETUP] + phase[TDX_STREAMNET_LENGTH]) / 1000.0,
+                 linkc = (phase[TDX_STREAMNET_COMPACT] + phase[TDX_STREAMNET_LINKS]) / 1000.0,
+                 wshed = (phase[TDX_STREAMNET_SCATTER] + phase[TDX_STREAMNET_LABEL]) / 1000.0;
+    printf("Processors: %d\nRead time: %f\nLength compute time: %f\nLink compute time: %f\nLink write time: %f\nWatershed compute time: %f\nWrite time: %f\nTotal time: %f\n",
+           t.nproc, t.readt - t.begint, lengthc, linkc, linkwt - t.computet, wshed, writet - linkwt, writet - t.begint);
+    print_gpu_stats("streamnet", t.st, nx * ny);
+    return 0;
 }
 
 // -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  -upid is refused: the reference appends a line per visit of a

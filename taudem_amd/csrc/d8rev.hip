@@ -30,14 +30,6 @@ namespace {
 using namespace tdxk;
 using namespace d8rev;
 
-// the receiver of a cell in the lockstep form of the reverse sweep: the single dependency bit
-__device__ __forceinline__ void rev_row_d8(unsigned inf, int (&k)[2], bool (&on)[2], double (&p)[2]) {
-    const unsigned m = inf & 0xFFu;
-    k[0] = m ? __ffs(int(m)) : 1; k[1] = k[0];
-    on[0] = m != 0u; on[1] = false;
-    p[0] = 0.; p[1] = 0.;
-}
-
 struct D8DistAlg {   // src/D8HDistToStrm.cpp:166-180
     using Cell = float;
     using Aux = float;                              // the cell's own step: dist[j][p]; 0 on stream cells; nodata without a receiver
@@ -64,32 +56,6 @@ struct D8DistAlg {   // src/D8HDistToStrm.cpp:166-180
 #pragma unroll
         for (int kk = 1; kk <= 8; kk++) if (kk == k[0]) n[0] = nb[kk];
         S.v[cl] = eval2(S.aux[c], on, p, n);
-    }
-};
-
-struct GageAlg {   // src/gagewatershed.cpp:226-233; record = index of the labelling outlet
-    using Cell = int32_t;
-    using Aux = float;                              // (none)
-    static constexpr bool HAS_AUX = false, HAS_DIST = false, HAS_ROWS = false;
-    static constexpr int kBulkSweeps = 0;
-    static constexpr unsigned kBulkUntil = 64;
-    static constexpr int kMinWaves32 = 5;
-    static constexpr int kMaxRelease = 8;
-    static __device__ __forceinline__ float head(int32_t c) { return __int_as_float(c); }
-    static __host__ __device__ __forceinline__ int32_t outside() { return GW_NODATA; }
-    static __device__ __forceinline__ unsigned rel_mask(unsigned inf) { return (inf >> 16) & 0xFFu; }
-    static __device__ __forceinline__ void rev_row(unsigned inf, const Aux&, double, int (&k)[2], bool (&on)[2], double (&p)[2]) { rev_row_d8(inf, k, on, p); }
-    __device__ __forceinline__ Cell eval2(const Aux&, const bool (&on)[2], const double (&)[2], const Cell (&n)[2]) const { return on[0] ? n[0] : GW_NODATA; }
-    template <class L>
-    __device__ __forceinline__ void eval(L& S, int, int cl, int, unsigned inf, const Cell (&nb)[9]) const {
-        int k[2];
-        bool on[2];
-        double p[2];
-        rev_row_d8(inf, k, on, p);
-        Cell n[2] = {GW_NODATA, GW_NODATA};
-#pragma unroll
-        for (int kk = 1; kk <= 8; kk++) if (kk == k[0]) n[0] = nb[kk];
-        S.v[cl] = eval2(Aux{}, on, p, n);
     }
 };
 

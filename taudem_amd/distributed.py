@@ -305,6 +305,20 @@ class _StripDropAnalysisStage:
         return api._dropanalysis(self._call(), ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids)
 
 
+class _StripStreamNetStage:
+    """StripPipeline.streamnet_compact / streamnet_label (include/taudem_amd_streamnet.h): the two strip halves of StreamNet.  Between them the parts
+    of all strips meet in taudem_amd.api.StreamNetLinks (strip order = row-major order), which builds the links once on the host."""
+
+    def streamnet_compact(self, p, src, fel, ad8, row0, dx=1.0, dy=1.0, nodata=int(P_NODATA), src_nodata=int(P_NODATA)):
+        """part = streamnet_compact(p, src, fel, ad8, row0) on this strip: fills the halo rows of p and src (keep them for streamnet_label), runs the
+        length sweep and returns the handle of the strip's stream cells.  row0: the global row of the strip's first owned row."""
+        return api._streamnet_compact(self._call(), p, src, fel, ad8, row0, dx, dy, nodata, src_nodata)
+
+    def streamnet_label(self, p, src, part, links, first_cell, single_watershed=False, nodata=int(P_NODATA), src_nodata=int(P_NODATA)):
+        """ord, w = streamnet_label(p, src, part, links.handle, links.first_cell[rank]) on this strip: the owned rows are those of Context.streamnet."""
+        return api._streamnet_label(self._call(), p, src, part, links, first_cell, single_watershed, nodata, src_nodata)
+
+
 class _StripPeukerDouglasStage:
     """StripPipeline.peukerdouglas (include/taudem_amd_peuker.h)."""
 
@@ -314,7 +328,7 @@ class _StripPeukerDouglasStage:
         return api._peukerdouglas(self._call(), fel, nodata, weights, float_weights, out)
 
 
-class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage):
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

@@ -169,6 +169,16 @@ def peukerdouglas(felfile, ssfile, p=(0.4, 0.1, 0.05)):
     return _lib.load().tdx_tool_peukerdouglas(_b(felfile), _b(ssfile), ctypes.cast(w, ctypes.c_void_p))
 
 
+def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, outletsds="", lyrname="", uselayername=0, lyrno=0, wfile="", streamnetsrc="",
+             streamnetlyr="", useOutlets=0, ordert=1, verbose=False):
+    """src/streamnet.cpp:372 (StreamNet); ordert = 0 is -sw.  The stream network layer is not written: a non-empty streamnetsrc / streamnetlyr is refused."""
+    return _lib.load().tdx_tool_streamnet(_b(pfile), _b(srcfile), _b(ordfile), _b(ad8file), _b(elevfile), _b(treefile), _b(coordfile), _b(outletsds), _b(lyrname),
+                                          int(uselayername), int(lyrno), _b(wfile), _b(streamnetsrc), _b(streamnetlyr), int(useOutlets), int(ordert), int(bool(verbose)))
+
+
+streamnet = netsetup
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
