@@ -490,7 +490,7 @@ __device__ __forceinline__ unsigned pending_bits(const Nbr8& nb) {
 }
 
 struct AreaEval {   // src/areadinf.cpp:187-217
-    // the same expression contributor by contributor (the walks fold the contributors that exist, in k order: eval_walk in dinf_sweep_tile.inc)
+    // the same expression contributor by contributor (the walks fold the contributors that exist, in k order: eval_cell in dinf_sweep.hpp)
     __device__ __forceinline__ float begin(float, double, bool) const { return 0.f; }
     __device__ __forceinline__ void fold(float& areares, bool& con, float v, double p, float) const {
         if (is_nodata_f(v, TDX_AREA_NODATA)) con = true;
@@ -585,50 +585,21 @@ __global__ __launch_bounds__(256) void verify_kernel(Eval ev, const float* __res
     }
 }
 
-// activation flags between the two tile geometries (a 64 x 64 tile = 2 x 2 tiles of 32 x 32, sh = 1, or 4 x 4 tiles of 16 x 16, sh = 2)
-static __global__ __launch_bounds__(256) void flags_down_kernel(const uint32_t* __restrict__ f64, int tiles_x64, uint32_t* __restrict__ f32, int tiles_x32,
-                                                                int tiles_y32, int sh) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= tiles_x32 * tiles_y32) return;
-    const int tx = t % tiles_x32, ty = t / tiles_x32;
-    f32[t] = f64[(ty >> sh) * tiles_x64 + (tx >> sh)] ? tilek::FLAG_FULL : 0u;
-}
-static __global__ __launch_bounds__(256) void flags_up_kernel(uint32_t* __restrict__ f32, int tiles_x32, int tiles_y32, uint32_t* __restrict__ f64, int tiles_x64, int sh) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= tiles_x32 * tiles_y32) return;
-    if (f32[t]) {
-        f32[t] = 0u;
-        const int tx = t % tiles_x32, ty = t / tiles_x32;
-        f64[(ty >> sh) * tiles_x64 + (tx >> sh)] = tilek::FLAG_HALO;   // walks only: the bulk sweeps have run
+// The evaluation policy of an accumulation and which optional rasters it reads: fn(eval, has_w, has_dm, decay raster) with the two flags as
+// std::true_type / std::false_type - the choice the sweep kernels and their verifier share.
+template <class Alg, class F>
+void with_eval_of(const Alg& alg, F&& fn) {
+    if constexpr (std::is_same<Alg, AreaAlg>::value) {
+        if (alg.W) fn(AreaEval{}, std::true_type{}, std::false_type{}, static_cast<const float*>(nullptr));
+        else fn(AreaEval{}, std::false_type{}, std::false_type{}, static_cast<const float*>(nullptr));
+    } else {
+        if (alg.W) fn(DecayEval{alg.dm_nodata}, std::true_type{}, std::true_type{}, alg.DM);
+        else fn(DecayEval{alg.dm_nodata}, std::false_type{}, std::true_type{}, alg.DM);
     }
 }
 }  // namespace dsweep
 
-#define DSWEEP_NS dsweep64
-#define DSWEEP_TS 64
-#define DSWEEP_NT 1024
-#include "dinf_sweep_tile.inc"
-#undef DSWEEP_NS
-#undef DSWEEP_TS
-#undef DSWEEP_NT
-#define DSWEEP_NS dsweep32
-#define DSWEEP_TS 32
-#define DSWEEP_NT 256
-#include "dinf_sweep_tile.inc"
-#undef DSWEEP_NS
-#undef DSWEEP_TS
-#undef DSWEEP_NT
-// 16 x 16 tiles, ONE wave per tile (no workgroup barrier in the hop loop, 10 KB of LDS: fifteen tiles per CU) - the variant VERDICT r04 asked to be
-// measured for the bulk rounds (TDX_DINF_BULK_TILE=16; docs/experiments_r05.md has what it did)
-#define DSWEEP_NS dsweep16
-#define DSWEEP_TS 16
-#define DSWEEP_NT 64
-#include "dinf_sweep_tile.inc"
-#undef DSWEEP_NS
-#undef DSWEEP_TS
-#undef DSWEEP_NT
-
-
+#include "dinf_sweep.hpp"
 
 template <class Alg>
 int run_dinf_accum(tdx_context* ctx, Alg alg, const Strip& st, float* d_ang, float ang_nodata, const double* dxc, const double* dyc, int contcheck,
@@ -705,155 +676,68 @@ int run_dinf_accum(tdx_context* ctx, Alg alg, const Strip& st, float* d_ang, flo
     int64_t rounds = 0, outer = 0;
     if (!use_walk) {
         TdxSpan sp(ctx, TDX_K_ACCUM);
-        // two tile geometries over the same arrays (the state of the sweep is the result raster alone): 32 x 32 tiles for the bulk
-        // rounds, 64 x 64 tiles for the tail (dinf_sweep_tile.inc)
-        tilek::TileGeom geom = tilek::make_geom(inx, iny, st.y0, st.y1);
-        geom.max_sweeps = dsweep64::BULK_SWEEPS;
+        // the schedule over two tile geometries is sweepsched::run's (sweep_schedule.hpp); the tile routine is dinf_sweep.hpp's
         // edge of the bulk rounds' tiles: 16 x 16 one-wave tiles gain 5 % at 32768^2 and nothing at 16384^2 (docs/experiments_r05.md), so they take the large
         // rasters (>= 2^29 cells per strip) of AreaDinf; DinfDecayAccum stays on 32 x 32 (its decay rows in LDS); TDX_DINF_BULK_TILE=16|32 decides otherwise
         static const int bulk_env = getenv("TDX_DINF_BULK_TILE") ? atoi(getenv("TDX_DINF_BULK_TILE")) : 0;
         const int bulk_ts = bulk_env == 16 ? 16 : (bulk_env == 32 ? 32 : ((std::is_same<Alg, AreaAlg>::value && n >= (size_t(1) << 29)) ? 16 : 32));
-        const int bulk_sh = bulk_ts == 16 ? 2 : 1;
-        tilek::TileGeom geom32 = geom;
-        geom32.tiles_x = (inx + bulk_ts - 1) / bulk_ts; geom32.tiles_y = (iny + bulk_ts - 1) / bulk_ts;
-        // lockstep sweeps of a fresh tile before the walks take over (dinf_sweep_tile.inc)
-        static const int bulk_sweeps = getenv("TDX_DINF_BULK_SWEEPS") ? std::max(0, atoi(getenv("TDX_DINF_BULK_SWEEPS"))) : dsweep32::BULK_SWEEPS;
-        geom32.max_sweeps = bulk_sweeps;
-        const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y), ntiles32 = size_t(geom32.tiles_x) * size_t(geom32.tiles_y);
-        uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
-        uint32_t* flags32 = static_cast<uint32_t*>(ctx->scratch(TDX_S_G, ntiles32 * 4 * (1 + tilek::SCHED_LIST_WORDS)));
+        // lockstep sweeps of a fresh tile before the walks take over (dinf_sweep.hpp)
+        static const int bulk_sweeps = getenv("TDX_DINF_BULK_SWEEPS") ? std::max(0, atoi(getenv("TDX_DINF_BULK_SWEEPS"))) : dsweep::BULK_SWEEPS;
         unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
-        if (!flags || !flags32 || !counts) return TDX_ERR_NOMEM;
-        const tilek::Sched sched{flags, flags + ntiles, counts}, sched32{flags32, flags32 + ntiles32, counts};
+        if (!counts) return TDX_ERR_NOMEM;
         const float* d_w = alg.W;
-        static const bool dbg_rounds = getenv("TDX_DEBUG_ROUNDS") != nullptr;   // active tiles per round on stderr
-        static const bool dbg_cycles = dbg_rounds && atoi(getenv("TDX_DEBUG_ROUNDS")) == 1;
+        static const bool dbg_cycles = getenv("TDX_DEBUG_ROUNDS") != nullptr && atoi(getenv("TDX_DEBUG_ROUNDS")) == 1;
         // the bulk phase ends when a round has at most this many active 32 x 32 tiles (0: no bulk phase)
         static const unsigned long long bulk_until = getenv("TDX_DINF_BULK_UNTIL") ? strtoull(getenv("TDX_DINF_BULK_UNTIL"), nullptr, 10) : 400ull;
         unsigned long long* dbg = dbg_cycles ? reinterpret_cast<unsigned long long*>(ctx->d_mail) + TDX_MAIL_DBG_SWEEP : nullptr;
+        const sweepsched::Params P{bulk_ts, bulk_ts == 16 ? 48 : 16, bulk_until, bulk_sweeps, dsweep::BULK_SWEEPS, true, "bulk rounds", "tail rounds",
+                                   "\ndinf sweep rounds(%d tiles of %d):"};
+        // one round of the tile kernel of edge TSZ (edge: std::integral_constant<int, TSZ>)
+        auto launch_edge = [&](auto edge, const tilek::TileGeom& gg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur,
+                               uint32_t* fnext, uint32_t* lnext, unsigned pull_max) {
+            constexpr int TSZ = decltype(edge)::value;
+            dsweep::with_eval_of(alg, [&](auto ev, auto has_w, auto has_dm, const float* dm) {
+                hipLaunchKernelGGL((dsweep::sweep_kernel<decltype(ev), TSZ, decltype(has_w)::value, decltype(has_dm)::value>), dim3(grid), dim3(dsweep::Dim<TSZ>::NT), 0, ls, ev,
+                                   gg, list, count, fcur, fnext, lnext, pull_max, d_P, d_w, dm, info32, d_rows, d_out, out_nodata, contcheck, dbg);
+            });
+        };
         auto launch = [&](bool small, const tilek::TileGeom& gg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur,
                           uint32_t* fnext, uint32_t* lnext, unsigned pull_max) {
-#define TDX_DSWEEP_LAUNCH(NS)                                                                                                                                   \
-    if constexpr (std::is_same<Alg, AreaAlg>::value) {                                                                                                          \
-        if (d_w)                                                                                                                                                \
-            hipLaunchKernelGGL((NS::sweep_kernel<dsweep::AreaEval, true, false>), dim3(grid), dim3(NS::NT), 0, ls, dsweep::AreaEval{}, gg, list, count, fcur,  \
-                               fnext, lnext, pull_max, d_P, d_w, nullptr, info32, d_rows, d_out, out_nodata, contcheck, dbg);                                   \
-        else                                                                                                                                                    \
-            hipLaunchKernelGGL((NS::sweep_kernel<dsweep::AreaEval, false, false>), dim3(grid), dim3(NS::NT), 0, ls, dsweep::AreaEval{}, gg, list, count, fcur, \
-                               fnext, lnext, pull_max, d_P, nullptr, nullptr, info32, d_rows, d_out, out_nodata, contcheck, dbg);                               \
-    } else {                                                                                                                                                    \
-        if (d_w)                                                                                                                                                \
-            hipLaunchKernelGGL((NS::sweep_kernel<dsweep::DecayEval, true, true>), dim3(grid), dim3(NS::NT), 0, ls, dsweep::DecayEval{alg.dm_nodata}, gg, list, \
-                               count, fcur, fnext, lnext, pull_max, d_P, d_w, alg.DM, info32, d_rows, d_out, out_nodata, contcheck, dbg);                       \
-        else                                                                                                                                                    \
-            hipLaunchKernelGGL((NS::sweep_kernel<dsweep::DecayEval, false, true>), dim3(grid), dim3(NS::NT), 0, ls, dsweep::DecayEval{alg.dm_nodata}, gg, list, \
-                               count, fcur, fnext, lnext, pull_max, d_P, nullptr, alg.DM, info32, d_rows, d_out, out_nodata, contcheck, dbg);                   \
-    }
-            if (small && bulk_ts == 16) { TDX_DSWEEP_LAUNCH(dsweep16) } else if (small) { TDX_DSWEEP_LAUNCH(dsweep32) } else { TDX_DSWEEP_LAUNCH(dsweep64) }
-#undef TDX_DSWEEP_LAUNCH
-        };
-        int64_t launches = 0;
-        // runs one geometry until no tile is active, or (stop_at > 0) until a round has at most stop_at active tiles; returns whether
-        // tiles are still active (their flags of the next round are then in run.flags_of(run.parity))
-        // ... or (max_rounds > 0) until that many rounds have run: a multi-strip tail exchanges its boundary rows every few rounds instead of running
-        // every strip to its local fixed point first
-        auto run_rounds = [&](bool small, const tilek::TileGeom& gg, const tilek::Sched& sc, unsigned long long stop_at, bool* active_left, int* parity_out,
-                              int max_rounds = 0) -> int {
-            RoundRunner<flatk::LevelOp> run(ctx, s, flatk::LevelOp{nullptr, nullptr}, gg, sc, ctx->h_mail + TDX_MAIL_RUN_A, nullptr);
-            if (max_rounds > 0) { run.batch = max_rounds; run.batch_max = max_rounds; }
-            if (small) { run.grid_full = unsigned(std::min(run.ntiles, (bulk_ts == 16 ? 48 : 16) * ctx->num_cus)); run.grid_small = unsigned(std::min(run.ntiles, 4 * ctx->num_cus)); }
-            run.custom_launch = [&](const tilek::TileGeom& rg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur, uint32_t* fnext,
-                                    uint32_t* lnext, unsigned pull_max) { launch(small, rg, grid, ls, list, count, fcur, fnext, lnext, pull_max); };
-            run.print_counts = dbg_rounds;
-            if (dbg_rounds) fprintf(stderr, "\ndinf sweep rounds(%d tiles of %d):", run.ntiles, small ? bulk_ts : 64);
-            if (dbg) TDX_HIP_CHECK(ctx, hipMemset(dbg, 0, 80));
-            int last_printed = -1;
-            int rcl = run.start();
-            if (rcl != TDX_OK) return rcl;
-            *active_left = false;
-            while (!run.done) {
-                rcl = run.enqueue();
-                if (rcl != TDX_OK) return rcl;
-                TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-                run.collect();
-                if (dbg) {   // per batch of rounds: average phase times (us) and hops per activation
-                    TDX_HIP_CHECK(ctx, hipMemcpy(ctx->h_mail + TDX_MAIL_DBG_SWEEP, dbg, 80, hipMemcpyDeviceToHost));
-                    TDX_HIP_CHECK(ctx, hipMemset(dbg, 0, 80));
-                    const double na = double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 7] ? ctx->h_mail[TDX_MAIL_DBG_SWEEP + 7] : 1);
-                    fprintf(stderr, "\n  [rounds %d..%lld] activations %.0f: stage %.1f scan+bulk %.1f walks %.1f writeback %.1f us; hops/act %.1f, busiest lane %.1f, phases %.2f; of the records staged %.1f %% were pending, %.1f %% were evaluated\n",
-                            last_printed + 1, (long long)run.rounds - 1, na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 0] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 1] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 2] / na / 100.0,
-                            ctx->h_mail[TDX_MAIL_DBG_SWEEP + 3] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 4] / na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 5] / na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 6] / na,
-                            100.0 * double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 8]) / (na * double(small ? bulk_ts * bulk_ts : 4096)), 100.0 * double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 9]) / (na * double(small ? bulk_ts * bulk_ts : 4096)));
-                    last_printed = int(run.rounds) - 1;
-                }
-                if (!run.done && stop_at > 0 && run.last_count <= stop_at) { *active_left = true; *parity_out = run.parity; break; }
-                if (!run.done && max_rounds > 0 && run.rounds >= max_rounds) { *active_left = true; *parity_out = run.parity; break; }
+            switch (small ? bulk_ts : 64) {
+            case 16: launch_edge(std::integral_constant<int, 16>{}, gg, grid, ls, list, count, fcur, fnext, lnext, pull_max); break;
+            case 32: launch_edge(std::integral_constant<int, 32>{}, gg, grid, ls, list, count, fcur, fnext, lnext, pull_max); break;
+            default: launch_edge(std::integral_constant<int, 64>{}, gg, grid, ls, list, count, fcur, fnext, lnext, pull_max); break;
             }
-            rounds += run.rounds;
-            launches += run.launches;
+        };
+        auto exchange = [&](uint32_t* flags, int tiles_x, int64_t* changed, int left) { return strip_exchange<float>(ctx, st, d_out, out_nodata, flags, tiles_x, changed, true, left); };
+        // TDX_DEBUG_ROUNDS=1, per batch of rounds: average phase times (us) and hops per activation
+        int last_printed = -1;
+        sweepsched::BatchHook phase_clocks;
+        if (dbg) phase_clocks = [&](bool small, const RoundSchedule& run, bool begin) -> int {
+            if (begin) { TDX_HIP_CHECK(ctx, hipMemset(dbg, 0, 80)); last_printed = -1; return TDX_OK; }
+            TDX_HIP_CHECK(ctx, hipMemcpy(ctx->h_mail + TDX_MAIL_DBG_SWEEP, dbg, 80, hipMemcpyDeviceToHost));
+            TDX_HIP_CHECK(ctx, hipMemset(dbg, 0, 80));
+            const double na = double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 7] ? ctx->h_mail[TDX_MAIL_DBG_SWEEP + 7] : 1);
+            fprintf(stderr, "\n  [rounds %d..%lld] activations %.0f: stage %.1f scan+bulk %.1f walks %.1f writeback %.1f us; hops/act %.1f, busiest lane %.1f, phases %.2f; of the records staged %.1f %% were pending, %.1f %% were evaluated\n",
+                    last_printed + 1, (long long)run.rounds - 1, na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 0] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 1] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 2] / na / 100.0,
+                    ctx->h_mail[TDX_MAIL_DBG_SWEEP + 3] / na / 100.0, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 4] / na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 5] / na, ctx->h_mail[TDX_MAIL_DBG_SWEEP + 6] / na,
+                    100.0 * double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 8]) / (na * double(small ? bulk_ts * bulk_ts : 4096)), 100.0 * double(ctx->h_mail[TDX_MAIL_DBG_SWEEP + 9]) / (na * double(small ? bulk_ts * bulk_ts : 4096)));
+            last_printed = int(run.rounds) - 1;
             return TDX_OK;
         };
-        hipLaunchKernelGGL(tilek::fill_u32_kernel, dim3(tdx_blocks_for(ntiles, 256)), dim3(256), 0, s, flags, tilek::FLAG_FULL, ntiles);   // round 0: every tile
-        bool bulk = bulk_until > 0 && ntiles32 > bulk_until;
-        for (;;) {
-            bool left = false, bulk_just_ran = false;
-            int par = 0;
-            if (bulk) {
-                ctx->phase = "bulk rounds";
-                // bulk phase on 32 x 32 tiles: every 32-tile under an active 64-tile starts active
-                hipLaunchKernelGGL(dsweep::flags_down_kernel, dim3(tdx_blocks_for(ntiles32, 256)), dim3(256), 0, s, flags, geom.tiles_x, flags32, geom32.tiles_x,
-                                   geom32.tiles_y, bulk_sh);
-                TDX_HIP_CHECK(ctx, hipMemsetAsync(flags, 0, ntiles * 4, s));
-                rc = run_rounds(true, geom32, sched32, bulk_until, &left, &par);
-                if (rc != TDX_OK) return rc;
-                if (left) {   // what is still active goes on in 64 x 64 tiles
-                    uint32_t* f32next = par ? sched32.list + 2 * ntiles32 : sched32.flags;
-                    hipLaunchKernelGGL(dsweep::flags_up_kernel, dim3(tdx_blocks_for(ntiles32, 256)), dim3(256), 0, s, f32next, geom32.tiles_x, geom32.tiles_y, flags,
-                                       geom.tiles_x, bulk_sh);
-                }
-                bulk = false;   // (strip re-activations are few tiles: 64 x 64)
-                bulk_just_ran = true;
-            } else left = true;
-            // (with neighbours the bulk phase is followed by an exchange at once: the tail's first rounds then see what the neighbours' bulk phases finished,
-            // and the segment trace shows the two phases apart - the step time is the same either way: 311.4 against 311.2 ms projected at BASELINE.json configs[4])
-            if (left && !(bulk_just_ran && st.multi())) {
-                ctx->phase = "tail rounds";
-                // Multi-strip tail: at most `eager` rounds between two exchanges.  A strip that runs to its local fixed point first makes every flow path
-                // that crosses a strip boundary wait for the longest chain ANYWHERE in the strip it enters - at BASELINE.json configs[4] 47 crossings x
-                // ~10 ms (profiles/r05b_projection_decay.txt); with frequent exchanges the paths advance side by side, as on one GPU.
-                const int eager_env = getenv("TDX_SWEEP_EAGER_ROUNDS") ? std::max(0, atoi(getenv("TDX_SWEEP_EAGER_ROUNDS"))) : 8;   // (0: local fixed points)
-                const int eager = st.multi() ? eager_env : 0;
-                rc = run_rounds(false, geom, sched, 0, &left, &par, eager);
-                if (rc != TDX_OK) return rc;
-                if (left && par)   // stopped with tiles still active: the next schedule starts from the first flag half
-                    hipLaunchKernelGGL(tilek::flags_fold_kernel, dim3(tdx_blocks_for(ntiles, 256)), dim3(256), 0, s, sched.flags, sched.list + 2 * ntiles, int(ntiles));
-            }
-            if (!st.multi()) break;
-            // the neighbours' boundary rows: cells finished there release the owned cells they drain into (addBorders() + queue
-            // refill of src/areadinf.cpp:241-262); tiles that see a changed halo cell run again
-            int64_t changed = 0;
-            rc = strip_exchange<float>(ctx, st, d_out, out_nodata, flags, geom.tiles_x, &changed, true, left ? 1 : 0);
-            if (rc != TDX_OK) return rc;
-            if (changed == 0) break;
-            outer++;
-        }
+        int64_t launches = 0;
+        rc = sweepsched::run(ctx, st, P, counts, launch, exchange, &rounds, &launches, &outer, phase_clocks);
+        if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_ACCUM] += launches;
         if (d8sweep::verify_enabled()) {
             unsigned long long* d_ver = reinterpret_cast<unsigned long long*>(ctx->d_mail) + TDX_MAIL_VERIFY;
             const unsigned long long init[3] = {0ull, 0ull, ~0ull};
             TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_ver, init, sizeof init, hipMemcpyHostToDevice, s));
             TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));   // `init` is a local
-#define TDX_DSWEEP_VERIFY(EV, EVOBJ, HW, HD, DMP)                                                                                                             \
-    hipLaunchKernelGGL((dsweep::verify_kernel<EV, HW, HD>), grid2d, dim3(256), 0, s, EVOBJ, ang_use, ang_nodata, inx, iny, st.y0, st.y1, d_P, d_w, DMP, info32, \
-                       d_rows, d_out, out_nodata, contcheck, d_ver)
-            if constexpr (std::is_same<Alg, AreaAlg>::value) {
-                if (d_w) TDX_DSWEEP_VERIFY(dsweep::AreaEval, dsweep::AreaEval{}, true, false, nullptr);
-                else TDX_DSWEEP_VERIFY(dsweep::AreaEval, dsweep::AreaEval{}, false, false, nullptr);
-            } else {
-                if (d_w) TDX_DSWEEP_VERIFY(dsweep::DecayEval, dsweep::DecayEval{alg.dm_nodata}, true, true, alg.DM);
-                else TDX_DSWEEP_VERIFY(dsweep::DecayEval, dsweep::DecayEval{alg.dm_nodata}, false, true, alg.DM);
-            }
-#undef TDX_DSWEEP_VERIFY
+            dsweep::with_eval_of(alg, [&](auto ev, auto has_w, auto has_dm, const float* dm) {
+                hipLaunchKernelGGL((dsweep::verify_kernel<decltype(ev), decltype(has_w)::value, decltype(has_dm)::value>), grid2d, dim3(256), 0, s, ev, ang_use, ang_nodata, inx, iny,
+                                   st.y0, st.y1, d_P, d_w, dm, info32, d_rows, d_out, out_nodata, contcheck, d_ver);
+            });
             rc = d8sweep::verify_report(ctx, "D-infinity dependency sweep", d_ver, inx);
             if (rc != TDX_OK) return rc;
         }

@@ -23,8 +23,8 @@
 #pragma once
 #include "context.hpp"
 #include "device_common.hpp"
-#include "flats.hpp"
 #include "strips.hpp"
+#include "sweep_schedule.hpp"
 #include "tile_relax.hpp"
 
 #include <cstring>
@@ -503,7 +503,7 @@ __device__ __forceinline__ int sweep_tile(const Alg& alg, const tilek::TileGeom&
     }
     if (rim) atomicOr(&S.rim, rim);
     // "did anybody write" through LDS and a barrier that waits for LDS only: __syncthreads_or() sits out the acknowledgement of every global store above, and
-    // nobody in this launch depends on them having landed (see sweep_tile_rev and dinf_sweep_tile.inc); the workgroup stages its next tile meanwhile
+    // nobody in this launch depends on them having landed (see sweep_tile_rev and dinf_sweep.hpp); the workgroup stages its next tile meanwhile
     if (wrote) S.wrote = 1;
     tdx_barrier_lds();
     const int res = (S.wrote ? (tilek::RES_CHANGED | S.rim) : 0) | (S.over ? tilek::RES_CAPPED : 0);
@@ -760,24 +760,6 @@ template <> struct BitsOf<4> { using type = uint32_t; };
 template <> struct BitsOf<8> { using type = uint2; };
 template <> struct BitsOf<16> { using type = uint4; };
 
-// activation flags between the two tile geometries (a 64 x 64 tile = 2 x 2 tiles of 32 x 32)
-static __global__ __launch_bounds__(256) void flags_down_kernel(const uint32_t* __restrict__ f64, int tiles_x64, uint32_t* __restrict__ f32, int tiles_x32,
-                                                                int tiles_y32) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= tiles_x32 * tiles_y32) return;
-    const int tx = t % tiles_x32, ty = t / tiles_x32;
-    f32[t] = f64[(ty >> 1) * tiles_x64 + (tx >> 1)] ? tilek::FLAG_FULL : 0u;
-}
-static __global__ __launch_bounds__(256) void flags_up_kernel(uint32_t* __restrict__ f32, int tiles_x32, int tiles_y32, uint32_t* __restrict__ f64, int tiles_x64) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= tiles_x32 * tiles_y32) return;
-    if (f32[t]) {
-        f32[t] = 0u;
-        const int tx = t % tiles_x32, ty = t / tiles_x32;
-        f64[(ty >> 1) * tiles_x64 + (tx >> 1)] = tilek::FLAG_HALO;   // walks only: the bulk sweeps have run
-    }
-}
-
 // ---- verifier (TDX_SWEEP_VERIFY=1) ------------------------------------------------------------------------------------------
 // The sweeps rely on a record being read and written by ONE instruction, so that a tile staging its ring while the neighbouring tile
 // writes back in the same round sees the old or the new record, never a mixture.  That holds for aligned 4 / 8 / 16-byte accesses on
@@ -895,90 +877,27 @@ static int verify(tdx_context* ctx, const Strip& st, Alg alg, Arrays<Alg> A) {
 // active tiles, the rest on 64 x 64 tiles.  The work array must be initialised (pending pattern on participating owned cells) and
 // its halo rows exchanged; cells still pending on return (on or below a cycle, fed by the p == 0 quirk) are the caller's to finish.
 template <class Alg>
-static int run(tdx_context* ctx, const Strip& st, Alg alg, Arrays<Alg> A, uint32_t* /*flags_unused*/, unsigned long long* counts, int64_t* rounds_out,
-               int64_t* launches_out, int64_t* outer_out) {
+static int run(tdx_context* ctx, const Strip& st, Alg alg, Arrays<Alg> A, unsigned long long* counts, int64_t* rounds_out, int64_t* launches_out, int64_t* outer_out) {
     using Bits = typename BitsOf<sizeof(typename Alg::Cell)>::type;
-    hipStream_t s = ctx->stream;
-    tilek::TileGeom geom = tilek::make_geom(st.nx, st.ny_arr, st.y0, st.y1);
     static const int bulk_sweeps_env = getenv("TDX_D8_BULK_SWEEPS") ? std::max(0, atoi(getenv("TDX_D8_BULK_SWEEPS"))) : -1;
-    geom.max_sweeps = bulk_sweeps_env >= 0 ? bulk_sweeps_env : Alg::kBulkSweeps;
-    tilek::TileGeom geom32 = geom;
-    geom32.tiles_x = (st.nx + 31) / 32; geom32.tiles_y = (st.ny_arr + 31) / 32;
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y), ntiles32 = size_t(geom32.tiles_x) * size_t(geom32.tiles_y);
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
-    uint32_t* flags32 = static_cast<uint32_t*>(ctx->scratch(TDX_S_G, ntiles32 * 4 * (1 + tilek::SCHED_LIST_WORDS)));
-    if (!flags || !flags32) return TDX_ERR_NOMEM;
-    const tilek::Sched sched{flags, flags + ntiles, counts}, sched32{flags32, flags32 + ntiles32, counts};
+    const int bulk_sweeps = bulk_sweeps_env >= 0 ? bulk_sweeps_env : Alg::kBulkSweeps;
     // rounds run on 32 x 32 tiles while more than this many are active (policy constant; TDX_D8_BULK_UNTIL overrides it for every policy)
     static const unsigned long long bulk_until = getenv("TDX_D8_BULK_UNTIL") ? strtoull(getenv("TDX_D8_BULK_UNTIL"), nullptr, 10) : (unsigned long long)Alg::kBulkUntil;
-    // (max_rounds > 0: stop after that many rounds with the active tiles' flags left in the schedule's flag half `*parity_out` - the multi-strip tail)
-    auto run_rounds = [&](bool small, const tilek::TileGeom& gg, const tilek::Sched& sc, unsigned long long stop_at, bool* active_left, int* parity_out,
-                          int max_rounds = 0) -> int {
-        RoundRunner<flatk::LevelOp> runner(ctx, s, flatk::LevelOp{nullptr, nullptr}, gg, sc, ctx->h_mail + TDX_MAIL_RUN_A, nullptr);
-        if (max_rounds > 0) { runner.batch = max_rounds; runner.batch_max = max_rounds; }
-        if (small) { runner.grid_full = unsigned(std::min(runner.ntiles, 16 * ctx->num_cus)); runner.grid_small = unsigned(std::min(runner.ntiles, 4 * ctx->num_cus)); }
-        static const bool print_rounds = getenv("TDX_DEBUG_ROUNDS") != nullptr;   // active tiles per round on stderr
-        runner.print_counts = print_rounds;
-        if (print_rounds) fprintf(stderr, "\nd8 sweep rounds(%d tiles of %d):", runner.ntiles, small ? 32 : 64);
-        runner.custom_launch = [&](const tilek::TileGeom& rg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur, uint32_t* fnext,
-                                   uint32_t* lnext, unsigned pull_max) {
-            if (small) hipLaunchKernelGGL((sweep_kernel<Alg, 32, Alg::kMinWaves32>), dim3(grid), dim3(Dim<32>::NT), 0, ls, alg, rg, list, count, fcur, fnext, lnext, pull_max, A);
-            else hipLaunchKernelGGL((sweep_kernel<Alg, 64>), dim3(grid), dim3(Dim<64>::NT), 0, ls, alg, rg, list, count, fcur, fnext, lnext, pull_max, A);
-        };
-        int rcl = runner.start();
-        if (rcl != TDX_OK) return rcl;
-        *active_left = false;
-        while (!runner.done) {
-            rcl = runner.enqueue();
-            if (rcl != TDX_OK) return rcl;
-            TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));
-            runner.collect();
-            if (!runner.done && stop_at > 0 && runner.last_count <= stop_at) { *active_left = true; *parity_out = runner.parity; break; }
-            if (!runner.done && max_rounds > 0 && runner.rounds >= max_rounds) { *active_left = true; *parity_out = runner.parity; break; }
-        }
-        if (rounds_out) *rounds_out += runner.rounds;
-        if (launches_out) *launches_out += runner.launches;
-        return TDX_OK;
+    const sweepsched::Params P{32, 16, bulk_until, bulk_sweeps, bulk_sweeps, false, nullptr, nullptr, "\nd8 sweep rounds(%d tiles of %d):"};
+    auto launch = [&](bool small, const tilek::TileGeom& rg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur, uint32_t* fnext,
+                      uint32_t* lnext, unsigned pull_max) {
+        if (small) hipLaunchKernelGGL((sweep_kernel<Alg, 32, Alg::kMinWaves32>), dim3(grid), dim3(Dim<32>::NT), 0, ls, alg, rg, list, count, fcur, fnext, lnext, pull_max, A);
+        else hipLaunchKernelGGL((sweep_kernel<Alg, 64>), dim3(grid), dim3(Dim<64>::NT), 0, ls, alg, rg, list, count, fcur, fnext, lnext, pull_max, A);
     };
-    hipLaunchKernelGGL(tilek::fill_u32_kernel, dim3(tdx_blocks_for(ntiles, 256)), dim3(256), 0, s, flags, tilek::FLAG_FULL, ntiles);   // round 0: every tile
-    bool bulk = bulk_until > 0 && ntiles32 > bulk_until;
-    int rc;
-    for (;;) {
-        bool left = false;
-        int par = 0;
-        if (bulk) {
-            hipLaunchKernelGGL(flags_down_kernel, dim3(tdx_blocks_for(ntiles32, 256)), dim3(256), 0, s, flags, geom.tiles_x, flags32, geom32.tiles_x, geom32.tiles_y);
-            TDX_HIP_CHECK(ctx, hipMemsetAsync(flags, 0, ntiles * 4, s));
-            rc = run_rounds(true, geom32, sched32, bulk_until, &left, &par);
-            if (rc != TDX_OK) return rc;
-            if (left) {   // what is still active goes on in 64 x 64 tiles
-                uint32_t* f32next = par ? sched32.list + 2 * ntiles32 : sched32.flags;
-                hipLaunchKernelGGL(flags_up_kernel, dim3(tdx_blocks_for(ntiles32, 256)), dim3(256), 0, s, f32next, geom32.tiles_x, geom32.tiles_y, flags, geom.tiles_x);
-            }
-            bulk = false;   // (strip re-activations are few tiles: 64 x 64)
-        } else left = true;
-        if (left) {
-            // Multi-strip tail: at most `eager` rounds between two exchanges (areadinf.hip has the reasoning and the measurement): the flow paths that
-            // cross strip boundaries advance side by side instead of each waiting for the longest chain of the strip it enters.
-            const int eager_env = getenv("TDX_SWEEP_EAGER_ROUNDS") ? std::max(0, atoi(getenv("TDX_SWEEP_EAGER_ROUNDS"))) : 8;   // (0: local fixed points)
-            rc = run_rounds(false, geom, sched, 0, &left, &par, st.multi() ? eager_env : 0);
-            if (rc != TDX_OK) return rc;
-            if (left && par)   // stopped with tiles still active: the next schedule starts from the first flag half
-                hipLaunchKernelGGL(tilek::flags_fold_kernel, dim3(tdx_blocks_for(ntiles, 256)), dim3(256), 0, s, sched.flags, sched.list + 2 * ntiles, int(ntiles));
-        }
-        if (!st.multi()) break;
-        // the neighbours' boundary rows (as bit patterns: a pending record must compare equal to itself): cells finished there
-        // release the owned cells they drain into (addBorders() + queue refill of src/aread8.cpp:282-303); tiles that see a changed
-        // halo cell run again
-        int64_t changed = 0;
+    // the records travel as bit patterns: a pending record must compare equal to itself
+    auto exchange = [&](uint32_t* flags, int tiles_x, int64_t* changed, int left) {
         Bits outside_bits;
         const typename Alg::Cell oc = Alg::outside();
         memcpy(&outside_bits, &oc, sizeof(Bits));
-        rc = strip_exchange<Bits>(ctx, st, reinterpret_cast<Bits*>(A.v), outside_bits, flags, geom.tiles_x, &changed, true, left ? 1 : 0);
-        if (rc != TDX_OK) return rc;
-        if (changed == 0) break;
-        if (outer_out) (*outer_out)++;
-    }
+        return strip_exchange<Bits>(ctx, st, reinterpret_cast<Bits*>(A.v), outside_bits, flags, tiles_x, changed, true, left);
+    };
+    const int rc = sweepsched::run(ctx, st, P, counts, launch, exchange, rounds_out, launches_out, outer_out);
+    if (rc != TDX_OK) return rc;
 #ifdef TDX_REV_CLOCKS
     if constexpr (Alg::kMaxRelease <= 2) {
         unsigned long long h[40];

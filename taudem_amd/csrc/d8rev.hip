@@ -119,7 +119,7 @@ int d8dist_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodat
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<D8DistAlg> A{d_dist, step, nullptr, nullptr, R.info};
-        rc = d8sweep::run(ctx, st, D8DistAlg{}, A, R.flags, R.counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, D8DistAlg{}, A, R.counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(d8sweep::finish_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, d_dist, first, nown, TDX_ANG_NODATA);
         if (stats) stats->launches[TDX_K_ACCUM] += launches;
@@ -178,7 +178,7 @@ int gage_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata,
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<GageAlg> A{d_gw, nullptr, nullptr, nullptr, R.info};
-        rc = d8sweep::run(ctx, st, GageAlg{}, A, R.flags, R.counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, GageAlg{}, A, R.counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         const int row_lo = st.up ? 0 : st.y0, row_hi = st.down ? st.ny_arr : st.y1;   // a halo row counts where a neighbouring rank owns it
         if (nseed) {

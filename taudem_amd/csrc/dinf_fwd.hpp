@@ -112,7 +112,7 @@ int fwd_sweep(tdx_context* ctx, const Strip& st, Alg alg, FwdSetup& R, const typ
     int64_t launches = 0;
     TdxSpan sp(ctx, TDX_K_ACCUM);
     d8sweep::Arrays<Alg> A{R.rec, aux, dist, R.d_a2, R.info};
-    int rc = d8sweep::run(ctx, st, alg, A, R.flags, R.counts, rounds, &launches, outer);
+    int rc = d8sweep::run(ctx, st, alg, A, R.counts, rounds, &launches, outer);
     if (rc != TDX_OK) return rc;
     if (stats) stats->launches[TDX_K_ACCUM] += launches;
     return TDX_OK;

@@ -1,21 +1,28 @@
-// Tile-size dependent part of the D-infinity dependency sweep (areadinf.hip): included once per tile geometry with
-//   DSWEEP_NS   namespace of the instance      DSWEEP_TS   tile edge      DSWEEP_NT   threads per tile
+// The tile routine of the D-infinity dependency sweep (AreaDinf, DinfDecayAccum), a template over the tile edge TSZ = 64 | 32 | 16.
 // 32 x 32 tiles (28 KB of LDS: five tiles per CU) carry the BULK rounds, in which every tile of the raster is active and a
 // tile's time is its longest in-tile chain - what counts is how many tiles a CU works on at once; 64 x 64 tiles (113 KB, one per
 // CU) carry the TAIL, where a round is one tile crossing of the longest dependency chain and fewer crossings win.
-namespace DSWEEP_NS {
-using namespace dsweep;
-constexpr int TS = DSWEEP_TS, LH = TS + 2;
-constexpr int NT = DSWEEP_NT;         // threads per tile: lane (tid % TS, tid / TS) owns column lx and RPL consecutive rows
-constexpr int RPL = TS * TS / NT;   // cells per lane
-constexpr int NSTAGE = (LH * LH + NT - 1) / NT;
+// 16 x 16 tiles, ONE wave per tile (no workgroup barrier in the hop loop, 13 KB of LDS) - the variant VERDICT r04 asked to be
+// measured for the bulk rounds (TDX_DINF_BULK_TILE=16; docs/experiments_r05.md has what it did).
+// Part of areadinf.hip: included there once, after the helpers of its namespace that the routine uses (Nbr8, load_nbrs, pending, pending_bits,
+// QCAP, wall_clock64); the evaluation policies (AreaEval, DecayEval) are template arguments.
+#pragma once
+namespace dsweep {
+template <int TSZ>
+struct Dim {
+    static constexpr int TS = TSZ, LH = TSZ + 2;
+    static constexpr int NT = TSZ == 64 ? 1024 : (TSZ == 32 ? 256 : 64);   // threads per tile: lane (tid % TS, tid / TS) owns column lx and RPL consecutive rows
+    static constexpr int RPL = TS * TS / NT;   // cells per lane
+    static constexpr int NSTAGE = (LH * LH + NT - 1) / NT;
+    static constexpr int QLEN = TS == 16 ? 64 : (TS == 32 ? 128 : QCAP);   // hand-over queue (a fork whose two branches become ready at once; an overflow re-runs the tile)
+    template <bool HAS_DM>
+    static constexpr bool USE_CW = TS <= 32 || !HAS_DM;
+};
 constexpr int BULK_SWEEPS = 6;    // lockstep sweeps of a fresh tile (measured, AreaDinf at 32768^2 / 16384^2: 1: 220.8 / 78.2 ms, 3: 219.2 / 77.5, 6: 217.6 / 77.3, 8: 219.2 / 76.2, 12: 221.7 / 77.6, 16: 221.7 / 78.1; profiles/r06ah_*)
 
-template <bool HAS_DM>
-constexpr bool USE_CW = TS <= 32 || !HAS_DM;
-constexpr int QLEN = TS == 16 ? 64 : (TS == 32 ? 128 : QCAP);   // hand-over queue (a fork whose two branches become ready at once; an overflow re-runs the tile)
-template <bool HAS_W, bool HAS_DM>
+template <int TSZ, bool HAS_W, bool HAS_DM>
 struct Lds {
+    static constexpr int TS = Dim<TSZ>::TS, LH = Dim<TSZ>::LH, QLEN = Dim<TSZ>::QLEN;
     double2 p[LH * LH];            // outflow proportions of tile + ring
     float out[LH * LH];
     float dm[HAS_DM ? LH * LH : 1];
@@ -25,7 +32,7 @@ struct Lds {
     uint32_t tw[TS * TS];          // the cell's targets inside the tile, made once per activation: index t0 [0:12) t1 [12:24), "is in the tile" bits 24 / 25,
                                    // "exists, outside the tile" bits 26 / 27 (the walks read them with the info word: no direction arithmetic per hop)
     uint32_t spare[64];            // what a target that does not exist decrements (one word per lane: the walk has no branch around its two atomics)
-    uint32_t cw[USE_CW<HAS_DM> ? TS * TS : 1];   // the cell's first three contributors, made once per activation: per slot i, bits [9i, 9i + 8) the contributor's
+    uint32_t cw[Dim<TSZ>::template USE_CW<HAS_DM> ? TS * TS : 1];   // the cell's first three contributors, made once per activation: per slot i, bits [9i, 9i + 8) the contributor's
                                    // element offset from the cell (signed), bit 9i + 8 which of its two proportions; bit 27 = info bit 8 (a neighbour is
                                    // missing), bits [28:32) the number of contributors.  (Not where it would not fit: the 64 x 64 decay tile.)
     double dx[TS];                 // cell size of the tile's rows (the unweighted increment)
@@ -37,9 +44,10 @@ struct Lds {
     unsigned long long dbg[10];    // TDX_DEBUG_ROUNDS=1: this workgroup's phase clocks of the launch; [8] cells pending when staged, [9] cells evaluated
 };
 
-
 // targets of a finished cell that lie outside the tile: those tiles have to look again
+template <int TSZ>
 __device__ __forceinline__ int rim_bits(unsigned inf, int cx, int ly) {
+    constexpr int TS = Dim<TSZ>::TS;
     int bits = 0;
     const int s1 = int((inf >> 9) & 7u) + 1;
 #pragma unroll
@@ -60,13 +68,14 @@ __device__ __forceinline__ int rim_bits(unsigned inf, int cx, int ly) {
 // pending makes the function return false before anything is folded; the walkers only reach cells whose last contributor has just finished.
 // Same operations in the same order as Eval::eval (which the verifier of areadinf.hip keeps using: an independent second form).
 // TDX_DSWEEP_DENSE restores the old form everywhere (A/B).
-template <bool CHECK, class Eval, bool HAS_W, bool HAS_DM>
-__device__ __forceinline__ bool eval_cell(const Eval& ev, const Lds<HAS_W, HAS_DM>& S, int c, int cl, int ly, unsigned inf, int contcheck, float* result) {
+template <bool CHECK, class Eval, int TSZ, bool HAS_W, bool HAS_DM>
+__device__ __forceinline__ bool eval_cell(const Eval& ev, const Lds<TSZ, HAS_W, HAS_DM>& S, int c, int cl, int ly, unsigned inf, int contcheck, float* result) {
+    constexpr int LH = Dim<TSZ>::LH;
     const float wv = HAS_W ? S.w[c] : 0.f;
     const double dxv = S.dx[ly];
 #ifdef TDX_DSWEEP_DENSE
     Nbr8 nb;
-    load_nbrs<Lds<HAS_W, HAS_DM>, HAS_DM, LH>(S, cl, nb);
+    load_nbrs<Lds<TSZ, HAS_W, HAS_DM>, HAS_DM, LH>(S, cl, nb);
     if (CHECK && (inf & 0xFFu & pending_bits(nb)) != 0u) return false;
     *result = ev.eval(nb, wv, dxv, inf, contcheck, HAS_W);
     return true;
@@ -75,7 +84,7 @@ __device__ __forceinline__ bool eval_cell(const Eval& ev, const Lds<HAS_W, HAS_D
     int kk[3];
     float vv[3], dd[3];
     double pp[3];
-    if constexpr (USE_CW<HAS_DM>) {
+    if constexpr (Dim<TSZ>::template USE_CW<HAS_DM>) {
         const unsigned cw = S.cw[c];
         const int ncon = int(cw >> 28);
 #pragma unroll
@@ -124,11 +133,12 @@ __device__ __forceinline__ bool eval_cell(const Eval& ev, const Lds<HAS_W, HAS_D
 #endif
 }
 
-template <class Eval, bool HAS_W, bool HAS_DM>
-__device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom& g, int tile, bool full, Lds<HAS_W, HAS_DM>& S, const double2* __restrict__ P,
+template <class Eval, int TSZ, bool HAS_W, bool HAS_DM>
+__device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom& g, int tile, bool full, Lds<TSZ, HAS_W, HAS_DM>& S, const double2* __restrict__ P,
                                           const float* __restrict__ W, const float* __restrict__ DM, const uint32_t* __restrict__ INFO,
                                           const RowProp* __restrict__ rows, float* __restrict__ OUT, float out_nodata, int contcheck,
                                           unsigned long long* __restrict__ dbg) {
+    constexpr int TS = Dim<TSZ>::TS, LH = Dim<TSZ>::LH, NT = Dim<TSZ>::NT, RPL = Dim<TSZ>::RPL, NSTAGE = Dim<TSZ>::NSTAGE, QLEN = Dim<TSZ>::QLEN;
     const int tid = threadIdx.x, lx = tid % TS, ry0 = (tid / TS) * RPL;
     const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
     const int x0 = tx * TS, y0 = ty * TS;
@@ -192,7 +202,7 @@ __device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom&
                 else tw |= (unsigned(ny2 * TS + nx2) << (12 * t)) | (1u << (24 + t));
             }
             S.tw[(ry0 + r) * TS + lx] = tw;
-            if constexpr (USE_CW<HAS_DM>) {
+            if constexpr (Dim<TSZ>::template USE_CW<HAS_DM>) {
                 unsigned cw = (unsigned(__popc(inf & 0xFFu)) << 28) | ((inf & 0x100u) << 19), mm = inf & 0xFFu;
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
@@ -228,9 +238,9 @@ __device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom&
                 const int ly = ry0 + r, c = ly * TS + lx, cl = (ly + 1) * LH + lx + 1;
                 const unsigned inf = S.info[c];
                 float val;
-                if (eval_cell<true, Eval, HAS_W, HAS_DM>(ev, S, c, cl, ly, inf, contcheck, &val)) {
+                if (eval_cell<true, Eval, TSZ, HAS_W, HAS_DM>(ev, S, c, cl, ly, inf, contcheck, &val)) {
                     S.out[cl] = val;
-                    rim |= rim_bits(inf, lx, ly);
+                    rim |= rim_bits<TSZ>(inf, lx, ly);
                     pendmask &= ~(1u << r);
                     prog = true;
                 }
@@ -267,10 +277,10 @@ __device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom&
         for (;;) {
             const int ly = c / TS, cx = c % TS, cl = (ly + 1) * LH + cx + 1;
             float val;
-            (void)eval_cell<false, Eval, HAS_W, HAS_DM>(ev, S, c, cl, ly, inf, contcheck, &val);
+            (void)eval_cell<false, Eval, TSZ, HAS_W, HAS_DM>(ev, S, c, cl, ly, inf, contcheck, &val);
             S.out[cl] = val;
             hops++;
-            if (tw >> 26) rim |= rim_bits(inf, cx, ly);   // a target in a neighbouring tile (cells on the tile's rim only)
+            if (tw >> 26) rim |= rim_bits<TSZ>(inf, cx, ly);   // a target in a neighbouring tile (cells on the tile's rim only)
             // the (at most two) targets in the tile: both decrements and the candidates' info / target words are in flight together, without a branch
             // (a target that does not exist decrements the lane's spare word and reads cell 0; `ok` keeps it out of what follows)
             const int t0 = int(tw & 0xFFFu), t1 = int((tw >> 12) & 0xFFFu);
@@ -340,21 +350,21 @@ __device__ __forceinline__ int sweep_tile(const Eval& ev, const tilek::TileGeom&
     return res;
 }
 
-template <class Eval, bool HAS_W, bool HAS_DM>
-__global__ __launch_bounds__(NT) void sweep_kernel(Eval ev, tilek::TileGeom g, const uint32_t* __restrict__ list, unsigned long long* __restrict__ count,
+template <class Eval, int TSZ, bool HAS_W, bool HAS_DM>
+__global__ __launch_bounds__(Dim<TSZ>::NT) void sweep_kernel(Eval ev, tilek::TileGeom g, const uint32_t* __restrict__ list, unsigned long long* __restrict__ count,
                                                    uint32_t* __restrict__ flags_cur, uint32_t* __restrict__ flags_next, uint32_t* __restrict__ list_next,
                                                    unsigned pull_max, const double2* __restrict__ P, const float* __restrict__ W, const float* __restrict__ DM,
                                                    const uint32_t* __restrict__ INFO, const RowProp* __restrict__ rows, float* __restrict__ OUT,
                                                    float out_nodata, int contcheck, unsigned long long* __restrict__ dbg) {
-    __shared__ Lds<HAS_W, HAS_DM> S;
+    __shared__ Lds<TSZ, HAS_W, HAS_DM> S;
     __shared__ tilek::TileLds L;
     if (dbg && threadIdx.x < 10) S.dbg[threadIdx.x] = 0ull;
     tilek::round_driver(list, count, flags_cur, flags_next, list_next, pull_max, g, L, [&](int tile, bool full) {
-        return sweep_tile<Eval, HAS_W, HAS_DM>(ev, g, tile, full, S, P, W, DM, INFO, rows, OUT, out_nodata, contcheck, dbg);
+        return sweep_tile<Eval, TSZ, HAS_W, HAS_DM>(ev, g, tile, full, S, P, W, DM, INFO, rows, OUT, out_nodata, contcheck, dbg);
     });
     if (dbg) {
         __syncthreads();
         if (threadIdx.x < 10 && S.dbg[threadIdx.x]) atomicAdd(dbg + threadIdx.x, S.dbg[threadIdx.x]);
     }
 }
-}  // namespace DSWEEP_NS
+}  // namespace dsweep

@@ -296,7 +296,7 @@ int dd_run(tdx_context* ctx, const Strip& st, const DdArgs& a, Alg alg, tdx_stat
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<Alg> A{rec, aux, nullptr, R.d_a2, R.info};
-        rc = d8sweep::run(ctx, st, alg, A, R.flags, R.counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, alg, A, R.counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         if constexpr (sizeof(Cell) == 8)
             hipLaunchKernelGGL(dd_unpack_p_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, reinterpret_cast<const float2*>(rec), first, nown, a.d_dd);

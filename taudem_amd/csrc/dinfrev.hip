@@ -139,7 +139,7 @@ int updep_impl(tdx_context* ctx, const Strip& st, float* d_ang, float ang_nodata
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<UpDepAlg> A{d_dep, R.aux, nullptr, R.d_a2, R.info};
-        rc = d8sweep::run(ctx, st, UpDepAlg{}, A, R.flags, R.counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, UpDepAlg{}, A, R.counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(d8sweep::finish_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, d_dep, first, nown, -1.0f);
         if (stats) stats->launches[TDX_K_ACCUM] += launches;
@@ -175,7 +175,7 @@ int revacc_impl(tdx_context* ctx, const Strip& st, float* d_ang, float ang_nodat
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<RevAccAlg> A{rec, R.aux, nullptr, R.d_a2, R.info};
-        rc = d8sweep::run(ctx, st, RevAccAlg{w_nodata}, A, R.flags, R.counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, RevAccAlg{w_nodata}, A, R.counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(rev_unpack2_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, rec, first, nown, d_racc, d_dmax);
         if (stats) stats->launches[TDX_K_ACCUM] += launches;

@@ -227,19 +227,16 @@ int dropan_impl(tdx_context* ctx, const Strip& st, const float* d_ad8, int16_t* 
     const dim3 grid2d((inx + 63) / 64, (iny + 3) / 4);
     const dim3 grid_stats((inx + 63) / 64, (st.y1 - st.y0 + 63) / 64);
     const unsigned nparts = grid_stats.x * grid_stats.y;
-    const tilek::TileGeom geom = tilek::make_geom(inx, iny, st.y0, st.y1);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
     const size_t nout = size_t(n_outlets > 0 ? n_outlets : 0);
 
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
     float2* rec = static_cast<float2*>(ctx->scratch(TDX_S_C, n * sizeof(float2)));
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
     DaPartial* partial = static_cast<DaPartial*>(ctx->scratch(TDX_S_D, size_t(nparts) * sizeof(DaPartial)));
     DaPartial* totals = static_cast<DaPartial*>(ctx->scratch(TDX_S_E, size_t(nthresh) * sizeof(DaPartial)));
     uint32_t* rowcnt = static_cast<uint32_t*>(ctx->scratch(TDX_S_F, size_t(nthresh) * 3 * size_t(iny) * 4));
     int32_t* d_out = static_cast<int32_t*>(ctx->scratch(TDX_S_R, (nout ? nout : 1) * 16));   // x, y, term, flag
-    if (!info || !rec || !flags || !counts || !partial || !totals || !rowcnt || !d_out) return TDX_ERR_NOMEM;
+    if (!info || !rec || !counts || !partial || !totals || !rowcnt || !d_out) return TDX_ERR_NOMEM;
 
     ctx->begin_call(stats);
     strip_mark(ctx, st, "dropanalysis");
@@ -296,7 +293,7 @@ int dropan_impl(tdx_context* ctx, const Strip& st, const float* d_ad8, int16_t* 
             TdxSpan sp(ctx, TDX_K_ACCUM);
             d8sweep::Arrays<DropAlg> A{rec, d_fel, nullptr, nullptr, info};
             int64_t o1 = 1;
-            rc = d8sweep::run(ctx, st, DropAlg{}, A, flags, counts, &rounds, &launches, &o1);
+            rc = d8sweep::run(ctx, st, DropAlg{}, A, counts, &rounds, &launches, &o1);
             if (rc != TDX_OK) return rc;
             outer += o1;
         }

@@ -59,11 +59,8 @@ int fdc_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     const size_t n = size_t(inx) * size_t(iny);
     const size_t first = size_t(st.y0) * size_t(inx), nown = size_t(st.y1 - st.y0) * size_t(inx);
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
-    const tilek::TileGeom geom = tilek::make_geom(inx, iny, st.y0, st.y1);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
-    if (!info || !flags || !counts) return TDX_ERR_NOMEM;
+    if (!info || !counts) return TDX_ERR_NOMEM;
     ctx->begin_call(stats);
     strip_mark(ctx, st, "flowdircond");
     int rc = strip_exchange<int16_t>(ctx, st, d_p, p_nodata);   // flowData->share()
@@ -80,7 +77,7 @@ int fdc_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<FlowDirCondAlg> A{d_out, d_z, nullptr, nullptr, info};
-        rc = d8sweep::run(ctx, st, FlowDirCondAlg{z_nodata}, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, FlowDirCondAlg{z_nodata}, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(fdc_finish_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, d_z, d_out, first, nown);   // never evaluated: the input value
         if (stats) stats->launches[TDX_K_ACCUM] += launches;

@@ -18,6 +18,7 @@
 #include "context.hpp"
 #include "d8_sweep.hpp"
 #include "device_common.hpp"
+#include "flats.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -307,7 +308,7 @@ int gridnet_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_noda
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<d8sweep::GridNetAlg> A{rec, nullptr, d_dist, nullptr, info};
-        rc = d8sweep::run(ctx, st, d8sweep::GridNetAlg{}, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, d8sweep::GridNetAlg{}, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_ACCUM] += launches;
     }

@@ -75,13 +75,10 @@ int sad_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     const int inx = st.nx, iny = st.ny_arr;
     const size_t n = size_t(inx) * size_t(iny);
     const size_t first = size_t(st.y0) * size_t(inx), nown = size_t(st.y1 - st.y0) * size_t(inx);
-    const tilek::TileGeom geom = tilek::make_geom(inx, iny, st.y0, st.y1);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
     float* pop = static_cast<float*>(ctx->scratch(TDX_S_B, n * 4));
     float2* rec[2] = {static_cast<float2*>(ctx->scratch(TDX_S_C, n * 8)), static_cast<float2*>(ctx->scratch(TDX_S_D, n * 8))};
     uint8_t* code = static_cast<uint8_t*>(ctx->scratch(TDX_S_E, n));
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
     // dist[j][k] = sqrt(d1^2 dxc^2 + d2^2 dyc^2) in double, stored as float (src/SlopeAveDown.cpp:119-128)
     static const int hd1[9] = {0, 1, 1, 0, -1, -1, -1, 0, 1}, hd2[9] = {0, 0, -1, -1, -1, 0, 1, 1, 1};
@@ -89,7 +86,7 @@ int sad_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
     for (int m = 0; m < iny; m++)
         for (int k = 1; k <= 8; k++) dist[size_t(m) * 9 + size_t(k)] = (float)sqrt(hd1[k] * hd1[k] * dxc[m] * dxc[m] + hd2[k] * hd2[k] * dyc[m] * dyc[m]);
     float* d_dist = static_cast<float*>(ctx->scratch(TDX_S_F, dist.size() * sizeof(float)));
-    if (!info || !pop || !rec[0] || !rec[1] || !code || !flags || !counts || !d_dist) return TDX_ERR_NOMEM;
+    if (!info || !pop || !rec[0] || !rec[1] || !code || !counts || !d_dist) return TDX_ERR_NOMEM;
     TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_dist, dist.data(), dist.size() * sizeof(float), hipMemcpyHostToDevice, s));
     TDX_HIP_CHECK(ctx, hipStreamSynchronize(s));   // `dist` is a local
     ctx->begin_call(stats);
@@ -110,7 +107,7 @@ int sad_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int16_t p_nodata, 
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::SumMaxMin alg{0, TDX_AREA_NODATA, 0.f, 0, false};
         d8sweep::Arrays<d8sweep::SumMaxMin> A{pop, nullptr, nullptr, nullptr, info};
-        rc = d8sweep::run(ctx, st, alg, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, alg, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_ACCUM] += launches;
     }

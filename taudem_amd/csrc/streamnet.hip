@@ -265,18 +265,15 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
     hipStream_t s = ctx->stream;
     const Strip st = strip_single(nx, ny);
     const size_t n = size_t(nx) * size_t(ny);
-    const tilek::TileGeom geom = tilek::make_geom(nx, ny, 0, ny);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
     const unsigned nblocks = tdx_blocks_for(n, BLOCK_CELLS);
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
     double* step = static_cast<double*>(ctx->scratch(TDX_S_B, n * 8));
     float* len = static_cast<float*>(ctx->scratch(TDX_S_C, n * 4));
     int32_t* rank = static_cast<int32_t*>(ctx->scratch(TDX_S_D, n * 4));
     double* d_step9 = static_cast<double*>(ctx->scratch(TDX_S_F, size_t(ny) * 9 * 8));
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
     uint32_t* block_off = static_cast<uint32_t*>(ctx->scratch(TDX_S_I, size_t(nblocks) * 4 + 16));
-    if (!info || !step || !len || !rank || !d_step9 || !flags || !counts || !block_off) return TDX_ERR_NOMEM;
+    if (!info || !step || !len || !rank || !d_step9 || !counts || !block_off) return TDX_ERR_NOMEM;
     unsigned long long* d_total = reinterpret_cast<unsigned long long*>(block_off + ((size_t(nblocks) + 1) & ~size_t(1)));
     // the step of code k on row j in double: dxc, dyc, or the diagonal (src/streamnet.cpp:604-606)
     std::vector<double> step9(size_t(ny) * 9, 0.);
@@ -300,7 +297,7 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
     {   // ---- distance to the outlet along the stream
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<StreamLenAlg> A{len, step, nullptr, nullptr, info};
-        rc = d8sweep::run(ctx, st, StreamLenAlg{}, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, StreamLenAlg{}, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(d8sweep::finish_kernel, dim3(tdx_blocks_for(n, 256)), dim3(256), 0, s, len, size_t(0), n, TDX_ANG_NODATA);
         if (stats) stats->launches[TDX_K_ACCUM] += launches + 1;
@@ -385,7 +382,7 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<d8rev::GageAlg> A{d_w, nullptr, nullptr, nullptr, info};
         int64_t launches_label = 0;   // (the sweeps' counters are apart: rounds / cells_evaluated of the stats are the two sums)
-        rc = d8sweep::run(ctx, st, d8rev::GageAlg{}, A, flags, counts, &rounds_label, &launches_label, &outer_label);
+        rc = d8sweep::run(ctx, st, d8rev::GageAlg{}, A, counts, &rounds_label, &launches_label, &outer_label);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(label_finish_kernel, dim3(tdx_blocks_for(n, 256)), dim3(256), 0, s, d_p, d_src, n, p_nodata, src_nodata, sw, d_w);
         if (stats) stats->launches[TDX_K_ACCUM] += launches_label + 1;
@@ -410,18 +407,15 @@ int strip_compact_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int32_t*
     hipStream_t s = ctx->stream;
     const int nx = st.nx, ny = st.ny_arr;
     const size_t n = size_t(nx) * size_t(ny), first = size_t(st.y0) * size_t(nx), nown = size_t(st.y1 - st.y0) * size_t(nx);
-    const tilek::TileGeom geom = tilek::make_geom(nx, ny, st.y0, st.y1);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
     const unsigned nblocks = tdx_blocks_for(nown, BLOCK_CELLS);
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
     double* step = static_cast<double*>(ctx->scratch(TDX_S_B, n * 8));
     float* len = static_cast<float*>(ctx->scratch(TDX_S_C, n * 4));
     int32_t* rank = static_cast<int32_t*>(ctx->scratch(TDX_S_D, n * 4));
     double* d_step9 = static_cast<double*>(ctx->scratch(TDX_S_F, size_t(ny) * 9 * 8));
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
     uint32_t* block_off = static_cast<uint32_t*>(ctx->scratch(TDX_S_I, size_t(nblocks) * 4 + 16));
-    if (!info || !step || !len || !rank || !d_step9 || !flags || !counts || !block_off) return TDX_ERR_NOMEM;
+    if (!info || !step || !len || !rank || !d_step9 || !counts || !block_off) return TDX_ERR_NOMEM;
     unsigned long long* d_total = reinterpret_cast<unsigned long long*>(block_off + ((size_t(nblocks) + 1) & ~size_t(1)));
     std::vector<double> step9(size_t(ny) * 9, 0.);
     for (int j = 0; j < ny; j++)
@@ -447,7 +441,7 @@ int strip_compact_impl(tdx_context* ctx, const Strip& st, int16_t* d_p, int32_t*
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<StreamLenAlg> A{len, step, nullptr, nullptr, info};
-        rc = d8sweep::run(ctx, st, StreamLenAlg{}, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, StreamLenAlg{}, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(d8sweep::finish_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, len, first, nown, TDX_ANG_NODATA);
         if (stats) stats->launches[TDX_K_ACCUM] += launches + 1;
@@ -516,15 +510,12 @@ int strip_label_impl(tdx_context* ctx, const Strip& st, const int16_t* d_p, cons
     hipStream_t s = ctx->stream;
     const int nx = st.nx, ny = st.ny_arr;
     const size_t n = size_t(nx) * size_t(ny), first = size_t(st.y0) * size_t(nx), nown = size_t(st.y1 - st.y0) * size_t(nx);
-    const tilek::TileGeom geom = tilek::make_geom(nx, ny, st.y0, st.y1);
-    const size_t ntiles = size_t(geom.tiles_x) * size_t(geom.tiles_y);
     const unsigned nc = unsigned(part->cidx.size());
     const size_t ncp = (size_t(nc) + 3) & ~size_t(3);
     uint32_t* info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));
-    uint32_t* flags = static_cast<uint32_t*>(ctx->scratch(TDX_S_L, ntiles * 4 * (1 + tilek::SCHED_LIST_WORDS)));
     unsigned long long* counts = static_cast<unsigned long long*>(ctx->scratch(TDX_S_M, size_t(tilek::COUNT_RING) * 16));
     uint8_t* buf = static_cast<uint8_t*>(ctx->scratch(TDX_S_H, ncp * 10 + 64));
-    if (!info || !flags || !counts || !buf) return TDX_ERR_NOMEM;
+    if (!info || !counts || !buf) return TDX_ERR_NOMEM;
     uint32_t* cidx = reinterpret_cast<uint32_t*>(buf);
     int32_t* clabel = reinterpret_cast<int32_t*>(buf + ncp * 4);
     int16_t* corder = reinterpret_cast<int16_t*>(buf + ncp * 8);
@@ -549,7 +540,7 @@ int strip_label_impl(tdx_context* ctx, const Strip& st, const int16_t* d_p, cons
     {
         TdxSpan sp(ctx, TDX_K_ACCUM);
         d8sweep::Arrays<d8rev::GageAlg> A{d_w, nullptr, nullptr, nullptr, info};
-        rc = d8sweep::run(ctx, st, d8rev::GageAlg{}, A, flags, counts, &rounds, &launches, &outer);
+        rc = d8sweep::run(ctx, st, d8rev::GageAlg{}, A, counts, &rounds, &launches, &outer);
         if (rc != TDX_OK) return rc;
         hipLaunchKernelGGL(label_finish_kernel, dim3(tdx_blocks_for(nown, 256)), dim3(256), 0, s, d_p + first, d_src + first, nown, p_nodata, src_nodata, sw, d_w + first);
         if (stats) stats->launches[TDX_K_ACCUM] += launches + 1;

@@ -55,7 +55,7 @@ struct TileGeom {
     int y_own0, y_own1;     // rows [y_own0, y_own1) may be updated; others are read-only halo rows
     int max_sweeps;         // sweeps per activation before a tile yields (it re-activates itself)
     int chain_max;          // solo rounds: tile hand-overs inside one launch (0 = one tile per launch; TDX_SOLO_CHAIN)
-    // Where a round reports its size to the host (set per batch by RoundRunner::enqueue; null = nobody listens): the first workgroup of the round
+    // Where a round reports its size to the host (set per batch by RoundSchedule::enqueue; null = nobody listens): the first workgroup of the round
     // launched with the counter `count` stores count[0] to cnt_host[count - cnt_dev] - pinned host memory - so that the host needs no copy
     // kernel between two batches of rounds (61 of them per 16384^2 pipeline step, ~6 us each: profiles/r04m_timeline_*).
     // The report carries the batch's sequence number (cnt_tag, upper 32 bits; the count is below 2^32): a batch of empty rounds that is still in flight
@@ -888,7 +888,7 @@ __device__ __forceinline__ void flag_neighbours(int res, int tile, const TileGeo
 // (count[1] = the next round's size).  Flags raised in round r are only read in round r + 1, so everything a tile loads
 // was written before its launch started.
 // The work distribution of one round, shared by every tile kernel that uses this schedule (the relaxation below, the
-// dependency sweeps of tile_dep.hpp): body(tile, full) processes one tile with the whole workgroup and returns its RES_* mask
+// dependency sweeps of d8_sweep.hpp and dinf_sweep.hpp): body(tile, full) processes one tile with the whole workgroup and returns its RES_* mask
 // (uniform); all threads must call it, and it must end with a barrier.
 template <class Body>
 __device__ __forceinline__ void round_driver(const uint32_t* __restrict__ list, unsigned long long* __restrict__ count, uint32_t* __restrict__ flags_cur,
@@ -1370,16 +1370,22 @@ static int tile_relax_async_finish(tdx_context* ctx, hipStream_t s, Op op, tilek
     return TDX_OK;
 }
 
-// The round schedule of ONE relaxation as a resumable object: batches of rounds (one launch each) are enqueued on `s`;
+// The round schedule of ONE fixed point as a resumable object: batches of rounds (one launch each) are enqueued on `s`;
 // after the stream has been synchronised collect() reads the batch's per-round tile counts and notes the first empty
 // round.  Two runners on two streams interleave two independent relaxations (tile_relax_run_pair).
-template <class Op>
-struct RoundRunner {
-    tdx_context* ctx; hipStream_t s; Op op; tilek::TileGeom g; tilek::Sched sc; uint64_t* h; unsigned long long* dbg;
+// RoundSchedule is the bookkeeping alone - batches, count ring, host slots, every environment switch of the schedule - and
+// launches a round through `launch`: the dependency sweeps (sweep_schedule.hpp) install their own tile kernels there,
+// RoundRunner<Op> below the relaxation kernel of an operator.
+struct RoundSchedule {
+    // launches one round (rg: the schedule's geometry of THIS launch - the caller's geometry plus where the round reports its size; the tile kernel must be given rg)
+    using Launch = std::function<void(const tilek::TileGeom& rg, unsigned grid, hipStream_t st, const uint32_t* list, unsigned long long* count, uint32_t* flags_cur,
+                                      uint32_t* flags_next, uint32_t* list_next, unsigned pull_max)>;
+    tdx_context* ctx; hipStream_t s; tilek::TileGeom g; tilek::Sched sc; uint64_t* h;
+    Launch launch;
     int ntiles; unsigned cgrid, grid_full, grid_small;
     bool print_counts = false;
     int ring_len;                        // rounds that fit the count ring before it wraps (TDX_RELAX_RING: test hook)
-    bool lds_variant;                    // TDX_RELAX_LDS=1: the LDS-resident tile kernel instead of the register-resident one
+    bool lds_variant;                    // TDX_RELAX_LDS=1: the LDS-resident tile kernel instead of the register-resident one (RoundRunner's launch)
     unsigned pull_max;                   // list entries per cursor atomic in large rounds (TDX_RELAX_PULL: test hook)
     // Batches are enqueued and collected through a two-slot queue, so that the host can read the counts of batch k while batch
     // k + 1 is already running (drive() / tile_relax_run_pair): a host round trip between batches costs ~40 us of idle GPU, a
@@ -1394,12 +1400,8 @@ struct RoundRunner {
     int64_t rounds = 0, launches = 0;
     bool short_tail = getenv("TDX_RELAX_LONG_TAIL") == nullptr;   // (A/B hook)
     unsigned long long last_count = 0;   // active tiles of the last non-empty round seen
-    // another tile kernel on the same schedule (tile_dep.hpp): launches one round; empty = the relaxation kernel of `op`
-    // (rg: the runner's geometry of THIS launch - the caller's geometry plus where the round reports its size; the tile kernel must be given rg)
-    std::function<void(const tilek::TileGeom& rg, unsigned grid, hipStream_t st, const uint32_t* list, unsigned long long* count, uint32_t* flags_cur,
-                       uint32_t* flags_next, uint32_t* list_next, unsigned pull_max)> custom_launch;
-    RoundRunner(tdx_context* c, hipStream_t st, Op o, tilek::TileGeom geom, tilek::Sched sched, uint64_t* host_mail, unsigned long long* d)
-        : ctx(c), s(st), op(o), g(geom), sc(sched), h(host_mail), dbg(d) {
+    RoundSchedule(tdx_context* c, hipStream_t st, tilek::TileGeom geom, tilek::Sched sched, uint64_t* host_mail, Launch l = nullptr)
+        : ctx(c), s(st), g(geom), sc(sched), h(host_mail), launch(std::move(l)) {
         ntiles = g.tiles_x * g.tiles_y;
         cgrid = tdx_blocks_for(size_t(ntiles), 256);
         grid_full = unsigned(std::min(ntiles, 8 * ctx->num_cus));
@@ -1411,6 +1413,7 @@ struct RoundRunner {
         const char* pm = getenv("TDX_RELAX_PULL");
         pull_max = pm ? unsigned(std::max(1, std::min(atoi(pm), tilek::PULL_MAX))) : 16u;
     }
+    RoundSchedule(const RoundSchedule&) = delete;   // (a launch may capture its schedule)
     uint32_t* list_of(int p) const { return sc.list + size_t(p) * size_t(ntiles); }
     uint32_t* flags_of(int p) const { return p ? sc.list + 2 * size_t(ntiles) : sc.flags; }
     bool prestarted = false;             // round 0 (flags, second flag half, first list, count ring) was set up by the caller (tilek::pair_start_kernel)
@@ -1467,19 +1470,7 @@ struct RoundRunner {
         for (int b = 0; b < batch; b++) {
             const int p = (parity + b) & 1;
             const int sp = timed ? ctx->span_begin(TDX_K_TILEK) : -1;   // this kernel alone: what bench.py's roofline is computed from
-            if (custom_launch)
-                custom_launch(g, grid, s, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1), list_of(p ^ 1), pull_max);
-            else if (lds_variant)
-                hipLaunchKernelGGL((relax_kernel<Op, false>), dim3(grid), dim3(NTHR), 0, s, op, g, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1),
-                                   list_of(p ^ 1), pull_max, dbg, 0u);
-            else {
-                // with macro blocks (TileGeom::blk_k): four more workgroups per CU in the same launch serve the blocks of the round (1 / 2 / 4 / 8 / 16 per CU: 22.07 / 21.97 / 21.86 / 21.81 / 21.87 ms per 16384^2 step, profiles/r06g_macro_wgs.txt)
-                static const int macro_wgs = getenv("TDX_MACRO_WGS") ? std::max(1, atoi(getenv("TDX_MACRO_WGS"))) : 4;   // (A/B hook: block workgroups per CU)
-                // (at least MACRO_WGS_MIN of them, whatever the number of CUs: macro_role keeps at most PULL_MAX blocks per workgroup)
-                const unsigned gm = (has_macro<Op>::value && g.blk_k != nullptr) ? std::max(unsigned(macro_wgs * ctx->num_cus), MACRO_WGS_MIN) : 0u;
-                hipLaunchKernelGGL((relax_kernel<Op, true>), dim3(grid + gm), dim3(NTHR), 0, s, op, g, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1),
-                                   list_of(p ^ 1), pull_max, dbg, gm ? grid : 0u);
-            }
+            launch(g, grid, s, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1), list_of(p ^ 1), pull_max);
             ctx->span_end(sp);
             if (timed && ctx->cur_stats) ctx->cur_stats->launches[TDX_K_TILEK]++;
         }
@@ -1565,6 +1556,28 @@ struct RoundRunner {
     }
 };
 
+// The round schedule of the relaxation of `op`: a round is one launch of relax_kernel<Op>.
+template <class Op>
+struct RoundRunner : RoundSchedule {
+    Op op; unsigned long long* dbg;
+    RoundRunner(tdx_context* c, hipStream_t st, Op o, tilek::TileGeom geom, tilek::Sched sched, uint64_t* host_mail, unsigned long long* d)
+        : RoundSchedule(c, st, geom, sched, host_mail), op(o), dbg(d) {
+        launch = [this](const tilek::TileGeom& rg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur, uint32_t* fnext,
+                        uint32_t* lnext, unsigned pm) {
+            using namespace tilek;
+            if (lds_variant)
+                hipLaunchKernelGGL((relax_kernel<Op, false>), dim3(grid), dim3(NTHR), 0, ls, op, rg, list, count, fcur, fnext, lnext, pm, dbg, 0u);
+            else {
+                // with macro blocks (TileGeom::blk_k): four more workgroups per CU in the same launch serve the blocks of the round (1 / 2 / 4 / 8 / 16 per CU: 22.07 / 21.97 / 21.86 / 21.81 / 21.87 ms per 16384^2 step, profiles/r06g_macro_wgs.txt)
+                static const int macro_wgs = getenv("TDX_MACRO_WGS") ? std::max(1, atoi(getenv("TDX_MACRO_WGS"))) : 4;   // (A/B hook: block workgroups per CU)
+                // (at least MACRO_WGS_MIN of them, whatever the number of CUs: macro_role keeps at most PULL_MAX blocks per workgroup)
+                const unsigned gm = (has_macro<Op>::value && rg.blk_k != nullptr) ? std::max(unsigned(macro_wgs * ctx->num_cus), MACRO_WGS_MIN) : 0u;
+                hipLaunchKernelGGL((relax_kernel<Op, true>), dim3(grid + gm), dim3(NTHR), 0, ls, op, rg, list, count, fcur, fnext, lnext, pm, dbg, gm ? grid : 0u);
+            }
+        };
+    }
+};
+
 // One batch of FUSED rounds for two relaxations in lockstep (relax_pair_kernel): A's batch bookkeeping leads, B's follows.
 template <class Op>
 static int enqueue_fused(RoundRunner<Op>& A, RoundRunner<Op>& B) {
@@ -1611,7 +1624,7 @@ template <class Op>
 static int tile_relax_run_fused(tdx_context* ctx, Op opA, tilek::Sched scA, Op opB, tilek::Sched scB, tilek::TileGeom g, int64_t* rounds_out,
                                 int64_t* launches_out) {
     RoundRunner<Op> A(ctx, ctx->stream, opA, g, scA, ctx->h_mail + TDX_MAIL_RUN_A, nullptr), B(ctx, ctx->stream, opB, g, scB, ctx->h_mail + TDX_MAIL_RUN_B, nullptr);
-    A.batch_max = B.batch_max = RoundRunner<Op>::pipelined_batch_max();
+    A.batch_max = B.batch_max = RoundSchedule::pipelined_batch_max();
     int rc = A.start();
     if (rc != TDX_OK) return rc;
     rc = B.start();
@@ -1653,7 +1666,7 @@ static int tile_relax_run_pair(tdx_context* ctx, Op opA, tilek::Sched scA, Op op
     RoundRunner<Op> A(ctx, ctx->stream, opA, g, scA, ctx->h_mail + TDX_MAIL_RUN_A, nullptr), B(ctx, ctx->stream2, opB, gB ? *gB : g, scB, ctx->h_mail + TDX_MAIL_RUN_B, nullptr);
     B.ev_base = 2;
     A.prestarted = B.prestarted = flags0 != nullptr;
-    A.batch_max = B.batch_max = RoundRunner<Op>::pipelined_batch_max();
+    A.batch_max = B.batch_max = RoundSchedule::pipelined_batch_max();
     int rc = A.start();
     if (rc != TDX_OK) return rc;
     rc = B.start();
