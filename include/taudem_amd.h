@@ -659,6 +659,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* StreamNet (compute entry points, the link rows and file-level tool function): likewise */
 #include "taudem_amd_streamnet.h"
 
+/* MoveOutletsToStrm, ConnectDown and the point-layer writer (compute entry points and file-level tool functions): likewise */
+#include "taudem_amd_outlets.h"
+
 #ifdef __cplusplus
 }
 #endif

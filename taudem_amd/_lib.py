@@ -300,6 +300,37 @@ _STREAMNET_SIGNATURES = {
 STREAMNET_SYMBOLS = tuple(_STREAMNET_SIGNATURES)
 STREAMNET_PHASES = ("setup", "length", "compact", "links", "scatter", "label", "total")
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_outlets.h declares, the fifth extension header
+# MoveOutletsToStrm: ctx, p, src, nx, ny, p_nodata, src_nodata, maxdist, outlet_x, outlet_y, n_outlets, out_x, out_y, dist_moved, stats
+_MOVEOUTLETS_HEAD = [_P, _P, _P, _I64, _I64, _I16, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P]
+# ConnectDown: ctx, p, w, ad8, nx, ny, p_nodata, w_nodata, movedist, &points, stats
+_CONNECTDOWN_HEAD = [_P, _P, _P, _P, _I64, _I64, _I16, _I32, _I32, C.POINTER(_P), _P]
+_OUTLETS_SIGNATURES = {
+    "tdx_moveoutlets": (C.c_int, _MOVEOUTLETS_HEAD),
+    "tdx_moveoutlets_dev": (C.c_int, _MOVEOUTLETS_HEAD),
+    # ctx, comm, p, src, nx, ny_local, row0, ny_total, p_nodata, src_nodata, maxdist, state_x, state_y, state_dist, state_done, n_outlets, &n_moved, stats
+    "tdx_moveoutlets_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I16, _I32, _I32, _P, _P, _P, _P, _I64, C.POINTER(_I64), _P]),
+    "tdx_connectdown": (C.c_int, _CONNECTDOWN_HEAD),
+    "tdx_connectdown_dev": (C.c_int, _CONNECTDOWN_HEAD),
+    "tdx_connectdown_points_count": (_I64, [_P]),
+    # points, ids, x, y, ad8max, moved_x, moved_y, id_down, phase_ms
+    "tdx_connectdown_points_copy": (None, [_P] * 9),
+    "tdx_connectdown_points_free": (None, [_P]),
+    # ctx, comm, w, ad8, nx, ny_local, row0, w_nodata, &part, stats
+    "tdx_connectdown_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    "tdx_connectdown_merge": (C.c_int, [_P, _I64, C.POINTER(_P)]),
+    # ctx, comm, p, w, nx, ny_local, row0, ny_total, movedist, state_x, state_y, state_dist, state_done, id_down, n_points, &n_moved, stats
+    "tdx_connectdown_walk_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _P, _P, _I64, C.POINTER(_I64), _P]),
+    "tdx_connectdown_points_set_moved": (C.c_int, [_P, _P, _P, _P]),
+    # path, x, y, n, nfields, names, types, columns
+    "tdx_points_write": (C.c_int, [C.c_char_p, _P, _P, _I64, _I32, _P, _P, _P]),
+    "tdx_tool_moveoutletstostrm": (C.c_int, [C.c_char_p] * 4 + [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int]),
+    "tdx_tool_connectdown": (C.c_int, [C.c_char_p] * 7 + [C.c_int]),
+}
+OUTLETS_SYMBOLS = tuple(_OUTLETS_SIGNATURES)
+CONNECTDOWN_PHASES = ("maxid", "argmax", "decode", "walk")
+CONNECTDOWN_MAX_ID = 134217727   # TDX_CONNECTDOWN_MAX_ID
+
 _lib = None
 
 
@@ -323,7 +354,8 @@ def load():
     except Exception:  # pragma: no cover - torch-less hosts use the system ROCm runtime
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES}.items():
+    for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
+                                   **_OUTLETS_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

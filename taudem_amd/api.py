@@ -197,7 +197,30 @@ class _StreamNetStage:
         return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage):
+class _OutletToolsStage:
+    """Context.moveoutletstostrm and Context.connectdown; their entry points are those of include/taudem_amd_outlets.h.  Both return numpy arrays on
+    the host for either side."""
+
+    def moveoutletstostrm(self, p, src, outlets, maxdist=50, *, nodata=int(P_NODATA), src_nodata=int(P_NODATA), stats=False):
+        """columns, rows, dist_moved = moveoutletstostrm(p, src, outlets)  (src/MoveOutletsToStrm.cpp:80): every outlet walks down the D8 directions p
+        until it stands on a stream cell (src int32, not nodata and >= 1).
+
+        outlets: (columns, rows).  dist_moved int32: the steps walked, 0 for an outlet that was on the stream, -1 for one that could not be moved: off
+        the raster, a p outside 1..8 off the stream, a receiver off the raster, or maxdist steps without a stream cell.  columns / rows int32: the cell
+        reached (with -1: the cell where the outlet gave up; the tool writes its original coordinates then)."""
+        return _ret(_moveoutlets(_Call(self), p, src, outlets, maxdist, nodata, src_nodata), stats)
+
+    def connectdown(self, p, w, ad8, movedist=10, *, nodata=int(P_NODATA), w_nodata=-2147483647, phases=False, stats=False):
+        """ids, columns, rows, ad8max, moved_columns, moved_rows, id_down = connectdown(p, w, ad8)  (src/ConnectDown.cpp:79): for every watershed id of w
+        (int32, any value that is not nodata, 0 .. CONNECTDOWN_MAX_ID), in ascending order, the cell of greatest ad8 (float32; the first one in
+        row-major order among equals), and the cell movedist steps down p from it, with the w found there.
+
+        All int32 but ad8max (float32).  phases=True also returns, after id_down, the device milliseconds of the phases as a dict (maxid, argmax,
+        decode, walk)."""
+        return _ret(_connectdown(_Call(self), p, w, ad8, movedist, nodata, w_nodata, phases), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -794,6 +817,168 @@ class StreamNetLinks:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _point_lists(outlets):
+    ox, oy = _flat(outlets[0], np.int32).copy(), _flat(outlets[1], np.int32).copy()
+    if ox.shape != oy.shape:
+        raise ValueError("outlets: need two equal-length 1-D index arrays (columns, rows)")
+    return ox, oy
+
+
+def _moveoutlets(f, p, src, outlets, maxdist, nodata, src_nodata):
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    ox, oy = _point_lists(outlets)
+    rx, ry, rd = np.zeros_like(ox), np.zeros_like(ox), np.zeros_like(ox)
+    n = int(ox.size)
+    st = f.call("tdx_moveoutlets", pp, ps, f.nx, f.ny, int(nodata), int(src_nodata), int(maxdist), _v(ox) if n else None, _v(oy) if n else None, n,
+                _v(rx) if n else None, _v(ry) if n else None, _v(rd) if n else None)
+    return rx, ry, rd, st
+
+
+def _moveoutlets_strip(f, p, src, row0, ny_total, maxdist, state, nodata, src_nodata):
+    """state = (columns, global rows, dist, done): int32 arrays advanced in place; returns the number of outlets this strip advanced or finished."""
+    pp = f.raster(p, np.int16, "p")
+    ps = f.raster(src, np.int32, "src")
+    sx, sy, sd, sn = _walk_state(state)
+    moved = C.c_int64(0)
+    n = int(sx.size)
+    st = f.call("tdx_moveoutlets", pp, ps, f.nx, f.ny, int(row0), int(ny_total), int(nodata), int(src_nodata), int(maxdist), _v(sx) if n else None,
+                _v(sy) if n else None, _v(sd) if n else None, _v(sn) if n else None, n, C.byref(moved))
+    return int(moved.value), st
+
+
+def _walk_state(state):
+    for a in state:
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 or not a.flags.c_contiguous or a.shape != state[0].shape:
+            raise ValueError("state: need equal-length C-contiguous 1-D int32 numpy arrays")
+    return state
+
+
+def _points_rows(lib, points, phases=False):
+    """The seven arrays of a tdx_connectdown_points handle (and the phase dict)."""
+    n = int(lib.tdx_connectdown_points_count(points))
+    ids, x, y, mx, my, down = (np.zeros(n, np.int32) for _ in range(6))
+    amax, ms = np.zeros(n, np.float32), np.zeros(len(_lib.CONNECTDOWN_PHASES), np.float64)
+    lib.tdx_connectdown_points_copy(points, _v(ids), _v(x), _v(y), _v(amax), _v(mx), _v(my), _v(down), _v(ms))
+    res = (ids, x, y, amax, mx, my, down)
+    return res + (dict(zip(_lib.CONNECTDOWN_PHASES, ms.tolist())),) if phases else res
+
+
+def _connectdown(f, p, w, ad8, movedist, nodata, w_nodata, phases):
+    pp = f.raster(p, np.int16, "p")
+    pw = f.raster(w, np.int32, "w")
+    pa = f.raster(ad8, np.float32, "ad8")
+    points = C.c_void_p()
+    lib = f.ctx._lib
+    st = f.call("tdx_connectdown", pp, pw, pa, f.nx, f.ny, int(nodata), int(w_nodata), int(movedist), C.byref(points))
+    try:
+        res = _points_rows(lib, points, phases)
+    finally:
+        lib.tdx_connectdown_points_free(points)
+    return res + (st,)
+
+
+def _connectdown_strip(f, w, ad8, row0, w_nodata):
+    """A strip's part of the maxima (a handle: ConnectDownPoints takes the parts of all strips)."""
+    pw = f.raster(w, np.int32, "w")
+    pa = f.raster(ad8, np.float32, "ad8")
+    part = C.c_void_p()
+    st = f.call("tdx_connectdown", pw, pa, f.nx, f.ny, int(row0), int(w_nodata), C.byref(part))
+    return part, st
+
+
+def _connectdown_walk_strip(f, p, w, row0, ny_total, movedist, state):
+    """state = (columns, global rows, dist, done, id_down), advanced in place; returns the number of points this strip advanced or finished."""
+    pp = f.raster(p, np.int16, "p")
+    pw = f.raster(w, np.int32, "w")
+    sx, sy, sd, sn, si = _walk_state(state)
+    moved = C.c_int64(0)
+    n = int(sx.size)
+    st = f.call("tdx_connectdown_walk", pp, pw, f.nx, f.ny, int(row0), int(ny_total), int(movedist), _v(sx) if n else None, _v(sy) if n else None,
+                _v(sd) if n else None, _v(sn) if n else None, _v(si) if n else None, n, C.byref(moved))
+    return int(moved.value), st
+
+
+class ConnectDownPoints:
+    """The maxima of a raster from the parts of ALL its strips in strip order (StripPipeline.connectdown_argmax): host code, no device.  ids, columns,
+    rows (of the whole raster) and ad8max as Context.connectdown returns them; state() is what the strips' connectdown_walk is handed, and
+    moved(state) the three arrays that complete Context.connectdown's result.  Owns the parts: close() frees them."""
+
+    def __init__(self, parts):
+        self._lib = _lib.load()
+        self.parts = list(parts)
+        arr = (C.c_void_p * len(self.parts))(*[p.value for p in self.parts])
+        self.handle = C.c_void_p()
+        check(self._lib.tdx_connectdown_merge(C.cast(arr, C.c_void_p), len(self.parts), C.byref(self.handle)))
+        self.ids, self.columns, self.rows, self.ad8max = _points_rows(self._lib, self.handle)[:4]
+
+    def state(self):
+        n = self.ids.size
+        return self.columns.copy(), self.rows.copy(), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+
+    @staticmethod
+    def moved(state):
+        return state[0], state[1], state[4]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.tdx_connectdown_points_free(self.handle)
+            self.handle = None
+            for p in self.parts:
+                self._lib.tdx_connectdown_points_free(p)
+            self.parts = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def moveoutletstostrm(p, src, outlets, maxdist=50, device=0, **kw):
+    """Context(device).moveoutletstostrm(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.moveoutletstostrm(p, src, outlets, maxdist, **kw)
+
+
+def connectdown(p, w, ad8, movedist=10, device=0, **kw):
+    """Context(device).connectdown(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.connectdown(p, w, ad8, movedist, **kw)
+
+
+def write_points(path, x, y, fields=None):
+    """A point layer at `path`: an ESRI shapefile (.shp, with its .shx and .dbf) or GeoJSON (.json / .geojson) by the extension; any other raises.
+    fields: {name: values}, one value per point; integer arrays become Integer fields, floating ones Real, anything else String.  Host code: needs
+    no GPU.  No .prj is written."""
+    xs, ys = _flat(x, np.float64), _flat(y, np.float64)
+    if xs.shape != ys.shape:
+        raise ValueError("x and y: need equal-length arrays")
+    n, fields = int(xs.size), dict(fields or {})
+    names, types, cols, keep = [], [], [], []
+    for name, vals in fields.items():
+        a = np.asarray(vals)
+        if a.shape != (n,):
+            raise ValueError(f"field {name}: need one value per point")
+        if a.dtype.kind in "iub":
+            if a.size and (a.min() < -2**31 or a.max() > 2**31 - 1):
+                raise ValueError(f"field {name}: integers beyond 32 bits")
+            a, t = np.ascontiguousarray(a, np.int32), 0
+            ptr = a.ctypes.data
+        elif a.dtype.kind == "f":
+            a, t = np.ascontiguousarray(a, np.float64), 1
+            ptr = a.ctypes.data
+        else:
+            strs = [str(v).encode() for v in a.tolist()]
+            a, t = (C.c_char_p * max(n, 1))(*strs), 2
+            ptr = C.cast(a, C.c_void_p).value
+        names.append(str(name).encode()); types.append(t); cols.append(ptr); keep.append(a)
+    k = len(names)
+    c_names, c_types, c_cols = (C.c_char_p * max(k, 1))(*names), np.array(types + [0], np.int32), (C.c_void_p * max(k, 1))(*cols)
+    check(_lib.load().tdx_points_write(str(path).encode(), _v(xs) if n else None, _v(ys) if n else None, n, k, C.cast(c_names, C.c_void_p) if k else None,
+                                       _v(c_types) if k else None, C.cast(c_cols, C.c_void_p) if k else None))
 
 
 def streamnet_text(tree, coord):

@@ -33,6 +33,8 @@
 //   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
 //   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
 //   tdx_tool_peukerdouglas       <- peukerdouglas()       src/PeukerDouglas.cpp:54-241
+//   tdx_tool_moveoutletstostrm   <- outletstosrc()        src/MoveOutletsToStrm.cpp:80-914
+//   tdx_tool_connectdown         <- connectdown()         src/ConnectDown.cpp:79-893
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -53,6 +55,7 @@
 #include "hand_tables.hpp"
 #include "outlets.hpp"
 #include "tool_strips.hpp"
+#include "vector_layer.hpp"
 
 #define TDVERSION "5.4.0"   /* src/commonLib.h:63 */
 
@@ -1318,6 +1321,254 @@ int tdx_tool_peukerdouglas(const char* felfile, const char* ssfile, const float*
     if (!ok) return t.rc;
     t.output(ssfile, ss, fel, -2.0);
     return t.finish("Processors", "peukerdouglas");
+}
+
+}  // extern "C"
+
+// ---- the outlet tools: MoveOutletsToStrm and ConnectDown write point layers (vector_layer.hpp)
+namespace {
+
+// where the rank threads of --gpus N meet; a rank that failed still comes, so that nobody waits for it
+struct RankMeet {
+    std::mutex m; std::condition_variable cv; int n = 1, here = 0, round = 0;
+    void wait() {
+        std::unique_lock<std::mutex> lk(m);
+        const int r = round;
+        if (++here == n) { here = 0; round++; cv.notify_all(); } else cv.wait(lk, [&] { return round != r; });
+    }
+};
+
+// the state of the points that walk down p, handed from strip to strip: every rank advances a copy of its own, rank 0 takes every point from the
+// rank that owned its row before the round, until a round moves nothing
+struct WalkState {
+    std::vector<int32_t> x, y, dist, done, down;
+    explicit WalkState(size_t n = 0) : x(n), y(n), dist(n, 0), done(n, 0), down(n, 0) {}
+    size_t n() const { return x.size(); }
+};
+template <class Step>   // Step(RankJob&, WalkState& mine, int64_t* moved) -> int
+int walk_over_strips(RankJob& j, RankMeet& meet, std::atomic<int>& failed, WalkState& shared, std::vector<WalkState>& copies, std::vector<int64_t>& moved,
+                     std::atomic<int>& again, int first_error, Step step) {
+    int e = first_error;
+    const int64_t base = j.ny / j.size;
+    for (;;) {
+        WalkState& mine = copies[size_t(j.rank)];
+        mine = shared;
+        moved[size_t(j.rank)] = 0;
+        if (e == TDX_OK && failed == 0) e = step(j, mine, &moved[size_t(j.rank)]);
+        if (e != TDX_OK) failed = e;
+        meet.wait();
+        if (j.rank == 0) {
+            int64_t total = 0;
+            for (size_t i = 0; i < shared.n(); i++) {
+                if (shared.done[i]) continue;
+                const int64_t yy = shared.y[i];
+                const int k = (yy < 0 || yy >= j.ny) ? 0 : int(std::min<int64_t>(yy / base, j.size - 1));
+                const WalkState& c = copies[size_t(k)];
+                shared.x[i] = c.x[i]; shared.y[i] = c.y[i]; shared.dist[i] = c.dist[i]; shared.done[i] = c.done[i]; shared.down[i] = c.down[i];
+            }
+            for (int64_t mv : moved) total += mv;
+            again = (failed == 0 && total > 0) ? 1 : 0;
+        }
+        meet.wait();
+        if (!again) break;
+    }
+    return e != TDX_OK ? e : int(failed);
+}
+
+int refuse_layer(const char* tool, const char* path) {
+    fprintf(stderr, "taudem_amd: %s cannot write %s: %s\n", tool, path, tdx::kLayerKindsMessage);
+    g_tdx_thread_error = std::string(tool) + ": unsupported output " + path;
+    return TDX_ERR_ARG;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tdx_points_write(const char* path, const double* x, const double* y, int64_t n, int32_t nfields, const char* const* names, const int32_t* types,
+                     const void* const* columns) {
+    if (!path || n < 0 || nfields < 0 || (n > 0 && (!x || !y)) || (nfields > 0 && (!names || !types || !columns)))
+        return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_points_write: bad argument");
+    if (tdx::layer_kind(path) == tdx::LayerKind::None) return tdx_fail(nullptr, TDX_ERR_ARG, std::string("tdx_points_write: unsupported output ") + path + ": " + tdx::kLayerKindsMessage);
+    tdx::PointLayer L;
+    for (int32_t k = 0; k < nfields; k++) {
+        if (!names[k] || types[k] < 0 || types[k] > 2 || (n > 0 && !columns[k])) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_points_write: bad argument");
+        L.add_field(names[k], types[k] == 0 ? tdx::FieldType::Integer : types[k] == 1 ? tdx::FieldType::Real : tdx::FieldType::String);
+    }
+    L.resize(size_t(n));
+    for (int64_t i = 0; i < n; i++) {
+        L.x[size_t(i)] = x[i]; L.y[size_t(i)] = y[i];
+        for (int32_t k = 0; k < nfields; k++) {
+            if (types[k] == 0) L.set(size_t(i), size_t(k), (long long)static_cast<const int32_t*>(columns[k])[i]);
+            else if (types[k] == 1) L.set(size_t(i), size_t(k), static_cast<const double*>(columns[k])[i]);
+            else { const char* s = static_cast<const char* const*>(columns[k])[i]; L.set(size_t(i), size_t(k), std::string(s ? s : "")); }
+        }
+    }
+    std::string err;
+    if (!tdx::write_point_layer(path, L, err)) return tdx_fail(nullptr, TDX_ERR_FILE, err);
+    return TDX_OK;
+}
+
+// MoveOutletsToStrm (src/MoveOutletsToStrm.cpp:80-914): reads src, then p (its words and its abort code 4 where they do not match), then the outlets
+// with all their fields.  The layer arguments are accepted and ignored, as for the other outlet tools.
+int tdx_tool_moveoutletstostrm(const char* pfile, const char* srcfile, const char* outletsdatasrc, const char* /*outletslayer*/, int /*uselyrname*/, int /*lyrno*/,
+                               const char* outletmoveddatasrc, const char* /*outletmovedlayer*/, int maxdist) {
+    if (!pfile || !srcfile || !outletsdatasrc || !outletmoveddatasrc) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_moveoutletstostrm: bad argument");
+    if (tdx::layer_kind(outletmoveddatasrc) == tdx::LayerKind::None) return refuse_layer("moveoutletstostrm", outletmoveddatasrc);
+    ToolRun t("MoveOutletsToStreams");
+    Raster src, p;
+    t.input(srcfile, I16, src);
+    if (t.rc == TDX_OK) {   // :108-114
+        const float timeestimate = float((2e-7 * double(src.info.nx) * double(src.info.ny) / pow(double(tool_gpus()), 0.65)) / 60 + 1);
+        fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+        fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+        fflush(stderr);
+    }
+    t.input(pfile, I16, p, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("src and p files not the same size. Exiting \n"); fflush(stdout); return 4; }
+    if (t.rc != TDX_OK) return t.rc;
+    std::vector<double> ox, oy; std::vector<int> oid; std::string err;
+    tdx::PointLayer layer;
+    if (!tdx::read_outlets(outletsdatasrc, ox, oy, oid, err) || !tdx::read_point_fields(outletsdatasrc, ox.size(), layer, err)) {
+        printf("Error Opening datasource %s.\n", outletsdatasrc);   // :186-187, exit(1)
+        fflush(stdout);
+        g_tdx_thread_error = err;
+        return 1;
+    }
+    if (!t.read_done()) return t.rc;
+    const size_t n = ox.size();
+    if (n == 0) { printf("Unable to read any points from shapefile\n\n"); fflush(stdout); return 0; }   // :291-297; the reference runs on into empty arrays
+    const int64_t nx = src.info.nx, ny = src.info.ny;
+    WalkState st(n);
+    for (size_t i = 0; i < n; i++) {
+        int gx, gy;
+        tdx::geo_to_global_xy(ox[i], oy[i], p.info.xleftedge, p.info.ytopedge, p.info.dlon, p.info.dlat, gx, gy);
+        st.x[i] = gx; st.y[i] = gy;
+    }
+    std::vector<int32_t> src32(src.s.begin(), src.s.end()), rx(n), ry(n), rd(n);
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t src_nd = (int32_t)(int16_t)src.info.nodata;
+    const int nranks = int(std::max<int64_t>(1, std::min<int64_t>(tool_gpus(), ny)));
+    RankMeet meet; meet.n = nranks;
+    std::atomic<int> failed{0}, again{0};
+    std::vector<WalkState> copies(static_cast<size_t>(nranks));
+    std::vector<int64_t> moved(size_t(nranks), 0);
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_moveoutlets(c, p.s.data(), src32.data(), nx, ny, p_nd, src_nd, maxdist, st.x.data(), st.y.data(), int64_t(n), rx.data(), ry.data(), rd.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_s = j.in(src32);
+            const int e = walk_over_strips(j, meet, failed, st, copies, moved, again, j.error, [&](RankJob& jj, WalkState& mine, int64_t* mv) {
+                return tdx_moveoutlets_strip(jj.ctx, jj.comm, d_p, d_s, jj.nx, jj.nyl, jj.y0, jj.ny, p_nd, src_nd, maxdist, mine.x.data(), mine.y.data(), mine.dist.data(),
+                                             mine.done.data(), int64_t(mine.n()), mv, s);
+            });
+            if (j.rank == 0 && e == TDX_OK) { rx = st.x; ry = st.y; rd = st.dist; }
+            return e;
+        });
+    if (!ok) return t.rc;
+    layer.x.resize(n); layer.y.resize(n);
+    const size_t kd = layer.add_field("Dist_moved", tdx::FieldType::Integer, 6);   // :275-277
+    for (size_t i = 0; i < n; i++) {
+        if (rd[i] < 0) { layer.x[i] = ox[i]; layer.y[i] = oy[i]; }   // not moved: the original coordinates (:744-748)
+        else {                                                       // tiffIO::globalXYToGeo (src/tiffIO.cpp:593-597)
+            layer.x[i] = p.info.xleftedge + p.info.dlon / 2. + rx[i] * p.info.dlon;
+            layer.y[i] = p.info.ytopedge - p.info.dlat / 2. - ry[i] * p.info.dlat;
+        }
+        layer.set(i, kd, (long long)rd[i]);
+    }
+    if (!tdx::write_point_layer(outletmoveddatasrc, layer, err)) { printf(" warning: Failed to create feature in shapefile.\n"); fflush(stdout); g_tdx_thread_error = err; return TDX_ERR_FILE; }
+    printf("Total time: %f\n", now_s() - t.begint);
+    print_gpu_stats("moveoutletstostrm", t.st, nx * ny);
+    return 0;
+}
+
+// ConnectDown (src/ConnectDown.cpp:79-893): reads w, p, ad8 with its words and its abort code 4 for a raster that does not match w.  Both layers carry
+// the same id_down (w at the cell reached), the -o layer at the maxima and the -od layer at the cells reached (:732-751, :831-856).
+int tdx_tool_connectdown(const char* pfile, const char* wfile, const char* ad8file, const char* outletdatasrc, const char* /*outletlyr*/,
+                         const char* movedoutletdatasrc, const char* /*movedoutletlyr*/, int movedist) {
+    if (!pfile || !wfile || !ad8file || !outletdatasrc || !movedoutletdatasrc) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_connectdown: bad argument");
+    if (tdx::layer_kind(outletdatasrc) == tdx::LayerKind::None) return refuse_layer("connectdown", outletdatasrc);
+    if (tdx::layer_kind(movedoutletdatasrc) == tdx::LayerKind::None) return refuse_layer("connectdown", movedoutletdatasrc);
+    ToolRun t("ConnectDown");
+    Raster w, p, ad8;
+    t.input(wfile, I32, w);
+    t.input(pfile, I16, p, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("w and p files not the same size. Exiting \n"); fflush(stdout); return 4; }
+    t.input(ad8file, F32, ad8, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) { printf("ad8 and w files not the same size. Exiting \n"); fflush(stdout); return 4; }
+    if (!t.read_done()) return t.rc;
+    const int64_t nx = w.info.nx, ny = w.info.ny;
+    const int16_t p_nd = (int16_t)p.info.nodata;
+    const int32_t w_nd = (int32_t)w.info.nodata;
+    tdx_connectdown_points* points = nullptr;
+    const int nranks = int(std::max<int64_t>(1, std::min<int64_t>(tool_gpus(), ny)));
+    RankMeet meet; meet.n = nranks;
+    std::atomic<int> failed{0}, again{0};
+    std::vector<tdx_connectdown_points*> parts(size_t(nranks), nullptr);
+    std::vector<WalkState> copies(static_cast<size_t>(nranks));
+    std::vector<int64_t> moved(size_t(nranks), 0);
+    WalkState st;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_connectdown(c, p.s.data(), w.l.data(), ad8.f.data(), nx, ny, p_nd, w_nd, movedist, &points, s); },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            int32_t* d_w = j.in(w.l);
+            float* d_a = j.in(ad8.f);
+            int e = j.error;
+            if (e == TDX_OK) e = tdx_connectdown_strip(j.ctx, j.comm, d_w, d_a, j.nx, j.nyl, j.y0, w_nd, &parts[size_t(j.rank)], s);
+            if (e != TDX_OK) failed = e;
+            meet.wait();
+            if (failed == 0 && j.rank == 0) {
+                const int em = tdx_connectdown_merge(parts.data(), j.size, &points);
+                if (em != TDX_OK) failed = em;
+                else {
+                    const size_t np = size_t(tdx_connectdown_points_count(points));
+                    st = WalkState(np);
+                    tdx_connectdown_points_copy(points, nullptr, st.x.data(), st.y.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+                }
+            }
+            meet.wait();
+            e = walk_over_strips(j, meet, failed, st, copies, moved, again, e, [&](RankJob& jj, WalkState& mine, int64_t* mv) {
+                return tdx_connectdown_walk_strip(jj.ctx, jj.comm, d_p, d_w, jj.nx, jj.nyl, jj.y0, jj.ny, movedist, mine.x.data(), mine.y.data(), mine.dist.data(),
+                                                  mine.done.data(), mine.down.data(), int64_t(mine.n()), mv, s);
+            });
+            if (j.rank == 0 && e == TDX_OK) e = tdx_connectdown_points_set_moved(points, st.x.data(), st.y.data(), st.down.data());
+            return e;
+        });
+    for (tdx_connectdown_points* part : parts) tdx_connectdown_points_free(part);
+    if (!ok) { tdx_connectdown_points_free(points); return t.rc; }
+    const size_t np = size_t(tdx_connectdown_points_count(points));
+    if (np == 0) {   // :345-351: the reference says so and runs on after MPI_Finalize; nothing is written here
+        tdx_connectdown_points_free(points);
+        printf("No points found\n\n");
+        fflush(stdout);
+        return 0;
+    }
+    std::vector<int32_t> ids(np), x(np), y(np), mx(np), my(np), down(np);
+    std::vector<float> amax(np);
+    tdx_connectdown_points_copy(points, ids.data(), x.data(), y.data(), amax.data(), mx.data(), my.data(), down.data(), nullptr);
+    tdx_connectdown_points_free(points);
+    std::string err;
+    for (int moved_layer = 0; moved_layer < 2; moved_layer++) {
+        tdx::PointLayer layer;
+        const size_t ki = layer.add_field("id", tdx::FieldType::Integer), kd = layer.add_field("id_down", tdx::FieldType::Integer), ka = layer.add_field("ad8", tdx::FieldType::Real);
+        layer.resize(np);
+        for (size_t i = 0; i < np; i++) {   // wIO.globalXYToGeo for the maxima, p.globalXYToGeo for the cells reached: the same expression on rasters that match
+            const tdx::RasterInfo& ri = moved_layer ? p.info : w.info;
+            layer.x[i] = ri.xleftedge + ri.dlon / 2. + (moved_layer ? mx[i] : x[i]) * ri.dlon;
+            layer.y[i] = ri.ytopedge - ri.dlat / 2. - (moved_layer ? my[i] : y[i]) * ri.dlat;
+            layer.set(i, ki, (long long)ids[i]);
+            layer.set(i, kd, (long long)down[i]);
+            layer.set(i, ka, (double)amax[i]);
+        }
+        const char* path = moved_layer ? movedoutletdatasrc : outletdatasrc;
+        if (!tdx::write_point_layer(path, layer, err)) { printf(" warning: Failed to create feature in shapefile.\n"); fflush(stdout); g_tdx_thread_error = err; return TDX_ERR_FILE; }
+    }
+    printf("Total time: %f\n", now_s() - t.begint);
+    print_gpu_stats("connectdown", t.st, nx * ny);
+    return 0;
 }
 
 }  // extern "C"

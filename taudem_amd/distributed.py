@@ -319,6 +319,25 @@ class _StripStreamNetStage:
         return api._streamnet_label(self._call(), p, src, part, links, first_cell, single_watershed, nodata, src_nodata)
 
 
+class _StripOutletToolsStage:
+    """StripPipeline.moveoutletstostrm / connectdown_argmax / connectdown_walk (include/taudem_amd_outlets.h).  The walks advance the points that lie in
+    this strip's owned rows and hand the state back: the caller passes it from strip to strip until a round over all strips moves nothing.  The
+    maxima of all strips meet in taudem_amd.api.ConnectDownPoints (strip order = row-major order).  No halo row is read."""
+
+    def moveoutletstostrm(self, p, src, row0, ny_total, state, maxdist=50, nodata=int(P_NODATA), src_nodata=int(P_NODATA)):
+        """moved = moveoutletstostrm(p, src, row0, ny_total, state) on this strip: state = (columns, GLOBAL rows, dist, done), int32 numpy arrays advanced
+        in place (start: dist 0, done 0); moved: the outlets this strip advanced or finished.  row0: the global row of the strip's first owned row."""
+        return api._moveoutlets_strip(self._call(), p, src, row0, ny_total, maxdist, state, nodata, src_nodata)
+
+    def connectdown_argmax(self, w, ad8, row0, w_nodata=-2147483647):
+        """part = connectdown_argmax(w, ad8, row0) on this strip: the handle of the maxima of its owned rows, the table sized by the largest id of all strips."""
+        return api._connectdown_strip(self._call(), w, ad8, row0, w_nodata)
+
+    def connectdown_walk(self, p, w, row0, ny_total, state, movedist=10):
+        """moved = connectdown_walk(p, w, row0, ny_total, state) on this strip: state = ConnectDownPoints.state(), advanced in place."""
+        return api._connectdown_walk_strip(self._call(), p, w, row0, ny_total, movedist, state)
+
+
 class _StripPeukerDouglasStage:
     """StripPipeline.peukerdouglas (include/taudem_amd_peuker.h)."""
 
@@ -328,7 +347,7 @@ class _StripPeukerDouglasStage:
         return api._peukerdouglas(self._call(), fel, nodata, weights, float_weights, out)
 
 
-class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage):
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

@@ -179,6 +179,21 @@ def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, ou
 streamnet = netsetup
 
 
+def outletstosrc(pfile, srcfile, outletsdatasrc, outletslayer="", uselyrname=0, lyrno=0, outletmoveddatasrc="", outletmovedlayer="", maxdist=50):
+    """src/MoveOutletsToStrm.cpp:80 (MoveOutletsToStrm).  The moved outlets go to a shapefile (.shp) or GeoJSON (.json / .geojson) layer; any other
+    output is refused before anything is read.  The layer arguments are accepted and ignored."""
+    return _lib.load().tdx_tool_moveoutletstostrm(_b(pfile), _b(srcfile), _b(outletsdatasrc), _b(outletslayer), int(uselyrname), int(lyrno), _b(outletmoveddatasrc),
+                                                  _b(outletmovedlayer), int(maxdist))
+
+
+moveoutletstostrm = outletstosrc
+
+
+def connectdown(pfile, wfile, ad8file, outletdatasrc, outletlyr="", movedoutletdatasrc="", movedoutletlyr="", movedist=10):
+    """src/ConnectDown.cpp:79 (ConnectDown).  Both outputs are shapefile or GeoJSON point layers, as for outletstosrc."""
+    return _lib.load().tdx_tool_connectdown(_b(pfile), _b(wfile), _b(ad8file), _b(outletdatasrc), _b(outletlyr), _b(movedoutletdatasrc), _b(movedoutletlyr), int(movedist))
+
+
 def dsllArea(angfile, ctptfile, dmfile, datasrc="", lyrname="", uselyrname=0, lyrno=0, qfile="", dgfile="", useOutlets=0, contcheck=1, cSol=1.0):
     """src/DinfConcLimAccum.cpp:61"""
     return _lib.load().tdx_tool_dinfconclimaccum(_b(angfile), _b(ctptfile), _b(dmfile), _b(datasrc), _b(lyrname), int(uselyrname), int(lyrno), _b(qfile), _b(dgfile),
