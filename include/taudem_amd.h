@@ -662,6 +662,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* MoveOutletsToStrm, ConnectDown and the point-layer writer (compute entry points and file-level tool functions): likewise */
 #include "taudem_amd_outlets.h"
 
+/* SinmapSI (compute entry points, the -calpar reader and the file-level tool function): likewise */
+#include "taudem_amd_sinmap.h"
+
 #ifdef __cplusplus
 }
 #endif

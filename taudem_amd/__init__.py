@@ -9,5 +9,6 @@ from ._lib import LIB_PATH, TdxError, load  # noqa: F401
 from .api import (ANG_NODATA, AREA_NODATA, FEL_NODATA, P_NODATA, SLOPE_NODATA, Context, StreamNetLinks, catchhydrogeo, dropanalysis, dropanalysis_table, inundepth, peukerdouglas, raster_info, streamnet, streamnet_text,  # noqa: F401
                   read_raster, synth_base_wavelength, write_raster)
 from .api import ConnectDownPoints, connectdown, moveoutletstostrm, write_points  # noqa: F401
+from .api import read_calpar, sinmapsi  # noqa: F401
 
 __version__ = "0.1.0"

@@ -331,6 +331,22 @@ OUTLETS_SYMBOLS = tuple(_OUTLETS_SIGNATURES)
 CONNECTDOWN_PHASES = ("maxid", "argmax", "decode", "walk")
 CONNECTDOWN_MAX_ID = 134217727   # TDX_CONNECTDOWN_MAX_ID
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_sinmap.h declares, the sixth extension header
+# SinmapSI: ctx, slp, sca, scamin, scamax (both optional), cal, nx, ny, slp_nodata, cal_nodata, nreg, reg_id, tmin, tmax, cmin, cmax, phimin, phimax, rhos,
+# rminter, rmaxter, g, rhow, si, sat, stats; the strip form has the comm after the context
+_SINMAP_TAIL = [_P, _P, _P, _P, _P, _I64, _I64, _F, C.c_double, _I32] + [_P] * 8 + [C.c_double, C.c_double, _F, _F, _P, _P, _P]
+_SINMAP_SIGNATURES = {
+    "tdx_sinmapsi": (C.c_int, [_P] + _SINMAP_TAIL),
+    "tdx_sinmapsi_dev": (C.c_int, [_P] + _SINMAP_TAIL),
+    "tdx_sinmapsi_strip": (C.c_int, [_P, _P] + _SINMAP_TAIL),
+    # path, capacity, reg_id, tmin, tmax, cmin, cmax, phimin, phimax, rhos, &count
+    "tdx_sinmap_read_calpar": (C.c_int, [C.c_char_p, _I32] + [_P] * 8 + [C.POINTER(_I32)]),
+    # slp, sca, scamin, scamax, cal, calpar, sat, si, rminter, rmaxter, par
+    "tdx_tool_sinmapsi": (C.c_int, [C.c_char_p] * 8 + [C.c_double, C.c_double, _P]),
+}
+SINMAP_SYMBOLS = tuple(_SINMAP_SIGNATURES)
+SINMAP_FIELDS = ("id", "tmin", "tmax", "cmin", "cmax", "phimin", "phimax", "rhos")   # the columns of a -calpar file
+
 _lib = None
 
 
@@ -355,7 +371,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
-                                   **_OUTLETS_SIGNATURES}.items():
+                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

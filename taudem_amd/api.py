@@ -220,7 +220,22 @@ class _OutletToolsStage:
         return _ret(_connectdown(_Call(self), p, w, ad8, movedist, nodata, w_nodata, phases), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage):
+class _SinmapStage:
+    """Context.sinmapsi; its entry points are those of include/taudem_amd_sinmap.h."""
+
+    def sinmapsi(self, slp, sca, cal, regions, rminter, rmaxter, g=9.81, rhow=1000.0, scamin=None, scamax=None, *, slp_nodata=float(SLOPE_NODATA),
+                 cal_nodata=-32768, out=None, stats=False):
+        """si, sat = sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g, rhow)  (src/SinmapSI.cpp:138): the SINMAP stability index and the saturation
+        raster, float32, nodata -1.
+
+        slp: tan of the slope angle (dinfflowdir's), sca: specific catchment area (areadinf's), cal: int16 region ids.  regions: the table of
+        read_calpar() - a dict of the columns id, tmin, tmax, cmin, cmax, phimin, phimax, rhos -, a sequence of such 8-tuples, or the path of a
+        -calpar file.  rminter / rmaxter: the recharge bounds, g and rhow the reference's -par; all four are rounded to float32 first, as the
+        reference scans them.  scamin / scamax: the road contributions, each optional.  out: (si, sat)."""
+        return _ret(_sinmapsi(_Call(self), slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scamax, slp_nodata, cal_nodata, out), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -680,6 +695,54 @@ def _peukerdouglas(f, fel, nodata, weights, float_weights, out):
     return (ss, w, st) if float_weights else (ss, st)
 
 
+def read_calpar(path):
+    """The region table of a SinmapSI -calpar file (one header line, then id,tmin,tmax,cmin,cmax,phimin,phimax,rhos per region, scanned as the
+    reference scans them): a dict of numpy columns, id int32 and the rest float32, in file order.  No GPU is needed.  A file that cannot be read
+    raises TdxError with code 15, a data line with fewer than 8 fields one that names the line."""
+    import os
+
+    lib = _lib.load()
+    n = C.c_int32(0)
+    check(lib.tdx_sinmap_read_calpar(os.fsencode(path), 0, *([None] * 8), C.byref(n)))
+    cols = {k: np.zeros(n.value, np.int32 if k == "id" else np.float32) for k in _lib.SINMAP_FIELDS}
+    check(lib.tdx_sinmap_read_calpar(os.fsencode(path), n.value, *[_v(cols[k]) for k in _lib.SINMAP_FIELDS], C.byref(n)))
+    return cols
+
+
+def _regions(regions):
+    """The eight columns of a region table given as read_calpar()'s dict, as rows of 8 values, or as a path."""
+    import os
+
+    if isinstance(regions, (str, bytes, os.PathLike)):
+        regions = read_calpar(regions)
+    if isinstance(regions, dict):
+        cols = [regions[k] for k in _lib.SINMAP_FIELDS]
+    else:
+        rows = [tuple(r) for r in regions]
+        if any(len(r) != 8 for r in rows):
+            raise ValueError("regions: need (id, tmin, tmax, cmin, cmax, phimin, phimax, rhos) per region")
+        cols = [[r[k] for r in rows] for k in range(8)]
+    cols = [_flat(c, np.int32 if k == 0 else np.float32) for k, c in enumerate(cols)]
+    if any(c.size != cols[0].size for c in cols):
+        raise ValueError("regions: columns of different lengths")
+    return cols
+
+
+def _sinmapsi(f, slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scamax, slp_nodata, cal_nodata, out):
+    ps = f.raster(slp, np.float32, "slp")
+    pa = f.raster(sca, np.float32, "sca")
+    pmin, pmax = f.raster(scamin, np.float32, "scamin"), f.raster(scamax, np.float32, "scamax")
+    pc = f.raster(cal, np.int16, "cal")
+    cols = _regions(regions)
+    f.keep += cols
+    o_si, o_sat = out if out is not None else (None, None)
+    si, psi = f.out(o_si, np.float32, "si")
+    sat, psat = f.out(o_sat, np.float32, "sat")
+    st = f.call("tdx_sinmapsi", ps, pa, pmin, pmax, pc, f.nx, f.ny, float(slp_nodata), float(cal_nodata), int(cols[0].size), *[_v(c) for c in cols],
+                float(np.float32(rminter)), float(np.float32(rmaxter)), float(g), float(rhow), psi, psat)
+    return si, sat, st
+
+
 def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids):
     """Context: (thresh, n1, n2, sums, length, total_area, table, optimum[, order, elevout], stats).  A strip: its own (thresh, n1, n2, sums, length,
     outlet_term[, order, elevout], stats) - outlet_term float32 per outlet, ad8 of the strip's terminal outlets and 0 elsewhere."""
@@ -1019,6 +1082,12 @@ def peukerdouglas(fel, device=0, **kw):
     """Context(device).peukerdouglas(...) for a single call."""
     with Context(device) as ctx:
         return ctx.peukerdouglas(fel, **kw)
+
+
+def sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g=9.81, rhow=1000.0, device=0, **kw):
+    """Context(device).sinmapsi(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g, rhow, **kw)
 
 
 def catchhydrogeo(hand, catch, slp, ids, stages, device=0, **kw):

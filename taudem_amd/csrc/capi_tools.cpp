@@ -33,6 +33,7 @@
 //   tdx_tool_inundepth           <- inundepth()           src/InunDepth.cpp:53-545
 //   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
 //   tdx_tool_peukerdouglas       <- peukerdouglas()       src/PeukerDouglas.cpp:54-241
+//   tdx_tool_sinmapsi            <- sindexcombined()      src/SinmapSI.cpp:138-441
 //   tdx_tool_moveoutletstostrm   <- outletstosrc()        src/MoveOutletsToStrm.cpp:80-914
 //   tdx_tool_connectdown         <- connectdown()         src/ConnectDown.cpp:79-893
 #include <atomic>
@@ -54,6 +55,7 @@
 #include "geotiff.hpp"
 #include "hand_tables.hpp"
 #include "outlets.hpp"
+#include "sinmap_table.hpp"
 #include "tool_strips.hpp"
 #include "vector_layer.hpp"
 
@@ -235,7 +237,8 @@ enum class Footer {
     FlowDir,       // D8FlowDir / DinfFlowDir: slopes and flats apart, the slope raster written in between (src/d8.cpp, src/dinf.cpp)
     CountOnly,     // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
     ComputeOnly,   // CatchHydroGeo / InunDepth: one line, <label>: the whole run in seconds
-    NoWrite        // DropAnalysis: <label>: N + read / compute / total (src/DropAnalysis.cpp:690-692)
+    NoWrite,       // DropAnalysis: <label>: N + read / compute / total (src/DropAnalysis.cpp:690-692)
+    ComputeWrite   // SinmapSI: "Compute time" from the start of the call (reading included) and "File write time" (src/SinmapSI.cpp:409-435)
 };
 
 template <class T> constexpr tdx::DType dtype_of();
@@ -330,6 +333,7 @@ struct ToolRun {
         case Footer::CountOnly: printf("%s: %d\n", label, nproc); break;
         case Footer::ComputeOnly: printf("%s: %f\n", label, writet - begint); break;
         case Footer::NoWrite: printf("%s: %d\nRead time: %f\nCompute time: %f\nTotal time: %f\n", label, nproc, readt - begint, writet - readt, writet - begint); break;
+        case Footer::ComputeWrite: printf("%s: %f\nFile write time: %f\n", label, computet - begint, writet - computet); break;
         }
         if (stats_name) print_gpu_stats(stats_name, st, grid->info.nx * grid->info.ny);
         return 0;
@@ -1569,6 +1573,90 @@ int tdx_tool_connectdown(const char* pfile, const char* wfile, const char* ad8fi
     printf("Total time: %f\n", now_s() - t.begint);
     print_gpu_stats("connectdown", t.st, nx * ny);
     return 0;
+}
+
+int tdx_sinmap_read_calpar(const char* path, int32_t capacity, int32_t* reg_id, float* tmin, float* tmax, float* cmin, float* cmax, float* phimin, float* phimax,
+                           float* rhos, int32_t* count) {
+    if (!path || !count || capacity < 0 || (capacity > 0 && !(reg_id && tmin && tmax && cmin && cmax && phimin && phimax && rhos)))
+        return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_sinmap_read_calpar: bad argument");
+    sinmap::Regions r;
+    std::string err;
+    const int rc = sinmap::read_calpar(path, r, err);
+    if (rc != 0) return tdx_fail(nullptr, rc == 15 ? 15 : TDX_ERR_ARG, "tdx_sinmap_read_calpar: " + err);
+    *count = int32_t(r.size());
+    for (size_t k = 0; k < r.size() && k < size_t(capacity); k++) {
+        reg_id[k] = r.id[k];
+        tmin[k] = r.tmin[k]; tmax[k] = r.tmax[k]; cmin[k] = r.cmin[k]; cmax[k] = r.cmax[k];
+        phimin[k] = r.phimin[k]; phimax[k] = r.phimax[k]; rhos[k] = r.rhos[k];
+    }
+    return TDX_OK;
+}
+
+// The reference reads the region table before it opens a raster (an unreadable file: 15 at once), compares every raster with the slope file and
+// returns 1 with a sentence naming the two files on stderr; both outputs take the slope file's georeferencing and the nodata tag -1.
+int tdx_tool_sinmapsi(const char* slopefile, const char* scaterrainfile, const char* scarminroadfile, const char* scarmaxroadfile, const char* tergridfile,
+                      const char* terparfile, const char* satfile, const char* sincombinedfile, double rminter, double rmaxter, const double* par) {
+    if (!slopefile || !scaterrainfile || !tergridfile || !terparfile || !satfile || !sincombinedfile || !par) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_sinmapsi: bad argument");
+    ToolRun t("SinmapSI");
+    const float g = float(par[0]), rw = float(par[1]);   // src/SinmapSI.cpp:174-175
+    sinmap::Regions reg;
+    {
+        std::string err;
+        const int rc = sinmap::read_calpar(terparfile, reg, err);
+        if (rc == 15) return 15;
+        if (rc != 0) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_sinmapsi: " + err);
+        if (reg.size() > 32767) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_sinmapsi: more than 32767 regions");
+    }
+    const bool have_min = scarminroadfile && *scarminroadfile, have_max = scarmaxroadfile && *scarmaxroadfile;
+    Raster slp, sca, smin, smax, cal;
+    t.input(slopefile, F32, slp);
+    if (t.rc == TDX_OK) {   // src/SinmapSI.cpp:233-239
+        const float timeestimate = (1e-7 * slp.info.nx * slp.info.ny / pow((double)tool_gpus(), 1)) / 60 + 1;
+        fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+        fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the "
+                        "computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+        fflush(stderr);
+    }
+    // (the last sentence says "road max contributing area" for the calibration grid: the reference's words)
+    const struct { const char* path; bool have; tdx::DType type; Raster* r; const char* what; } ins[] = {
+        {scaterrainfile, true, F32, &sca, "Contributing area"}, {scarminroadfile, have_min, F32, &smin, "road min contributing area"},
+        {scarmaxroadfile, have_max, F32, &smax, "road max contributing area"}, {tergridfile, true, I16, &cal, "road max contributing area"}};
+    for (const auto& in : ins) {
+        if (!in.have || t.rc != TDX_OK) continue;
+        t.input(in.path, in.type, *in.r, Mismatch::Silent);
+        if (t.rc == TDX_ERR_MISMATCH) {
+            fprintf(stderr, "Slope (%s) and %s (%s) files have different dimensions", slopefile, in.what, in.path);
+            fflush(stderr);
+            return 1;
+        }
+    }
+    if (!t.read_done()) return t.rc;
+    std::vector<float> si(t.cells()), sat(t.cells());
+    const float nd = (float)slp.info.nodata;
+    const double cal_nd = cal.info.nodata;
+    const int32_t nreg = int32_t(reg.size());
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            return tdx_sinmapsi(c, slp.f.data(), sca.f.data(), have_min ? smin.f.data() : nullptr, have_max ? smax.f.data() : nullptr, cal.s.data(), slp.info.nx, slp.info.ny,
+                                nd, cal_nd, nreg, reg.id.data(), reg.tmin.data(), reg.tmax.data(), reg.cmin.data(), reg.cmax.data(), reg.phimin.data(), reg.phimax.data(),
+                                reg.rhos.data(), rminter, rmaxter, g, rw, si.data(), sat.data(), s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            const float* d_slp = j.in(slp.f);
+            const float* d_sca = j.in(sca.f);
+            const float* d_min = have_min ? j.in(smin.f) : nullptr;
+            const float* d_max = have_max ? j.in(smax.f) : nullptr;
+            const int16_t* d_cal = j.in(cal.s);
+            float* d_si = j.out(si);
+            float* d_sat = j.out(sat);
+            if (j.error) return j.error;
+            return tdx_sinmapsi_strip(j.ctx, j.comm, d_slp, d_sca, d_min, d_max, d_cal, j.nx, j.nyl, nd, cal_nd, nreg, reg.id.data(), reg.tmin.data(), reg.tmax.data(),
+                                      reg.cmin.data(), reg.cmax.data(), reg.phimin.data(), reg.phimax.data(), reg.rhos.data(), rminter, rmaxter, g, rw, d_si, d_sat, s);
+        });
+    if (!ok) return t.rc;
+    t.output(sincombinedfile, si, slp, -1.0);
+    t.output(satfile, sat, slp, -1.0);
+    return t.finish("Compute time", "sinmapsi", Footer::ComputeWrite);
 }
 
 }  // extern "C"

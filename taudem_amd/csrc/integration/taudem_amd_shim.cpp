@@ -6,7 +6,7 @@
 // mains call (prototypes: src/flood.h:1-2, src/d8.h:5, src/aread8.h:3, src/tardemlib.h:70, src/areadinf.h:2,
 // src/dinfdecayaccum.cpp:61-62, src/gridnet.cpp:54-55, src/Threshold.cpp:49, src/D8flowpathextremeup.cpp:58,
 // src/DinfUpDependence.cpp:52, src/DinfRevAccum.cpp:51, src/DinfDistDown.cpp:66-67, src/DinfDistUp.cpp:65-66,
-// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56, src/flowdircond.cpp:54, src/D8VDistToStrm.cpp:58, src/SlopeAveDown.cpp:59, src/retlimro.h, src/DinfAvalanche.cpp:62-63, src/CatchHydroGeo.cpp:69, src/InunDepth.h, src/DropAnalysis.h, src/PeukerDouglasmn.cpp:51) forwards to the
+// src/D8HDistToStrm.cpp:57, src/gagewatershed.cpp:56, src/flowdircond.cpp:54, src/D8VDistToStrm.cpp:58, src/SlopeAveDown.cpp:59, src/retlimro.h, src/DinfAvalanche.cpp:62-63, src/CatchHydroGeo.cpp:69, src/InunDepth.h, src/DropAnalysis.h, src/PeukerDouglasmn.cpp:51, src/SinmapSI.cpp:138) forwards to the
 // file-level C ABI, and nameadd() (src/commonLib.cpp:53-73, the only other symbol the mains use) is provided here.  No MPI and
 // no GDAL at link time (their headers are only needed to COMPILE the mains, which include commonLib.h).
 // oracle/Makefile builds oracle/_ref/shim_<tool> this way; tests/test_gpu_cli.py runs them against the reference's rasters.
@@ -64,6 +64,8 @@ int dropan(char* areafile, char* dirfile, char* elevfile, char* ssafile, char* d
 { return tdx_tool_dropanalysis(areafile, dirfile, elevfile, ssafile, dropfile, datasrc, lyrname, uselyrname, lyrno, threshmin, threshmax, nthresh, steptype, threshopt); }
 int peukerdouglas(char* felfile, char* ssfile, float* p)
 { return tdx_tool_peukerdouglas(felfile, ssfile, p); }
+int sindexcombined(char* slopefile, char* scaterrainfile, char* scarminroadfile, char* scarmaxroadfile, char* tergridfile, char* terparfile, char* satfile, char* sincombinedfile, double Rminter, double Rmaxter, double* par)
+{ return tdx_tool_sinmapsi(slopefile, scaterrainfile, scarminroadfile, scarmaxroadfile, tergridfile, terparfile, satfile, sincombinedfile, Rminter, Rmaxter, par); }
 int threshold(char* ssafile, char* srcfile, char* maskfile, float thresh, int usemask)
 { return tdx_tool_threshold(ssafile, srcfile, maskfile, thresh, usemask); }
 

@@ -347,7 +347,17 @@ class _StripPeukerDouglasStage:
         return api._peukerdouglas(self._call(), fel, nodata, weights, float_weights, out)
 
 
-class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage):
+class _StripSinmapStage:
+    """StripPipeline.sinmapsi (include/taudem_amd_sinmap.h)."""
+
+    def sinmapsi(self, slp, sca, cal, regions, rminter, rmaxter, g=9.81, rhow=1000.0, scamin=None, scamax=None, slp_nodata=float(api.SLOPE_NODATA), cal_nodata=-32768,
+                 out=None):
+        """si, sat = sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g, rhow) on this strip (src/SinmapSI.cpp:138).  Cells are independent: the owned
+        rows are computed, nothing is exchanged, and the halo rows of si and sat are not written."""
+        return api._sinmapsi(self._call(), slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scamax, slp_nodata, cal_nodata, out)
+
+
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

@@ -169,6 +169,23 @@ def peukerdouglas(felfile, ssfile, p=(0.4, 0.1, 0.05)):
     return _lib.load().tdx_tool_peukerdouglas(_b(felfile), _b(ssfile), ctypes.cast(w, ctypes.c_void_p))
 
 
+def sindexcombined(slopefile, scaterrainfile, scarminroadfile, scarmaxroadfile, tergridfile, terparfile, satfile, sincombinedfile, Rminter, Rmaxter, par=(9.81, 1000.0)):
+    """src/SinmapSI.cpp:138 (SinmapSI): par = (g, rhow); an empty road file name means that raster is absent.  The four numbers are rounded to float32
+    first, as the reference's main scans them."""
+    import ctypes
+
+    import numpy as np
+
+    p = (ctypes.c_double * 2)(float(np.float32(par[0])), float(np.float32(par[1])))
+    return _lib.load().tdx_tool_sinmapsi(_b(slopefile), _b(scaterrainfile), _b(scarminroadfile or ""), _b(scarmaxroadfile or ""), _b(tergridfile), _b(terparfile),
+                                         _b(satfile), _b(sincombinedfile), float(np.float32(Rminter)), float(np.float32(Rmaxter)), ctypes.cast(p, ctypes.c_void_p))
+
+
+def sinmapsi(slpfile, scafile, calfile, calparfile, sifile, satfile, rminter, rmaxter, g=9.81, rhow=1000.0, scaminfile="", scamaxfile=""):
+    """SinmapSI with the arguments in the order of the reference's command line."""
+    return sindexcombined(slpfile, scafile, scaminfile, scamaxfile, calfile, calparfile, satfile, sifile, rminter, rmaxter, (g, rhow))
+
+
 def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, outletsds="", lyrname="", uselayername=0, lyrno=0, wfile="", streamnetsrc="",
              streamnetlyr="", useOutlets=0, ordert=1, verbose=False):
     """src/streamnet.cpp:372 (StreamNet); ordert = 0 is -sw.  The stream network layer is not written: a non-empty streamnetsrc / streamnetlyr is refused."""
