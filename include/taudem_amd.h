@@ -665,6 +665,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* SinmapSI (compute entry points, the -calpar reader and the file-level tool function): likewise */
 #include "taudem_amd_sinmap.h"
 
+/* TWI, SlopeArea, SlopeAreaRatio, LengthArea and SetRegion (compute entry points and file-level tool functions): likewise */
+#include "taudem_amd_indices.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,5 +10,6 @@ from .api import (ANG_NODATA, AREA_NODATA, FEL_NODATA, P_NODATA, SLOPE_NODATA, C
                   read_raster, synth_base_wavelength, write_raster)
 from .api import ConnectDownPoints, connectdown, moveoutletstostrm, write_points  # noqa: F401
 from .api import read_calpar, sinmapsi  # noqa: F401
+from .api import lengtharea, setregion, terrain_indices  # noqa: F401
 
 __version__ = "0.1.0"

@@ -347,6 +347,32 @@ _SINMAP_SIGNATURES = {
 SINMAP_SYMBOLS = tuple(_SINMAP_SIGNATURES)
 SINMAP_FIELDS = ("id", "tmin", "tmax", "cmin", "cmax", "phimin", "phimax", "rhos")   # the columns of a -calpar file
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_indices.h declares, the seventh extension header
+# terrain indices: ctx, slp, sca, nx, ny, slp_nodata, sca_nodata, m, n, twi, sa, sar (each optional, not all three), stats
+_TERRAIN_TAIL = [_P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P]
+# LengthArea: ctx, plen, ad8, nx, ny, M, y, ss, stats
+_LENGTHAREA_TAIL = [_P, _P, _I64, _I64, _F, _F, _P, _P]
+# SetRegion: ctx, p, gw, nx, ny, p_nodata, gw_nodata, region_id, out, stats
+_SETREGION_TAIL = [_P, _P, _I64, _I64, _I16, _I32, _I32, _P, _P]
+_INDICES_SIGNATURES = {
+    "tdx_terrain_indices": (C.c_int, [_P] + _TERRAIN_TAIL),
+    "tdx_terrain_indices_dev": (C.c_int, [_P] + _TERRAIN_TAIL),
+    "tdx_terrain_indices_strip": (C.c_int, [_P, _P] + _TERRAIN_TAIL),
+    "tdx_lengtharea": (C.c_int, [_P] + _LENGTHAREA_TAIL),
+    "tdx_lengtharea_dev": (C.c_int, [_P] + _LENGTHAREA_TAIL),
+    "tdx_lengtharea_strip": (C.c_int, [_P, _P] + _LENGTHAREA_TAIL),
+    "tdx_setregion": (C.c_int, [_P] + _SETREGION_TAIL),
+    "tdx_setregion_dev": (C.c_int, [_P] + _SETREGION_TAIL),
+    "tdx_setregion_strip": (C.c_int, [_P, _P] + _SETREGION_TAIL),
+    "tdx_tool_twi": (C.c_int, [C.c_char_p] * 3),
+    "tdx_tool_slopearea": (C.c_int, [C.c_char_p] * 3 + [_P]),
+    "tdx_tool_slopearearatio": (C.c_int, [C.c_char_p] * 3),
+    "tdx_tool_lengtharea": (C.c_int, [C.c_char_p] * 3 + [_P]),
+    "tdx_tool_setregion": (C.c_int, [C.c_char_p] * 3 + [_I32]),
+}
+INDICES_SYMBOLS = tuple(_INDICES_SIGNATURES)
+TERRAIN_OUTPUTS = ("twi", "sa", "sar")   # the outputs of tdx_terrain_indices, in the header's order
+
 _lib = None
 
 
@@ -371,7 +397,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
-                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES}.items():
+                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -235,7 +235,45 @@ class _SinmapStage:
         return _ret(_sinmapsi(_Call(self), slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scamax, slp_nodata, cal_nodata, out), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage):
+class _TerrainIndexStage:
+    """Context.terrain_indices, twi, slopearea, slopearearatio, lengtharea and setregion; their entry points are those of include/taudem_amd_indices.h."""
+
+    def terrain_indices(self, slp, sca, m=2.0, n=1.0, want=_lib.TERRAIN_OUTPUTS, *, slp_nodata=float(SLOPE_NODATA), sca_nodata=float(AREA_NODATA), out=None,
+                        stats=False):
+        """twi, sa, sar = terrain_indices(slp, sca): the outputs named in `want` (any non-empty subset of "twi", "sa", "sar", returned in that order) from
+        one pass over slp and sca, float32, nodata -1.
+
+        twi = ln(sca / slp) where both have data and are > 0 (src/TWI.cpp:49); sa = slp^m * sca^n where both are >= 0, without a nodata test
+        (src/SlopeArea.cpp:52); sar = slp / sca where sca has data (src/SlopeAreaRatio.cpp:49).  m and n are rounded to float32 first, as the reference
+        scans them.  ln and the powers are the correctly rounded float32 (include/taudem_amd_indices.h).  out: one raster per name in `want`."""
+        return _ret(_terrain_indices(_Call(self), slp, sca, m, n, want, slp_nodata, sca_nodata, out), stats)
+
+    def twi(self, slp, sca, *, slp_nodata=float(SLOPE_NODATA), sca_nodata=float(AREA_NODATA), out=None, stats=False):
+        """twi = terrain_indices(slp, sca, want=("twi",))  (src/TWI.cpp:49)."""
+        return _ret(_terrain_indices(_Call(self), slp, sca, 0.0, 0.0, ("twi",), slp_nodata, sca_nodata, None if out is None else (out,)), stats)
+
+    def slopearea(self, slp, sca, m=2.0, n=1.0, *, out=None, stats=False):
+        """sa = terrain_indices(slp, sca, m, n, want=("sa",))  (src/SlopeArea.cpp:52)."""
+        return _ret(_terrain_indices(_Call(self), slp, sca, m, n, ("sa",), float(SLOPE_NODATA), float(AREA_NODATA), None if out is None else (out,)), stats)
+
+    def slopearearatio(self, slp, sca, *, sca_nodata=float(AREA_NODATA), out=None, stats=False):
+        """sar = terrain_indices(slp, sca, want=("sar",))  (src/SlopeAreaRatio.cpp:49)."""
+        return _ret(_terrain_indices(_Call(self), slp, sca, 0.0, 0.0, ("sar",), float(SLOPE_NODATA), sca_nodata, None if out is None else (out,)), stats)
+
+    def lengtharea(self, plen, ad8, M=0.03, y=1.3, *, out=None, stats=False):
+        """ss = lengtharea(plen, ad8)  (src/LengthArea.cpp:51): int16, 1 where ad8 >= M * plen^y, 0 where not, -32768 where plen is negative or NaN.
+
+        plen float32 (gridnet's), ad8 float32 as aread8 leaves it: each value becomes the int32 the reference's read of the file gives (halves away
+        from zero) and is compared as a float.  M and y are rounded to float32 first."""
+        return _ret(_lengtharea(_Call(self), plen, ad8, M, y, out), stats)
+
+    def setregion(self, p, gw, region_id=1, *, nodata=int(P_NODATA), gw_nodata=-2147483647, out=None, stats=False):
+        """region = setregion(p, gw, region_id)  (src/SetRegion.cpp:78): int32, region_id on every cell that has data in gw (int32) or in p (int16) or
+        that a neighbour's p drains into, -2147483647 on the rest."""
+        return _ret(_setregion(_Call(self), p, gw, region_id, nodata, gw_nodata, out), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -743,6 +781,35 @@ def _sinmapsi(f, slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scam
     return si, sat, st
 
 
+def _terrain_indices(f, slp, sca, m, n, want, slp_nodata, sca_nodata, out):
+    want = tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in _lib.TERRAIN_OUTPUTS for w in want):
+        raise ValueError(f"want: need a non-empty selection of {_lib.TERRAIN_OUTPUTS} without repeats, not {want!r}")
+    given = (None,) * len(want) if out is None else tuple(out)
+    if len(given) != len(want):
+        raise ValueError("out: need one raster per name in want")
+    ps = f.raster(slp, np.float32, "slp")
+    pa = f.raster(sca, np.float32, "sca")
+    res = {w: f.out(g, np.float32, w) for w, g in zip(want, given)}
+    ptr = [res[w][1] if w in res else None for w in _lib.TERRAIN_OUTPUTS]
+    st = f.call("tdx_terrain_indices", ps, pa, f.nx, f.ny, float(slp_nodata), float(sca_nodata), float(np.float32(m)), float(np.float32(n)), *ptr)
+    return tuple(res[w][0] for w in want) + (st,)
+
+
+def _lengtharea(f, plen, ad8, M, y, out):
+    pl = f.raster(plen, np.float32, "plen")
+    pa = f.raster(ad8, np.float32, "ad8")
+    ss, ps = f.out(out, np.int16, "ss")
+    return ss, f.call("tdx_lengtharea", pl, pa, f.nx, f.ny, float(np.float32(M)), float(np.float32(y)), ps)
+
+
+def _setregion(f, p, gw, region_id, nodata, gw_nodata, out):
+    pp = f.raster(p, np.int16, "p")
+    pg = f.raster(gw, np.int32, "gw")
+    o, po = f.out(out, np.int32, "region")
+    return o, f.call("tdx_setregion", pp, pg, f.nx, f.ny, int(nodata), int(gw_nodata), int(region_id), po)
+
+
 def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids):
     """Context: (thresh, n1, n2, sums, length, total_area, table, optimum[, order, elevout], stats).  A strip: its own (thresh, n1, n2, sums, length,
     outlet_term[, order, elevout], stats) - outlet_term float32 per outlet, ad8 of the strip's terminal outlets and 0 elsewhere."""
@@ -1082,6 +1149,24 @@ def peukerdouglas(fel, device=0, **kw):
     """Context(device).peukerdouglas(...) for a single call."""
     with Context(device) as ctx:
         return ctx.peukerdouglas(fel, **kw)
+
+
+def terrain_indices(slp, sca, m=2.0, n=1.0, want=_lib.TERRAIN_OUTPUTS, device=0, **kw):
+    """Context(device).terrain_indices(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.terrain_indices(slp, sca, m, n, want, **kw)
+
+
+def lengtharea(plen, ad8, M=0.03, y=1.3, device=0, **kw):
+    """Context(device).lengtharea(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.lengtharea(plen, ad8, M, y, **kw)
+
+
+def setregion(p, gw, region_id=1, device=0, **kw):
+    """Context(device).setregion(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.setregion(p, gw, region_id, **kw)
 
 
 def sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g=9.81, rhow=1000.0, device=0, **kw):

@@ -34,6 +34,11 @@
 //   tdx_tool_dropanalysis        <- dropan()              src/DropAnalysis.cpp:172-705
 //   tdx_tool_peukerdouglas       <- peukerdouglas()       src/PeukerDouglas.cpp:54-241
 //   tdx_tool_sinmapsi            <- sindexcombined()      src/SinmapSI.cpp:138-441
+//   tdx_tool_twi                 <- twigrid()             src/TWI.cpp:49-153
+//   tdx_tool_slopearea           <- slopearea()           src/SlopeArea.cpp:52-152
+//   tdx_tool_slopearearatio      <- atanbgrid()           src/SlopeAreaRatio.cpp:49-148
+//   tdx_tool_lengtharea          <- lengtharea()          src/LengthArea.cpp:51-149
+//   tdx_tool_setregion           <- setregion()           src/SetRegion.cpp:78-191
 //   tdx_tool_moveoutletstostrm   <- outletstosrc()        src/MoveOutletsToStrm.cpp:80-914
 //   tdx_tool_connectdown         <- connectdown()         src/ConnectDown.cpp:79-893
 #include <atomic>
@@ -238,7 +243,8 @@ enum class Footer {
     CountOnly,     // RetLimFlow: the reference prints no times; the count that ran, as the other tools say it
     ComputeOnly,   // CatchHydroGeo / InunDepth: one line, <label>: the whole run in seconds
     NoWrite,       // DropAnalysis: <label>: N + read / compute / total (src/DropAnalysis.cpp:690-692)
-    ComputeWrite   // SinmapSI: "Compute time" from the start of the call (reading included) and "File write time" (src/SinmapSI.cpp:409-435)
+    ComputeWrite,  // SinmapSI: "Compute time" from the start of the call (reading included) and "File write time" (src/SinmapSI.cpp:409-435)
+    ComputeLine    // TWI, SlopeArea, SlopeAreaRatio, LengthArea: one line, <label>: the compute step alone (src/TWI.cpp:91,132-141)
 };
 
 template <class T> constexpr tdx::DType dtype_of();
@@ -334,6 +340,7 @@ struct ToolRun {
         case Footer::ComputeOnly: printf("%s: %f\n", label, writet - begint); break;
         case Footer::NoWrite: printf("%s: %d\nRead time: %f\nCompute time: %f\nTotal time: %f\n", label, nproc, readt - begint, writet - readt, writet - begint); break;
         case Footer::ComputeWrite: printf("%s: %f\nFile write time: %f\n", label, computet - begint, writet - computet); break;
+        case Footer::ComputeLine: printf("%s: %f\n", label, computet - readt); break;
         }
         if (stats_name) print_gpu_stats(stats_name, st, grid->info.nx * grid->info.ny);
         return 0;
@@ -1657,6 +1664,125 @@ int tdx_tool_sinmapsi(const char* slopefile, const char* scaterrainfile, const c
     t.output(sincombinedfile, si, slp, -1.0);
     t.output(satfile, sat, slp, -1.0);
     return t.finish("Compute time", "sinmapsi", Footer::ComputeWrite);
+}
+
+}  // extern "C"
+
+namespace {
+
+// what rank 0 of TWI, SlopeArea, SlopeAreaRatio and LengthArea says on stderr once the first raster is open (src/TWI.cpp:67-73)
+void print_time_estimate(const ToolRun& t, const Raster& first) {
+    if (t.rc != TDX_OK) return;
+    const float timeestimate = (1e-7 * first.info.nx * first.info.ny / pow((double)tool_gpus(), 1)) / 60 + 1;
+    fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+    fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the "
+                    "computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+    fflush(stderr);
+}
+
+// TWI, SlopeArea and SlopeAreaRatio: slp and sca in, one float raster out with the slope file's georeferencing and the nodata tag -1.  which: 0 twi, 1 sa, 2 sar
+int terrain_index_tool(const char* banner, const char* stats_name, int which, const char* slopefile, const char* areafile, const char* outfile, float m, float n) {
+    ToolRun t(banner);
+    Raster slp, sca;
+    t.input(slopefile, F32, slp);
+    print_time_estimate(t, slp);
+    t.input(areafile, F32, sca, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) return 1;
+    if (!t.read_done()) return t.rc;
+    std::vector<float> out(t.cells());
+    const float slp_nd = (float)slp.info.nodata, sca_nd = (float)sca.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            float* o = out.data();
+            return tdx_terrain_indices(c, slp.f.data(), sca.f.data(), slp.info.nx, slp.info.ny, slp_nd, sca_nd, m, n, which == 0 ? o : nullptr, which == 1 ? o : nullptr,
+                                       which == 2 ? o : nullptr, s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            const float* d_slp = j.in(slp.f);
+            const float* d_sca = j.in(sca.f);
+            float* o = j.out(out);
+            if (j.error) return j.error;
+            return tdx_terrain_indices_strip(j.ctx, j.comm, d_slp, d_sca, j.nx, j.nyl, slp_nd, sca_nd, m, n, which == 0 ? o : nullptr, which == 1 ? o : nullptr,
+                                             which == 2 ? o : nullptr, s);
+        });
+    if (!ok) return t.rc;
+    t.output(outfile, out, slp, -1.0);
+    return t.finish("Compute time", stats_name, Footer::ComputeLine);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tdx_tool_twi(const char* slopefile, const char* areafile, const char* twifile) {
+    if (!slopefile || !areafile || !twifile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_twi: bad argument");
+    return terrain_index_tool("Topographic Wetness Index", "twi", 0, slopefile, areafile, twifile, 0.0f, 0.0f);
+}
+
+int tdx_tool_slopearea(const char* slopefile, const char* scafile, const char* safile, const float* p) {
+    if (!slopefile || !scafile || !safile || !p) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_slopearea: bad argument");
+    return terrain_index_tool("SlopeArea", "slopearea", 1, slopefile, scafile, safile, p[0], p[1]);
+}
+
+int tdx_tool_slopearearatio(const char* slopefile, const char* areafile, const char* atanbfile) {
+    if (!slopefile || !areafile || !atanbfile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_slopearearatio: bad argument");
+    return terrain_index_tool("SlopeAreaRatio", "slopearearatio", 2, slopefile, areafile, atanbfile, 0.0f, 0.0f);
+}
+
+// ad8 is read as the reference reads it (LONG_TYPE) and handed to the library as the float of that integer: the kernel's conversion gives the integer's
+// float back, which is what the reference compares.  ss takes the ad8 file's georeferencing (src/LengthArea.cpp:142).
+int tdx_tool_lengtharea(const char* plenfile, const char* ad8file, const char* ssfile, const float* p) {
+    if (!plenfile || !ad8file || !ssfile || !p) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_lengtharea: bad argument");
+    ToolRun t("LengthArea");
+    Raster plen, ad8;
+    t.input(plenfile, F32, plen);
+    print_time_estimate(t, plen);
+    t.input(ad8file, I32, ad8, Mismatch::Silent);
+    if (t.rc == TDX_ERR_MISMATCH) return 1;
+    if (t.rc == TDX_OK) {
+        ad8.f.resize(ad8.l.size());
+        for (size_t i = 0; i < ad8.l.size(); i++) ad8.f[i] = float(ad8.l[i]);
+    }
+    if (!t.read_done()) return t.rc;
+    std::vector<int16_t> ss(t.cells());
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_lengtharea(c, plen.f.data(), ad8.f.data(), plen.info.nx, plen.info.ny, p[0], p[1], ss.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            const float* d_plen = j.in(plen.f);
+            const float* d_ad8 = j.in(ad8.f);
+            int16_t* d_ss = j.out(ss);
+            if (j.error) return j.error;
+            return tdx_lengtharea_strip(j.ctx, j.comm, d_plen, d_ad8, j.nx, j.nyl, p[0], p[1], d_ss, s);
+        });
+    if (!ok) return t.rc;
+    t.output(ssfile, ss, ad8, -32768.0);
+    return t.finish("Compute time", "lengtharea", Footer::ComputeLine);
+}
+
+// The region grid takes the gw file's georeferencing and the nodata tag MISSINGLONG; the one time the reference prints covers the whole run (src/SetRegion.cpp:88-185)
+int tdx_tool_setregion(const char* fdrfile, const char* regiongwfile, const char* newfile, int32_t region_id) {
+    if (!fdrfile || !regiongwfile || !newfile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_setregion: bad argument");
+    ToolRun t("SetRegion");
+    Raster p, gw;
+    t.input(fdrfile, I16, p);
+    if (t.rc == TDX_OK) { fprintf(stderr, "Time estimate not available.\n"); fflush(stderr); }
+    t.input(regiongwfile, I32, gw);   // "File sizes do not match" and 5 (src/SetRegion.cpp:120-125)
+    if (!t.read_done()) return t.rc;
+    std::vector<int32_t> out(t.cells());
+    const int16_t pnd = (int16_t)p.info.nodata;
+    const int32_t gnd = (int32_t)gw.info.nodata;
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_setregion(c, p.s.data(), gw.l.data(), p.info.nx, p.info.ny, pnd, gnd, region_id, out.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_p = j.in(p.s);
+            const int32_t* d_gw = j.in(gw.l);
+            int32_t* d_out = j.out(out);
+            if (j.error) return j.error;
+            return tdx_setregion_strip(j.ctx, j.comm, d_p, d_gw, j.nx, j.nyl, pnd, gnd, region_id, d_out, s);
+        });
+    if (!ok) return t.rc;
+    t.output(newfile, out, gw, -2147483647.0);
+    return t.finish("Compute time", "setregion", Footer::ComputeOnly);
 }
 
 }  // extern "C"

@@ -66,6 +66,16 @@ int peukerdouglas(char* felfile, char* ssfile, float* p)
 { return tdx_tool_peukerdouglas(felfile, ssfile, p); }
 int sindexcombined(char* slopefile, char* scaterrainfile, char* scarminroadfile, char* scarmaxroadfile, char* tergridfile, char* terparfile, char* satfile, char* sincombinedfile, double Rminter, double Rmaxter, double* par)
 { return tdx_tool_sinmapsi(slopefile, scaterrainfile, scarminroadfile, scarmaxroadfile, tergridfile, terparfile, satfile, sincombinedfile, Rminter, Rmaxter, par); }
+int twigrid(char* slopefile, char* areafile, char* twifile)
+{ return tdx_tool_twi(slopefile, areafile, twifile); }
+int slopearea(char* slopefile, char* scafile, char* safile, float* p)
+{ return tdx_tool_slopearea(slopefile, scafile, safile, p); }
+int atanbgrid(char* slopefile, char* areafile, char* atanbfile)
+{ return tdx_tool_slopearearatio(slopefile, areafile, atanbfile); }
+int lengtharea(char* plenfile, char* ad8file, char* ssfile, float* p)
+{ return tdx_tool_lengtharea(plenfile, ad8file, ssfile, p); }
+int setregion(char* fdrfile, char* regiongwfile, char* newfile, int32_t regionID)
+{ return tdx_tool_setregion(fdrfile, regiongwfile, newfile, regionID); }
 int threshold(char* ssafile, char* srcfile, char* maskfile, float thresh, int usemask)
 { return tdx_tool_threshold(ssafile, srcfile, maskfile, thresh, usemask); }
 

@@ -357,7 +357,33 @@ class _StripSinmapStage:
         return api._sinmapsi(self._call(), slp, sca, cal, regions, rminter, rmaxter, g, rhow, scamin, scamax, slp_nodata, cal_nodata, out)
 
 
-class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage):
+class _StripTerrainIndexStage:
+    """StripPipeline.terrain_indices, twi, slopearea, slopearearatio, lengtharea and setregion (include/taudem_amd_indices.h).  The first five exchange nothing;
+    setregion fills the halo rows of p.  The halo rows of the outputs are not written."""
+
+    def terrain_indices(self, slp, sca, m=2.0, n=1.0, want=api._lib.TERRAIN_OUTPUTS, slp_nodata=float(api.SLOPE_NODATA), sca_nodata=float(api.AREA_NODATA), out=None):
+        """the outputs named in `want` (of "twi", "sa", "sar"), then the stats dict, on this strip."""
+        return api._terrain_indices(self._call(), slp, sca, m, n, want, slp_nodata, sca_nodata, out)
+
+    def twi(self, slp, sca, slp_nodata=float(api.SLOPE_NODATA), sca_nodata=float(api.AREA_NODATA), out=None):
+        return api._terrain_indices(self._call(), slp, sca, 0.0, 0.0, ("twi",), slp_nodata, sca_nodata, None if out is None else (out,))
+
+    def slopearea(self, slp, sca, m=2.0, n=1.0, out=None):
+        return api._terrain_indices(self._call(), slp, sca, m, n, ("sa",), float(api.SLOPE_NODATA), float(api.AREA_NODATA), None if out is None else (out,))
+
+    def slopearearatio(self, slp, sca, sca_nodata=float(api.AREA_NODATA), out=None):
+        return api._terrain_indices(self._call(), slp, sca, 0.0, 0.0, ("sar",), float(api.SLOPE_NODATA), sca_nodata, None if out is None else (out,))
+
+    def lengtharea(self, plen, ad8, M=0.03, y=1.3, out=None):
+        """ss = lengtharea(plen, ad8) on this strip (src/LengthArea.cpp:51)."""
+        return api._lengtharea(self._call(), plen, ad8, M, y, out)
+
+    def setregion(self, p, gw, region_id=1, nodata=int(P_NODATA), gw_nodata=-2147483647, out=None):
+        """region = setregion(p, gw, region_id) on this strip (src/SetRegion.cpp:78): the library fills the halo rows of p."""
+        return api._setregion(self._call(), p, gw, region_id, nodata, gw_nodata, out)
+
+
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage, _StripTerrainIndexStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

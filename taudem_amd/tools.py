@@ -186,6 +186,44 @@ def sinmapsi(slpfile, scafile, calfile, calparfile, sifile, satfile, rminter, rm
     return sindexcombined(slpfile, scafile, scaminfile, scamaxfile, calfile, calparfile, satfile, sifile, rminter, rmaxter, (g, rhow))
 
 
+def _two_floats(p):
+    import ctypes
+
+    v = (ctypes.c_float * 2)(float(p[0]), float(p[1]))
+    return v, ctypes.cast(v, ctypes.c_void_p)
+
+
+def twigrid(slopefile, areafile, twifile):
+    """src/TWI.cpp:49 (TWI)."""
+    return _lib.load().tdx_tool_twi(_b(slopefile), _b(areafile), _b(twifile))
+
+
+def slopearea(slopefile, scafile, safile, p=(2.0, 1.0)):
+    """src/SlopeArea.cpp:52 (SlopeArea): p = (m, n), the exponents of slope and area."""
+    keep, ptr = _two_floats(p)
+    return _lib.load().tdx_tool_slopearea(_b(slopefile), _b(scafile), _b(safile), ptr)
+
+
+def atanbgrid(slopefile, areafile, atanbfile):
+    """src/SlopeAreaRatio.cpp:49 (SlopeAreaRatio)."""
+    return _lib.load().tdx_tool_slopearearatio(_b(slopefile), _b(areafile), _b(atanbfile))
+
+
+def lengtharea(plenfile, ad8file, ssfile, p=(0.03, 1.3)):
+    """src/LengthArea.cpp:51 (LengthArea): p = (M, y)."""
+    keep, ptr = _two_floats(p)
+    return _lib.load().tdx_tool_lengtharea(_b(plenfile), _b(ad8file), _b(ssfile), ptr)
+
+
+def setregion(fdrfile, regiongwfile, newfile, regionID=1):
+    """src/SetRegion.cpp:78 (SetRegion)."""
+    return _lib.load().tdx_tool_setregion(_b(fdrfile), _b(regiongwfile), _b(newfile), int(regionID))
+
+
+twi = twigrid
+slopearearatio = atanbgrid
+
+
 def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, outletsds="", lyrname="", uselayername=0, lyrno=0, wfile="", streamnetsrc="",
              streamnetlyr="", useOutlets=0, ordert=1, verbose=False):
     """src/streamnet.cpp:372 (StreamNet); ordert = 0 is -sw.  The stream network layer is not written: a non-empty streamnetsrc / streamnetlyr is refused."""
