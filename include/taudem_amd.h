@@ -668,6 +668,12 @@ int tdx_tool_set_gpus(int ngpus);
 /* TWI, SlopeArea, SlopeAreaRatio, LengthArea and SetRegion (compute entry points and file-level tool functions): likewise */
 #include "taudem_amd_indices.h"
 
+/* EditRaster (compute entry points, the change-file reader and the file-level tool function): likewise */
+#include "taudem_amd_editraster.h"
+
+/* Line layers and CatchOutlets (host code throughout): likewise */
+#include "taudem_amd_catchoutlets.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,10 +63,26 @@ int tdx_streamnet_label_strip(tdx_context* ctx, const tdx_comm* comm, const int1
 /* The -tree and / or the -coord file from the rows (src/streamnet.cpp:1165, :1177; either name may be NULL: that file is not touched).  Returns 0 or
  * TDX_ERR_FILE. */
 int tdx_streamnet_write_text(const tdx_streamnet_links* links, const char* treefile, const char* coordfile);
+/* The stream network layer (-net) from the link rows: reachshape() src/streamnet.cpp:244-365 per link, in tree order.  Host code, no context, no GPU.
+ *   tdx_streamnet_net_rows   tree [n_links][9] and coord [n_points][5] as tdx_streamnet_links_copy returns them (columns 2..4 of coord hold float values and
+ *                            are used as floats: the reference's arithmetic on them is float arithmetic) -> real [n_links][9]: Length, DSContArea, strmDrop,
+ *                            Slope, StraightL, USContArea, DOUTEND, DOUTSTART, DOUTMID; first [n_links + 1]: offsets into x / y; x, y [n_vertices]: the
+ *                            vertices of every link REVERSED, so that vertex 0 is its downstream end (a link of one point is a line of ONE vertex, as the
+ *                            reference writes it).  n_vertices: the sum over the links of tree[.][2] - tree[.][1] + 1.  geographic: the raster's flag -
+ *                            every segment then goes through tiffIO::geotoLength (src/tiffIO.cpp:434), which needs nothing else of the raster.
+ *                            TDX_ERR_ARG: a link's rows lie outside coord, or n_vertices is not that sum.
+ *   tdx_streamnet_net_write  the layer of those lines with the reference's 17 fields (LINKNO, DSLINKNO, USLINKNO1, USLINKNO2: width 6; DSNODEID: 12;
+ *                            strmOrder: 6; Length: 16.1; Magnitude: 6; DSContArea: 16.1; strmDrop: 16.2; Slope: 16.12; StraightL: 16.1; USContArea:
+ *                            16.1; WSNO: 6; DOUTEND, DOUTSTART, DOUTMID: 16.1) as an ESRI shapefile or GeoJSON, by the extension of path.  Returns 0,
+ *                            TDX_ERR_ARG (extension) or TDX_ERR_FILE. */
+int tdx_streamnet_net_rows(const int64_t* tree, const double* coord, int64_t n_links, int64_t n_points, int geographic, int64_t n_vertices, double* real,
+                           int64_t* first, double* x, double* y);
+int tdx_streamnet_net_write(const tdx_streamnet_links* links, int geographic, const char* path);
 /* int netsetup(char* pfile, char* srcfile, char* ordfile, char* ad8file, char* elevfile, char* treefile, char* coordfile, char* outletsds,
  *              char* lyrname, int uselayername, int lyrno, char* wfile, char* streamnetsrc, char* streamnetlyr, long useOutlets, long ordert,
  *              bool verbose)                                                                                            src/streamnet.cpp:372
- * ordert = 0 is -sw.  The -net layer is not written: a call with a non-empty streamnetsrc or streamnetlyr is refused before anything is read. */
+ * ordert = 0 is -sw.  The -net layer is not written: a call with a non-empty streamnetsrc or streamnetlyr is refused before anything is read
+ * (tdx_streamnet_net_write makes the layer from the links of tdx_streamnet). */
 int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfile, const char* ad8file, const char* elevfile, const char* treefile,
                        const char* coordfile, const char* outletsds, const char* lyrname, int uselayername, int lyrno, const char* wfile,
                        const char* streamnetsrc, const char* streamnetlyr, long useOutlets, long ordert, int verbose);

@@ -11,5 +11,7 @@ from .api import (ANG_NODATA, AREA_NODATA, FEL_NODATA, P_NODATA, SLOPE_NODATA, C
 from .api import ConnectDownPoints, connectdown, moveoutletstostrm, write_points  # noqa: F401
 from .api import read_calpar, sinmapsi  # noqa: F401
 from .api import lengtharea, setregion, terrain_indices  # noqa: F401
+from .api import editraster, read_changes  # noqa: F401
+from .api import catchoutlets, read_lines, streamnet_net, write_lines  # noqa: F401
 
 __version__ = "0.1.0"

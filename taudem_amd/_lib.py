@@ -295,6 +295,8 @@ _STREAMNET_SIGNATURES = {
     # ctx, comm, p, src, nx, ny_local, p_nodata, src_nodata, part, links, first_cell, single_watershed, ord, w, stats
     "tdx_streamnet_label_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I16, C.c_int32, _P, _P, _I64, _INT, _P, _P, _P]),
     "tdx_streamnet_write_text": (C.c_int, [_P, C.c_char_p, C.c_char_p]),
+    "tdx_streamnet_net_rows": (C.c_int, [_P, _P, _I64, _I64, C.c_int, _I64, _P, _P, _P, _P]),
+    "tdx_streamnet_net_write": (C.c_int, [_P, C.c_int, C.c_char_p]),
     "tdx_tool_streamnet": (C.c_int, [C.c_char_p] * 9 + [C.c_int, C.c_int] + [C.c_char_p] * 3 + [C.c_long, C.c_long, C.c_int]),
 }
 STREAMNET_SYMBOLS = tuple(_STREAMNET_SIGNATURES)
@@ -373,6 +375,39 @@ _INDICES_SIGNATURES = {
 INDICES_SYMBOLS = tuple(_INDICES_SIGNATURES)
 TERRAIN_OUTPUTS = ("twi", "sa", "sar")   # the outputs of tdx_terrain_indices, in the header's order
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_editraster.h declares, the eighth extension header
+# EditRaster: ctx, in, nx, ny, [row0,] in_nodata, cols, rows, vals, n, out, stats
+_EDITRASTER_SIGNATURES = {
+    "tdx_editraster": (C.c_int, [_P, _P, _I64, _I64, _I16, _P, _P, _P, _I64, _P, _P]),
+    "tdx_editraster_dev": (C.c_int, [_P, _P, _I64, _I64, _I16, _P, _P, _P, _I64, _P, _P]),
+    "tdx_editraster_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I16, _P, _P, _P, _I64, _P, _P]),
+    "tdx_editraster_read_changes": (C.c_int, [C.c_char_p, _I64, _P, _P, _P, _P]),
+    "tdx_tool_editraster": (C.c_int, [C.c_char_p] * 3),
+}
+EDITRASTER_SYMBOLS = tuple(_EDITRASTER_SIGNATURES)
+
+# name -> (restype, argtypes): the symbols include/taudem_amd_catchoutlets.h declares, the ninth extension header (host code only)
+_CATCHOUTLETS_SIGNATURES = {
+    "tdx_lines_write": (C.c_int, [C.c_char_p, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "tdx_lines_read": (C.c_int, [C.c_char_p, _P]),
+    "tdx_line_layer_count": (_I64, [_P, _P, _P]),
+    "tdx_line_layer_vertices": (None, [_P, _P, _P, _P]),
+    "tdx_line_layer_field": (C.c_char_p, [_P, _I32, _P, _P, _P]),
+    "tdx_line_layer_value": (C.c_char_p, [_P, _I64, _I32]),
+    "tdx_line_layer_free": (None, [_P]),
+    # pfile, 4 int32 columns, 7 float64 columns, n_links, mindist, gwstartno, minarea, capacity, out_row, out_x, out_y, out_doutend, out_id, n_out
+    "tdx_catchoutlets": (C.c_int, [C.c_char_p] + [_P] * 11 + [_I64, C.c_double, _I32, C.c_double, _I64] + [_P] * 6),
+    "tdx_tool_catchoutlets": (C.c_int, [C.c_char_p] * 5 + [C.c_double, C.c_int, C.c_double]),
+}
+CATCHOUTLETS_SYMBOLS = tuple(_CATCHOUTLETS_SIGNATURES)
+# the fields of the stream network layer in the reference's order: name, type (0 Integer, 1 Real), width, decimals (src/streamnet.cpp:163-239); the Real
+# ones are, in this order, the nine columns of tdx_streamnet_net_rows
+NET_FIELDS = (("LINKNO", 0, 6, 0), ("DSLINKNO", 0, 6, 0), ("USLINKNO1", 0, 6, 0), ("USLINKNO2", 0, 6, 0), ("DSNODEID", 0, 12, 0), ("strmOrder", 0, 6, 0),
+              ("Length", 1, 16, 1), ("Magnitude", 0, 6, 0), ("DSContArea", 1, 16, 1), ("strmDrop", 1, 16, 2), ("Slope", 1, 16, 12), ("StraightL", 1, 16, 1),
+              ("USContArea", 1, 16, 1), ("WSNO", 0, 6, 0), ("DOUTEND", 1, 16, 1), ("DOUTSTART", 1, 16, 1), ("DOUTMID", 1, 16, 1))
+NET_TREE_COLUMN = {"LINKNO": 0, "DSLINKNO": 3, "USLINKNO1": 4, "USLINKNO2": 5, "DSNODEID": 7, "strmOrder": 6, "Magnitude": 8, "WSNO": 0}   # of the -tree file
+CATCHOUTLETS_FIELDS = (("LINKNO", 0, 6, 0), ("DSLINKNO", 0, 6, 0), ("USLINKNO1", 0, 6, 0), ("USLINKNO2", 0, 6, 0), ("DOUTEND", 1, 16, 1), ("Id", 0, 10, 0))
+
 _lib = None
 
 
@@ -397,7 +432,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
-                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES}.items():
+                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES, **_EDITRASTER_SIGNATURES, **_CATCHOUTLETS_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

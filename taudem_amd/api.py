@@ -7,6 +7,7 @@ dtypes and nodata conventions are the reference's (include/taudem_amd.h).
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -182,8 +183,10 @@ class _StreamNetStage:
     """Context.streamnet; its entry points are those of include/taudem_amd_streamnet.h."""
 
     def streamnet(self, p, src, fel, ad8, outlets=None, single_watershed=False, *, dx=1.0, dy=1.0, geotransform=None, nodata=int(P_NODATA),
-                  src_nodata=int(P_NODATA), out=None, phases=False, stats=False):
+                  src_nodata=int(P_NODATA), out=None, phases=False, stats=False, net=None, geographic=False):
         """ord, w, tree, coord = streamnet(p, src, fel, ad8)  (src/streamnet.cpp:372): the stream network of the stream raster src on the D8 directions p.
+        net=path also writes the stream network line layer (the reference's -net: a shapefile or GeoJSON by the extension, 17 fields per link) from the
+        links once the call has returned them; geographic: the raster's flag, which decides how the layer's lengths are measured.
 
         ord int16: the Strahler order on the stream cells (src not nodata, src > 0, p not nodata), 0 elsewhere.  w int32: the id of the link that
         drains each cell, the catchment grid catchhydrogeo and inundepth take; -2147483647 where no stream is reached; single_watershed (-sw): 1
@@ -194,7 +197,7 @@ class _StreamNetStage:
         link there.  geotransform: GDAL's six numbers of the raster file (default: left edge 0, top edge 0, cells of dx x dy of the middle row).
         tree and coord are numpy arrays on the host for either side; phases=True also returns, after coord, the wall milliseconds of the call's
         phases as a dict (setup, length, compact, links, scatter, label, total).  out: (ord, w)."""
-        return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases), stats)
+        return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net, geographic), stats)
 
 
 class _OutletToolsStage:
@@ -273,7 +276,18 @@ class _TerrainIndexStage:
         return _ret(_setregion(_Call(self), p, gw, region_id, nodata, gw_nodata, out), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage):
+class _EditRasterStage:
+    """Context.editraster; its entry points are those of include/taudem_amd_editraster.h."""
+
+    def editraster(self, raster, cols, rows, vals, out=None, *, nodata=int(P_NODATA), stats=False):
+        """new = editraster(raster, cols, rows, vals)  (src/EditRaster.cpp:69): the int16 raster with its nodata cells as -32768 and cell (rows[k], cols[k])
+        set to vals[k] for every k; a change off the raster is skipped, the last change of a cell holds, a value no int16 holds raises TdxError.
+
+        out=raster edits a tensor (or a numpy array) in place."""
+        return _ret(_editraster(_Call(self), raster, cols, rows, vals, nodata, out), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage, _EditRasterStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -810,6 +824,34 @@ def _setregion(f, p, gw, region_id, nodata, gw_nodata, out):
     return o, f.call("tdx_setregion", pp, pg, f.nx, f.ny, int(nodata), int(gw_nodata), int(region_id), po)
 
 
+def _editraster(f, raster, cols, rows, vals, nodata, out, row0=None):
+    """row0: a strip's first owned row in the raster (rows are then GLOBAL rows); None for a Context."""
+    pi = f.raster(raster, np.int16, "raster")
+    cx, cy, cv = (_flat(a, np.int64) for a in (cols, rows, vals))
+    if not cx.shape == cy.shape == cv.shape:
+        raise ValueError("cols, rows, vals: need three equal-length 1-D arrays")
+    lim = np.iinfo(np.int32)
+    # cells beyond int32 are off every raster; values beyond it are for the library to refuse: both keep that meaning after the clip
+    cx, cy, cv = (np.ascontiguousarray(np.clip(a, lim.min, lim.max).astype(np.int32)) for a in (cx, cy, cv))
+    f.keep += [cx, cy, cv]
+    n = int(cx.size)
+    o, po = f.out(out, np.int16, "out")
+    where = (f.nx, f.ny) if row0 is None else (f.nx, f.ny, int(row0))
+    return o, f.call("tdx_editraster", pi, *where, int(nodata), _v(cx) if n else None, _v(cy) if n else None, _v(cv) if n else None, n, po)
+
+
+def read_changes(path):
+    """x, y, vals (float64, float64, int32) of an EditRaster change file: the first line is skipped, then "x,y,value" records up to the first one that does
+    not scan (src/EditRaster.cpp:124-133).  TdxError: the file cannot be opened, or a value is outside -32768 .. 32767.  No GPU is touched."""
+    lib = _lib.load()
+    n = C.c_int64(0)
+    check(lib.tdx_editraster_read_changes(os.fsencode(path), 0, None, None, None, C.byref(n)))
+    x, y, v = np.zeros(n.value, np.float64), np.zeros(n.value, np.float64), np.zeros(n.value, np.int32)
+    if n.value:
+        check(lib.tdx_editraster_read_changes(os.fsencode(path), n.value, _v(x), _v(y), _v(v), C.byref(n)))
+    return x, y, v
+
+
 def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh, steptype, dx, dy, nodata, ssa_nodata, grids):
     """Context: (thresh, n1, n2, sums, length, total_area, table, optimum[, order, elevout], stats).  A strip: its own (thresh, n1, n2, sums, length,
     outlet_term[, order, elevout], stats) - outlet_term float32 per outlet, ad8 of the strip's terminal outlets and 0 elsewhere."""
@@ -844,7 +886,7 @@ def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh,
     return (thresh, n1, n2, sums, length, scal[0], text.value.decode(), scal[1] if found[0] else None) + extra + (st,)
 
 
-def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases):
+def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net=None, geographic=False):
     pp = f.raster(p, np.int16, "p")
     ps = f.raster(src, np.int32, "src")
     pf = f.raster(fel, np.float32, "fel")
@@ -872,6 +914,8 @@ def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransf
                 _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), int(bool(single_watershed)), po, pw, C.byref(links))
     try:
         tree, coord, ms = _links_rows(lib, links, phases=True)
+        if net is not None:
+            check(lib.tdx_streamnet_net_write(links, int(bool(geographic)), os.fsencode(net)))
     finally:
         lib.tdx_streamnet_links_free(links)
     res = (ordg, w, tree, coord)
@@ -933,6 +977,10 @@ class StreamNetLinks:
         check(self._lib.tdx_streamnet_links_build(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), dxa, dya, _v(g4), _v(ox) if ox.size else None,
                                                   _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), C.byref(self.handle)))
         self.tree, self.coord = _links_rows(self._lib, self.handle)
+
+    def write_net(self, path, geographic=False):
+        """The stream network line layer of the links (tdx_streamnet_net_write): the file Context.streamnet(..., net=path) writes."""
+        check(self._lib.tdx_streamnet_net_write(self.handle, int(bool(geographic)), os.fsencode(path)))
 
     def close(self):
         if getattr(self, "handle", None):
@@ -1086,12 +1134,19 @@ def write_points(path, x, y, fields=None):
     xs, ys = _flat(x, np.float64), _flat(y, np.float64)
     if xs.shape != ys.shape:
         raise ValueError("x and y: need equal-length arrays")
-    n, fields = int(xs.size), dict(fields or {})
+    n = int(xs.size)
+    k, c_names, c_types, c_cols, keep = _field_columns(fields, n)
+    check(_lib.load().tdx_points_write(str(path).encode(), _v(xs) if n else None, _v(ys) if n else None, n, k, C.cast(c_names, C.c_void_p) if k else None,
+                                       _v(c_types) if k else None, C.cast(c_cols, C.c_void_p) if k else None))
+
+
+def _field_columns(fields, n):
+    """(count, names, types, columns, what keeps them alive) of {name: values} for tdx_points_write / tdx_lines_write"""
     names, types, cols, keep = [], [], [], []
-    for name, vals in fields.items():
+    for name, vals in dict(fields or {}).items():
         a = np.asarray(vals)
         if a.shape != (n,):
-            raise ValueError(f"field {name}: need one value per point")
+            raise ValueError(f"field {name}: need one value per feature")
         if a.dtype.kind in "iub":
             if a.size and (a.min() < -2**31 or a.max() > 2**31 - 1):
                 raise ValueError(f"field {name}: integers beyond 32 bits")
@@ -1106,9 +1161,118 @@ def write_points(path, x, y, fields=None):
             ptr = C.cast(a, C.c_void_p).value
         names.append(str(name).encode()); types.append(t); cols.append(ptr); keep.append(a)
     k = len(names)
-    c_names, c_types, c_cols = (C.c_char_p * max(k, 1))(*names), np.array(types + [0], np.int32), (C.c_void_p * max(k, 1))(*cols)
-    check(_lib.load().tdx_points_write(str(path).encode(), _v(xs) if n else None, _v(ys) if n else None, n, k, C.cast(c_names, C.c_void_p) if k else None,
-                                       _v(c_types) if k else None, C.cast(c_cols, C.c_void_p) if k else None))
+    return k, (C.c_char_p * max(k, 1))(*names), np.array(types + [0], np.int32), (C.c_void_p * max(k, 1))(*cols), keep
+
+
+def _line_arrays(lines):
+    """first (n + 1 offsets), x, y of a list of (vertices, 2) arrays"""
+    parts = [np.asarray(v, np.float64).reshape(-1, 2) for v in lines]
+    first = np.zeros(len(parts) + 1, np.int64)
+    if parts:
+        first[1:] = np.cumsum([len(v) for v in parts])
+    xy = np.concatenate(parts, axis=0) if parts else np.zeros((0, 2), np.float64)
+    return first, np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+
+
+def write_lines(path, lines, fields=None, widths=None):
+    """A line layer at `path`: an ESRI shapefile (.shp of PolyLines, one part each, with its .shx and .dbf) or GeoJSON (LineString features) by the
+    extension; any other raises.  lines: one (vertices, 2) array of x, y per feature - a single vertex is legal; fields: {name: values} as for
+    write_points; widths: {name: (width, decimals)} for the .dbf columns (streamnet_net's fields come with theirs: api.NET_WIDTHS).  Host code: needs
+    no GPU.  No .prj is written."""
+    first, xs, ys = _line_arrays(lines)
+    n = len(first) - 1
+    k, c_names, c_types, c_cols, keep = _field_columns(fields, n)
+    wd = np.zeros((2, max(k, 1)), np.int32)
+    for j, name in enumerate(dict(fields or {})):
+        wd[:, j] = (widths or {}).get(name, (0, 0))
+    check(_lib.load().tdx_lines_write(str(path).encode(), _v(first), _v(xs) if xs.size else None, _v(ys) if xs.size else None, n, k,
+                                      C.cast(c_names, C.c_void_p) if k else None, _v(c_types) if k else None, _v(wd[0]) if k else None, _v(wd[1]) if k else None,
+                                      C.cast(c_cols, C.c_void_p) if k else None))
+
+
+def read_lines(path):
+    """lines, fields of a line layer (shapefile PolyLine / PolyLineZ / PolyLineM, or GeoJSON LineString features): one (vertices, 2) float64 array per
+    feature, and {name: values} with int32 arrays for Integer fields, float64 for Real ones (a null is 0), lists of str for the rest.  Host code."""
+    lib = _lib.load()
+    h = C.c_void_p()
+    check(lib.tdx_lines_read(str(path).encode(), C.byref(h)))
+    try:
+        nv, nf = C.c_int64(0), C.c_int32(0)
+        n = int(lib.tdx_line_layer_count(h, C.byref(nv), C.byref(nf)))
+        first, x, y = np.zeros(n + 1, np.int64), np.zeros(nv.value, np.float64), np.zeros(nv.value, np.float64)
+        lib.tdx_line_layer_vertices(h, _v(first), _v(x), _v(y))
+        lines = [np.stack([x[a:b], y[a:b]], axis=1) for a, b in zip(first[:-1], first[1:])]
+        fields = {}
+        for k in range(nf.value):
+            t = C.c_int32(0)
+            name = lib.tdx_line_layer_field(h, k, C.byref(t), None, None).decode()
+            text = [lib.tdx_line_layer_value(h, i, k).decode("utf-8", "replace").strip(" \0") for i in range(n)]
+            if t.value == 2:
+                fields[name] = text
+            else:
+                fields[name] = np.array([float(v) if v else 0.0 for v in text], np.float64)
+                if t.value == 0:
+                    fields[name] = fields[name].astype(np.int32)
+        return lines, fields
+    finally:
+        lib.tdx_line_layer_free(h)
+
+
+NET_WIDTHS = {name: (w, d) for name, _, w, d in _lib.NET_FIELDS}
+
+
+def streamnet_net(tree, coord, geographic=False):
+    """fields, lines = the stream network layer of Context.streamnet's tree and coord rows (reachshape(), src/streamnet.cpp:244-365): the 17 fields of
+    the reference's -net layer as {name: array} in its order (int32 / float64), and per link its (vertices, 2) array, REVERSED so that vertex 0 is the
+    downstream end; a link of one point is a line of one vertex.  geographic: the raster's flag (every segment's length is then tiffIO::geotoLength's).
+    write_lines(path, lines, fields, NET_WIDTHS) writes what tdx_streamnet_net_write does.  Host code: needs no GPU."""
+    tree = np.ascontiguousarray(np.asarray(tree, np.int64).reshape(-1, 9))
+    coord = np.ascontiguousarray(np.asarray(coord, np.float64).reshape(-1, 5))
+    nl = len(tree)
+    nv = int((tree[:, 2] - tree[:, 1] + 1).sum()) if nl else 0
+    real, first = np.zeros((nl, 9), np.float64), np.zeros(nl + 1, np.int64)
+    x, y = np.zeros(max(nv, 0), np.float64), np.zeros(max(nv, 0), np.float64)
+    check(_lib.load().tdx_streamnet_net_rows(_v(tree), _v(coord), nl, len(coord), int(bool(geographic)), nv, _v(real), _v(first), _v(x), _v(y)))
+    fields, r = {}, 0
+    for name, t, _, _ in _lib.NET_FIELDS:
+        if t == 0:
+            fields[name] = tree[:, _lib.NET_TREE_COLUMN[name]].astype(np.int32)
+        else:
+            fields[name] = real[:, r].copy()
+            r += 1
+    return fields, [np.stack([x[a:b], y[a:b]], axis=1) for a, b in zip(first[:-1], first[1:])]
+
+
+def catchoutlets(pfile, fields, lines, mindist=0.0, gwstartno=1, minarea=0.0):
+    """x, y, fields = CatchOutlets (src/CatchOutlets.cpp:126) on the stream network (fields, lines) - streamnet_net's or read_lines' - and the D8 flow
+    direction FILE pfile, of which the header and one cell per outlet link are read: the outlets in the reference's order with the fields LINKNO,
+    DSLINKNO, USLINKNO1, USLINKNO2, DOUTEND and Id of its point layer (write_points(path, x, y, fields) writes it).  Vertex 0 of a line is the link's
+    downstream end.  Host code: no context is created and no GPU touched."""
+    need = ("LINKNO", "DSLINKNO", "USLINKNO1", "USLINKNO2", "DOUTEND", "DOUTSTART", "USContArea")
+    for name in need:
+        if name not in fields:
+            raise ValueError(f"the stream network has no field {name}")
+    n = len(lines)
+    ints = [np.ascontiguousarray(np.asarray(fields[k]), np.int32) for k in need[:4]]
+    reals = [np.ascontiguousarray(np.asarray(fields[k]), np.float64) for k in need[4:]]
+    if any(a.shape != (n,) for a in ints + reals):
+        raise ValueError("need one value per line in every field")
+    ends = np.zeros((4, n), np.float64)
+    for i, v in enumerate(lines):
+        v = np.asarray(v, np.float64).reshape(-1, 2)
+        if len(v):
+            ends[:, i] = (v[0, 0], v[0, 1], v[-1, 0], v[-1, 1])
+        elif ints[1][i] < 0 or ints[2][i] >= 0 or ints[3][i] >= 0:
+            raise ValueError(f"line {i} has no vertex")
+    cap = 2 * n + 2
+    row, ox, oy, od, oid, nout = np.zeros(cap, np.int64), np.zeros(cap), np.zeros(cap), np.zeros(cap), np.zeros(cap, np.int32), C.c_int64(0)
+    check(_lib.load().tdx_catchoutlets(os.fsencode(pfile), *[_v(a) for a in ints], *[_v(a) for a in reals], *[_v(np.ascontiguousarray(e)) for e in ends], n,
+                                       float(mindist), int(gwstartno), float(minarea), cap, _v(row), _v(ox), _v(oy), _v(od), _v(oid), C.byref(nout)))
+    m = nout.value
+    row = row[:m]
+    out = {k: a[row] for k, a in zip(need[:4], ints)}
+    out["DOUTEND"], out["Id"] = od[:m].copy(), oid[:m].copy()
+    return ox[:m].copy(), oy[:m].copy(), out
 
 
 def streamnet_text(tree, coord):
@@ -1167,6 +1331,12 @@ def setregion(p, gw, region_id=1, device=0, **kw):
     """Context(device).setregion(...) for a single call."""
     with Context(device) as ctx:
         return ctx.setregion(p, gw, region_id, **kw)
+
+
+def editraster(raster, cols, rows, vals, device=0, **kw):
+    """Context(device).editraster(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.editraster(raster, cols, rows, vals, **kw)
 
 
 def sinmapsi(slp, sca, cal, regions, rminter, rmaxter, g=9.81, rhow=1000.0, device=0, **kw):

@@ -39,6 +39,8 @@
 //   tdx_tool_slopearearatio      <- atanbgrid()           src/SlopeAreaRatio.cpp:49-148
 //   tdx_tool_lengtharea          <- lengtharea()          src/LengthArea.cpp:51-149
 //   tdx_tool_setregion           <- setregion()           src/SetRegion.cpp:78-191
+//   tdx_tool_editraster          <- editraster()          src/EditRaster.cpp:69-168
+//   tdx_tool_catchoutlets        <- catchoutlets()        src/CatchOutlets.cpp:126-443   (host code: no GPU)
 //   tdx_tool_moveoutletstostrm   <- outletstosrc()        src/MoveOutletsToStrm.cpp:80-914
 //   tdx_tool_connectdown         <- connectdown()         src/ConnectDown.cpp:79-893
 #include <atomic>
@@ -56,7 +58,9 @@
 #include <vector>
 
 #include "context.hpp"
+#include "catchoutlets.hpp"
 #include "dropan_table.hpp"
+#include "editraster_changes.hpp"
 #include "geotiff.hpp"
 #include "hand_tables.hpp"
 #include "outlets.hpp"
@@ -870,8 +874,9 @@ int tdx_tool_d8hdisttostrm(const char* pfile, const char* srcfile, const char* d
 }
 
 // StreamNet (src/streamnet.cpp:372-1508): reads src, p, ad8, fel in the reference's order with its own words for a raster that does not match (it
-// aborts with 4), then the outlets.  -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  The -net layer is not written: every
-// one of its fields is a host function of the tree and coord rows (reachshape, :244-365), and there is no OGR writer here to hold one against.
+// aborts with 4), then the outlets.  -lyrname / -lyrno are accepted and ignored, as for the other outlet tools.  The -net flag is still refused here;
+// the layer itself - every one of its fields is a host function of the tree and coord rows (reachshape, :244-365) - is written by
+// tdx_streamnet_net_write from the links of tdx_streamnet.
 int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfile, const char* ad8file, const char* elevfile, const char* treefile,
                        const char* coordfile, const char* outletsds, const char* /*lyrname*/, int /*uselayername*/, int /*lyrno*/, const char* wfile,
                        const char* streamnetsrc, const char* streamnetlyr, long useOutlets, long ordert, int verbose) {
@@ -1783,6 +1788,124 @@ int tdx_tool_setregion(const char* fdrfile, const char* regiongwfile, const char
     if (!ok) return t.rc;
     t.output(newfile, out, gw, -2147483647.0);
     return t.finish("Compute time", "setregion", Footer::ComputeOnly);
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int tdx_editraster_read_changes(const char* path, int64_t capacity, double* x, double* y, int32_t* vals, int64_t* n) {
+    if (!path || !n || capacity < 0 || (capacity > 0 && (!x || !y || !vals))) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_editraster_read_changes: bad argument");
+    std::vector<tdx::RasterChange> ch;
+    const int rc = tdx::read_raster_changes(path, ch);
+    *n = int64_t(ch.size());
+    if (rc == tdx::CHANGES_NO_FILE) return tdx_fail(nullptr, TDX_ERR_FILE, std::string("tdx_editraster_read_changes: cannot open ") + path);
+    for (int64_t k = 0; k < std::min<int64_t>(*n, capacity); k++) { x[k] = ch[size_t(k)].x; y[k] = ch[size_t(k)].y; vals[k] = ch[size_t(k)].val; }
+    if (rc == tdx::CHANGES_RANGE)
+        return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_editraster_read_changes: record " + std::to_string(*n) + " of " + path + " holds a value outside -32768 .. 32767");
+    return TDX_OK;
+}
+
+// The change file is read once the raster is: the reference opens it after its copy pass (src/EditRaster.cpp:124) and prints one line per change it applies
+// while it applies them; here the lines come before the compute step, in the same place of the output.  A change file that cannot be opened ends the
+// reference in a null FILE*; a value no short holds overwrites its stack: both are refused, with nothing written.
+int tdx_tool_editraster(const char* rasterfile, const char* newfile, const char* changefile) {
+    if (!rasterfile || !newfile || !changefile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_editraster: bad argument");
+    ToolRun t("Editraster");
+    Raster in;
+    t.input(rasterfile, I16, in);
+    if (t.rc == TDX_OK) { fprintf(stderr, "Time estimate not available.\n"); fflush(stderr); }
+    if (!t.read_done()) return t.rc;
+    const int16_t nd = (int16_t)in.info.nodata;
+    std::vector<tdx::RasterChange> ch;
+    const int crc = tdx::read_raster_changes(changefile, ch);
+    if (crc == tdx::CHANGES_NO_FILE) {
+        printf("Error opening file %s.\n", changefile);
+        fflush(stdout);
+        return tdx_fail(nullptr, TDX_ERR_FILE, std::string("tdx_tool_editraster: cannot open ") + changefile);
+    }
+    if (crc == tdx::CHANGES_RANGE) {
+        fprintf(stderr, "taudem_amd: record %zu of %s holds a value outside -32768 .. 32767\n", ch.size(), changefile);
+        return tdx_fail(nullptr, TDX_ERR_ARG, std::string("tdx_tool_editraster: a value outside -32768 .. 32767 in ") + changefile);
+    }
+    std::vector<int32_t> cols, rows, vals;
+    for (const tdx::RasterChange& c : ch) {
+        int gx, gy;
+        tdx::geo_to_global_xy(c.x, c.y, in.info.xleftedge, in.info.ytopedge, in.info.dlon, in.info.dlat, gx, gy);
+        if (gx < 0 || gx >= in.info.nx || gy < 0 || gy >= in.info.ny) continue;   // rasterData->isInPartition
+        printf("Process: %d changing %lf, %lf, %d\n", 0, c.x, c.y, c.val);
+        cols.push_back(gx); rows.push_back(gy); vals.push_back(c.val);
+    }
+    fflush(stdout);
+    std::vector<int16_t> out(t.cells());
+    const int64_t n = int64_t(cols.size());
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_editraster(c, in.s.data(), in.info.nx, in.info.ny, nd, cols.data(), rows.data(), vals.data(), n, out.data(), s); },
+        [&](RankJob& j, tdx_stats* s) {
+            const int16_t* d_in = j.in(in.s);
+            int16_t* d_out = j.out(out);
+            if (j.error) return j.error;
+            return tdx_editraster_strip(j.ctx, j.comm, d_in, j.nx, j.nyl, j.y0, nd, cols.data(), rows.data(), vals.data(), n, d_out, s);
+        });
+    if (!ok) return t.rc;
+    t.output(newfile, out, in, -32768.0);
+    return t.finish("Compute time", "editraster", Footer::ComputeLine);
+}
+
+// CatchOutlets is host code from end to end: no context is created and no GPU touched.  Of p the header is read here (for the reference's words about
+// it) and one cell per outlet link in tdx_catchoutlets; the reference reads the whole raster.  It prints no times (src/CatchOutlets.cpp:126-443).
+int tdx_tool_catchoutlets(const char* pfile, const char* streamnetsrc, const char* treefile, const char* coordfile, const char* outletsdatasrc, double mindist,
+                          int gwstartno, double minarea) {
+    if (!pfile || !outletsdatasrc) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_catchoutlets: bad argument");
+    const bool net = streamnetsrc && *streamnetsrc, tree = treefile && *treefile, coord = coordfile && *coordfile;
+    if (net == (tree || coord) || tree != coord) {
+        fprintf(stderr, "taudem_amd: catchoutlets takes the stream network either as -net <line layer> or as -tree <file> -coord <file>\n");
+        return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_catchoutlets: give -net, or -tree and -coord");
+    }
+    if (tdx::layer_kind(outletsdatasrc) == tdx::LayerKind::None) return refuse_layer("catchoutlets", outletsdatasrc);
+    if (net && tdx::layer_kind(streamnetsrc) == tdx::LayerKind::None) {
+        fprintf(stderr, "taudem_amd: catchoutlets cannot read %s: %s\n", streamnetsrc, tdx::kLineLayerKindsMessage);
+        return tdx_fail(nullptr, TDX_ERR_ARG, std::string("catchoutlets: unsupported input ") + streamnetsrc);
+    }
+    printf("Catchment Outlets version %s\n", TDVERSION);
+    fflush(stdout);
+    // tiffIO p(pfile, SHORT_TYPE), the time estimate and CreateNewPartition (:146-165)
+    tdx::TiffReader rd;
+    if (!rd.open(pfile)) { printf("Error opening file %s.\n", pfile); fflush(stdout); return tdx_fail(nullptr, TDX_ERR_FILE, rd.error()); }
+    const tdx::RasterInfo& ri = rd.info();
+    printf("Input file %s has %s coordinate system.\n", pfile, ri.geographic ? "geographic" : "projected");
+    const float timeestimate = float((2e-7 * double(ri.nx) * double(ri.ny) / pow(1.0, 0.65)) / 60 + 1);
+    fprintf(stderr, "This run may take on the order of %.0f minutes to complete.\n", timeestimate);
+    fprintf(stderr, "This estimate is very approximate. \nRun time is highly uncertain as it depends on the complexity of the input data \nand speed and memory of the computer. This estimate is based on our testing on \na dual quad core Dell Xeon E5405 2.0GHz PC with 16GB RAM.\n");
+    fflush(stderr);
+    printf("Nodata value input to create partition from file: %lf\nNodata value recast to int16_t used in partition raster: %d\n", ri.nodata, (int16_t)ri.nodata);
+    fflush(stdout);
+    std::vector<tdx::NetLink> links;
+    std::string err;
+    if (net) {
+        tdx::LineLayer L;
+        if (!tdx::read_line_layer(streamnetsrc, L, err)) { printf("Error opening file %s.\n", streamnetsrc); fflush(stdout); return tdx_fail(nullptr, TDX_ERR_FILE, err); }
+        if (!tdx::links_from_layer(L, links, err)) { fprintf(stderr, "taudem_amd: %s: %s\n", streamnetsrc, err.c_str()); return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_catchoutlets: " + err); }
+    } else if (!tdx::links_from_text(treefile, coordfile, links, err)) {
+        const bool missing = err.rfind("cannot open", 0) == 0;
+        if (missing) { printf("Error opening file %s.\n", err.substr(12).c_str()); fflush(stdout); }
+        else fprintf(stderr, "taudem_amd: %s\n", err.c_str());
+        return tdx_fail(nullptr, missing ? TDX_ERR_FILE : TDX_ERR_ARG, "tdx_tool_catchoutlets: " + err);
+    }
+    tdx::FlowGrid g;
+    g.nx = ri.nx; g.ny = ri.ny; g.xleftedge = ri.xleftedge; g.ytopedge = ri.ytopedge; g.dlon = ri.dlon; g.dlat = ri.dlat;
+    g.p_at = [&](int64_t col, int64_t row, int16_t& dir) { return rd.read_window(col, row, 1, 1, I16, &dir); };
+    std::vector<tdx::CatchOutlet> outs;
+    if (!tdx::catch_outlets(links, g, mindist, gwstartno, minarea, outs, err)) {
+        const bool io = err.rfind("cannot read", 0) == 0;
+        if (io) { printf("Error opening file %s.\n", pfile); fflush(stdout); err += ": " + rd.error(); }
+        else fprintf(stderr, "taudem_amd: %s\n", err.c_str());
+        return tdx_fail(nullptr, io ? TDX_ERR_FILE : TDX_ERR_ARG, "tdx_tool_catchoutlets: " + err);
+    }
+    tdx::PointLayer P;
+    tdx::catch_outlets_layer(links, outs, P);
+    if (!tdx::write_point_layer(outletsdatasrc, P, err)) { printf("Error opening file %s.\n", outletsdatasrc); fflush(stdout); return tdx_fail(nullptr, TDX_ERR_FILE, err); }
+    return 0;
 }
 
 }  // extern "C"

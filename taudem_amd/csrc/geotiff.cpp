@@ -14,32 +14,14 @@
 #include <map>
 #include <thread>
 
+#include "geo_length.hpp"
+
 namespace tdx {
 
 // ----------------------------------------------------------------------------------------------
 // RasterInfo: derived quantities exactly as tiffIO::tiffIO computes them.
 // ----------------------------------------------------------------------------------------------
-namespace {
-// WGS84 constants and the truncated PI the reference uses (src/tiffIO.h:94-96, src/commonLib.h:76)
-const double kPI = 3.14159265359;
-const double kElipA = 6378137.000;
-const double kElipB = 6356752.314;
-const double kBoa = kElipB / kElipA;
-
-// src/tiffIO.cpp:434-445 (geotoLength)
-void geo_to_length(double dlon, double dlat, double lat, double* xyc) {
-    double ds2, beta, dbeta;
-    dlat = dlat * kPI / 180.;
-    dlon = dlon * kPI / 180.;
-    lat = lat * kPI / 180.;
-    beta = atan(kBoa * tan(lat));
-    dbeta = dlat * kBoa * (cos(beta) / cos(lat)) * (cos(beta) / cos(lat));
-    ds2 = (pow(kElipA * sin(beta), 2) + pow(kElipB * cos(beta), 2)) * pow(dbeta, 2);
-    xyc[0] = kElipA * cos(beta) * std::fabs(dlon);
-    xyc[1] = double(sqrt(double(ds2)));
-}
-}  // namespace
-
+// (geo_to_length: src/tiffIO.cpp:434-445, geo_length.hpp)
 void RasterInfo::derive_cell_sizes() {
     dlon = std::fabs(gt[1]);
     dlat = std::fabs(gt[5]);

@@ -76,6 +76,8 @@ int lengtharea(char* plenfile, char* ad8file, char* ssfile, float* p)
 { return tdx_tool_lengtharea(plenfile, ad8file, ssfile, p); }
 int setregion(char* fdrfile, char* regiongwfile, char* newfile, int32_t regionID)
 { return tdx_tool_setregion(fdrfile, regiongwfile, newfile, regionID); }
+int editraster(char* rasterfile, char* newfile, char* changefile)
+{ return tdx_tool_editraster(rasterfile, newfile, changefile); }
 int threshold(char* ssafile, char* srcfile, char* maskfile, float thresh, int usemask)
 { return tdx_tool_threshold(ssafile, srcfile, maskfile, thresh, usemask); }
 

@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
         else if (a.is("-v")) { a.flag(); verbose = 1; }
         else usage(argv[0]);
     }
+    // (the layer itself exists one level down: tdx_streamnet_net_write makes it from the links of tdx_streamnet, and catchoutlets takes -tree / -coord)
     if (!netfile.empty() || !netlyr.empty()) {
         fprintf(stderr, "streamnet: -net / -netlyr are not supported: the stream network layer is not written; its fields follow from the -tree and -coord files\n");
         return 2;

@@ -13,6 +13,7 @@
 
 namespace tdx {
 const char* const kLayerKindsMessage = "supported point layers: ESRI shapefile (.shp) and GeoJSON (.json, .geojson)";
+const char* const kLineLayerKindsMessage = "supported line layers: ESRI shapefile (.shp) and GeoJSON (.json, .geojson)";
 
 namespace {
 std::string lower_ext(const std::string& p) {
@@ -50,22 +51,26 @@ FieldType type_of_dbf(char t, int decimals) { return (t == 'N' || t == 'F') ? (d
 int default_width(FieldType t) { return t == FieldType::Integer ? 9 : t == FieldType::Real ? 24 : 80; }
 
 // ---- .shp / .shx / .dbf
-std::string shape_header(uint32_t words, const PointLayer& L) {
+// xmin, ymin, xmax, ymax of a run of vertices, grown over calls; zeros while no vertex has been seen
+struct Box {
+    double b[4] = {0, 0, 0, 0};
+    bool any = false;
+    void add(const std::vector<double>& x, const std::vector<double>& y) {
+        for (size_t i = 0; i < x.size(); i++) {
+            if (!any) { b[0] = b[2] = x[i]; b[1] = b[3] = y[i]; any = true; continue; }
+            b[0] = std::min(b[0], x[i]); b[2] = std::max(b[2], x[i]);
+            b[1] = std::min(b[1], y[i]); b[3] = std::max(b[3], y[i]);
+        }
+    }
+};
+std::string shape_header(uint32_t words, uint32_t shape_type, const Box& box) {
     std::string h;
     put_be32(h, 9994);
     for (int i = 0; i < 5; i++) put_be32(h, 0);
     put_be32(h, words);
     put_le32(h, 1000);
-    put_le32(h, 1);   // Point
-    double box[4] = {0, 0, 0, 0};
-    if (!L.x.empty()) {
-        box[0] = box[2] = L.x[0]; box[1] = box[3] = L.y[0];
-        for (size_t i = 1; i < L.x.size(); i++) {
-            box[0] = std::min(box[0], L.x[i]); box[2] = std::max(box[2], L.x[i]);
-            box[1] = std::min(box[1], L.y[i]); box[3] = std::max(box[3], L.y[i]);
-        }
-    }
-    for (double b : box) put_le64f(h, b);
+    put_le32(h, shape_type);
+    for (double b : box.b) put_le64f(h, b);
     for (int i = 0; i < 4; i++) put_le64f(h, 0.0);   // z and m ranges
     return h;
 }
@@ -85,15 +90,8 @@ std::string dbf_cell(const LayerField& f, int width, int decimals, const std::st
     return f.type == FieldType::String ? t + pad : pad + t;
 }
 
-bool write_shapefile(const std::string& path, const PointLayer& L, std::string& err) {
-    const size_t n = L.x.size();
-    if (n > 0x7000000u) { err = "too many points for a shapefile"; return false; }
-    std::string shp = shape_header(uint32_t(50 + 14 * n), L), shx = shape_header(uint32_t(50 + 4 * n), L);
-    for (size_t i = 0; i < n; i++) {
-        put_be32(shx, uint32_t(50 + 14 * i)); put_be32(shx, 10);
-        put_be32(shp, uint32_t(i + 1)); put_be32(shp, 10);
-        put_le32(shp, 1); put_le64f(shp, L.x[i]); put_le64f(shp, L.y[i]);
-    }
+// the .dbf of a table of n features
+bool dbf_bytes(const LayerTable& L, size_t n, std::string& dbf, std::string& err) {
     // widths: a carried-over column keeps its own; otherwise the field's, or the type's default (an Integer column grows to its longest value)
     std::vector<int> width(L.fields.size()), decimals(L.fields.size());
     size_t reclen = 1;
@@ -110,7 +108,6 @@ bool write_shapefile(const std::string& path, const PointLayer& L, std::string& 
         reclen += size_t(width[k]);
     }
     if (reclen > 65535 || L.fields.size() > 2046) { err = "too many fields for a .dbf"; return false; }
-    std::string dbf;
     const char date[4] = {0x03, 95, 7, 26};   // version, and a fixed date: the same layer gives the same bytes
     dbf.append(date, 4);
     put_le32(dbf, uint32_t(n));
@@ -132,10 +129,85 @@ bool write_shapefile(const std::string& path, const PointLayer& L, std::string& 
         for (size_t k = 0; k < L.fields.size(); k++) dbf += dbf_cell(L.fields[k], width[k], decimals[k], L.values[i][k]);
     }
     dbf.push_back('\x1a');
-    return spill(path, shp, err) && spill(with_ext(path, ".shx"), shx, err) && spill(with_ext(path, ".dbf"), dbf, err);
+    return true;
 }
 
-bool read_dbf_fields(const std::string& shp_path, size_t n_features, PointLayer& L, std::string& err) {
+bool write_shapefile(const std::string& path, const PointLayer& L, std::string& err) {
+    const size_t n = L.x.size();
+    if (n > 0x7000000u) { err = "too many points for a shapefile"; return false; }
+    Box box;
+    box.add(L.x, L.y);
+    std::string shp = shape_header(uint32_t(50 + 14 * n), 1, box), shx = shape_header(uint32_t(50 + 4 * n), 1, box), dbf;
+    for (size_t i = 0; i < n; i++) {
+        put_be32(shx, uint32_t(50 + 14 * i)); put_be32(shx, 10);
+        put_be32(shp, uint32_t(i + 1)); put_be32(shp, 10);
+        put_le32(shp, 1); put_le64f(shp, L.x[i]); put_le64f(shp, L.y[i]);
+    }
+    return dbf_bytes(L, n, dbf, err) && spill(path, shp, err) && spill(with_ext(path, ".shx"), shx, err) && spill(with_ext(path, ".dbf"), dbf, err);
+}
+
+// PolyLine records: shape type, box, one part that starts at vertex 0, the vertices - 24 + 8 * vertices 16-bit words each
+bool write_line_shapefile(const std::string& path, const LineLayer& L, std::string& err) {
+    const size_t n = L.x.size();
+    size_t words = 50;
+    Box all;
+    for (size_t i = 0; i < n; i++) { words += 4 + 24 + 8 * L.x[i].size(); all.add(L.x[i], L.y[i]); }
+    if (n > 0x7000000u || words > 0x7fffffffu) { err = "too many vertices for a shapefile"; return false; }
+    std::string shp = shape_header(uint32_t(words), 3, all), shx = shape_header(uint32_t(50 + 4 * n), 3, all), dbf;
+    size_t at = 50;
+    for (size_t i = 0; i < n; i++) {
+        const size_t np = L.x[i].size(), len = 24 + 8 * np;
+        put_be32(shx, uint32_t(at)); put_be32(shx, uint32_t(len));
+        put_be32(shp, uint32_t(i + 1)); put_be32(shp, uint32_t(len));
+        put_le32(shp, 3);
+        Box b;
+        b.add(L.x[i], L.y[i]);
+        for (double v : b.b) put_le64f(shp, v);
+        put_le32(shp, 1); put_le32(shp, uint32_t(np)); put_le32(shp, 0);
+        for (size_t k = 0; k < np; k++) { put_le64f(shp, L.x[i][k]); put_le64f(shp, L.y[i][k]); }
+        at += 4 + len;
+    }
+    return dbf_bytes(L, n, dbf, err) && spill(path, shp, err) && spill(with_ext(path, ".shx"), shx, err) && spill(with_ext(path, ".dbf"), dbf, err);
+}
+
+uint32_t rd_be32(const unsigned char* q) { return (uint32_t(q[0]) << 24) | (uint32_t(q[1]) << 16) | (uint32_t(q[2]) << 8) | q[3]; }
+uint32_t rd_le32(const unsigned char* q) { return uint32_t(q[0]) | (uint32_t(q[1]) << 8) | (uint32_t(q[2]) << 16) | (uint32_t(q[3]) << 24); }
+double rd_le64f(const unsigned char* q) { double v; memcpy(&v, q, 8); return v; }
+
+// The records of a .shp of type PolyLine, PolyLineZ or PolyLineM: every record is a feature (a null shape, or one of another type, without vertices, so
+// that the rows of the .dbf stay with their records); every count is checked against the record's length before a vertex is read
+bool read_line_shapes(const std::string& path, LineLayer& L, std::string& err) {
+    std::string bytes;
+    if (!slurp(path, bytes)) { err = "cannot open " + path; return false; }
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(bytes.data());
+    if (bytes.size() < 100 || rd_be32(u) != 9994) { err = "not a shapefile: " + path; return false; }
+    const uint32_t type = rd_le32(u + 32);
+    if (!(type == 3 || type == 13 || type == 23)) { err = "shapefile layer is not a line layer: " + path; return false; }
+    size_t pos = 100;
+    while (pos + 8 <= bytes.size()) {
+        const size_t clen = size_t(rd_be32(u + pos + 4)) * 2;
+        pos += 8;
+        if (clen > bytes.size() - pos) { err = "truncated record in " + path; return false; }
+        std::vector<double> x, y;
+        const uint32_t t = clen >= 4 ? rd_le32(u + pos) : 0;
+        if (t == 3 || t == 13 || t == 23) {
+            if (clen < 44) { err = "short line record in " + path; return false; }
+            const size_t nparts = rd_le32(u + pos + 36), npoints = rd_le32(u + pos + 40);
+            if (nparts > clen / 4 || npoints > clen / 16 || 44 + 4 * nparts + 16 * npoints > clen) { err = "line record with impossible counts in " + path; return false; }
+            size_t first = 0, last = npoints;
+            if (nparts >= 1) first = rd_le32(u + pos + 44);
+            if (nparts >= 2) last = rd_le32(u + pos + 48);
+            if (first > last || last > npoints) { err = "line record with impossible parts in " + path; return false; }
+            const unsigned char* pts = u + pos + 44 + 4 * nparts;
+            for (size_t k = first; k < last; k++) { x.push_back(rd_le64f(pts + 16 * k)); y.push_back(rd_le64f(pts + 16 * k + 8)); }
+        }
+        L.x.push_back(std::move(x)); L.y.push_back(std::move(y));
+        pos += clen;
+    }
+    return true;
+}
+
+bool read_dbf_fields(const std::string& shp_path, size_t n_features, LayerTable& L, std::string& err) {
     std::string b;
     if (!slurp(with_ext(shp_path, ".dbf"), b) && !slurp(with_ext(shp_path, ".DBF"), b)) return true;   // a .shp without attributes: no field
     if (b.size() < 33) { err = "not a .dbf file next to " + shp_path; return false; }
@@ -154,7 +226,7 @@ bool read_dbf_fields(const std::string& shp_path, size_t n_features, PointLayer&
         off.push_back(o);
         o += size_t(f.width);
     }
-    if (o > rlen || nrec != n_features || hlen + nrec * rlen > b.size()) { err = "the .dbf next to " + shp_path + " does not match its points"; return false; }
+    if (o > rlen || nrec != n_features || hlen + nrec * rlen > b.size()) { err = "the .dbf next to " + shp_path + " does not match its features"; return false; }
     for (size_t i = 0; i < nrec; i++)
         for (size_t k = 0; k < L.fields.size(); k++) L.values[i].push_back(b.substr(hlen + i * rlen + off[k], size_t(L.fields[k].width)));
     return true;
@@ -270,15 +342,8 @@ bool is_int_text(const std::string& t) {
     const long long v = strtoll(t.c_str(), nullptr, 10);
     return v >= INT_MIN && v <= INT_MAX;
 }
-bool read_geojson_fields(const std::string& path, size_t n_features, PointLayer& L, std::string& err) {
-    std::string text;
-    if (!slurp(path, text)) { err = "cannot open " + path; return false; }
-    JParser jp(text);
-    const JVal root = jp.value();
-    if (!jp.ok) { err = "cannot parse " + path; return false; }
-    std::vector<const JVal*> feats;
-    collect_point_features(root, feats);
-    if (feats.size() != n_features) { err = "the properties of " + path + " do not match its points"; return false; }
+// the properties of features -> fields (in order of first appearance; Integer until a value says otherwise) and values
+void fill_properties(const std::vector<const JVal*>& feats, LayerTable& L) {
     for (size_t i = 0; i < feats.size(); i++) {
         const JVal* pr = feats[i]->get("properties");
         if (!pr || pr->kind != JVal::Object) continue;
@@ -294,8 +359,20 @@ bool read_geojson_fields(const std::string& path, size_t n_features, PointLayer&
             L.values[i][k] = (e.kind == JVal::Array || e.kind == JVal::Object) ? std::string("(nested)") : e.text;
         }
     }
+}
+bool read_geojson_fields(const std::string& path, size_t n_features, PointLayer& L, std::string& err) {
+    std::string text;
+    if (!slurp(path, text)) { err = "cannot open " + path; return false; }
+    JParser jp(text);
+    const JVal root = jp.value();
+    if (!jp.ok) { err = "cannot parse " + path; return false; }
+    std::vector<const JVal*> feats;
+    collect_point_features(root, feats);
+    if (feats.size() != n_features) { err = "the properties of " + path + " do not match its points"; return false; }
+    fill_properties(feats, L);
     return true;
 }
+
 std::string json_string(const std::string& s) {
     std::string o = "\"";
     for (unsigned char c : s) {
@@ -320,21 +397,73 @@ std::string json_number(const std::string& t, bool integer) {
     if (s.find_first_of(".e") == std::string::npos) s += ".0";   // a Real stays one for its reader: 3.0, and -0.0 keeps its sign
     return s;
 }
+// the head of feature i up to its geometry
+std::string feature_head(const LayerTable& L, size_t i) {
+    std::string o = "{ \"type\": \"Feature\", \"properties\": { ";
+    for (size_t k = 0; k < L.fields.size(); k++) {
+        const std::string v = trim(L.values[i][k]);
+        o += (k ? ", " : "") + json_string(L.fields[k].name) + ": ";
+        o += v.empty() ? "null" : L.fields[k].type == FieldType::String ? json_string(v) : json_number(v, L.fields[k].type == FieldType::Integer);
+    }
+    return o + " }, \"geometry\": { \"type\": ";
+}
+std::string position(double x, double y) {
+    char c[96];
+    snprintf(c, sizeof c, "[ %.17g, %.17g ]", x, y);
+    return c;
+}
 bool write_geojson(const std::string& path, const PointLayer& L, std::string& err) {
     std::string o = "{\n\"type\": \"FeatureCollection\",\n\"features\": [\n";
+    for (size_t i = 0; i < L.x.size(); i++)
+        o += feature_head(L, i) + "\"Point\", \"coordinates\": " + position(L.x[i], L.y[i]) + " } }" + (i + 1 < L.x.size() ? ",\n" : "\n");
+    o += "]\n}\n";
+    return spill(path, o, err);
+}
+bool write_line_geojson(const std::string& path, const LineLayer& L, std::string& err) {
+    std::string o = "{\n\"type\": \"FeatureCollection\",\n\"features\": [\n";
     for (size_t i = 0; i < L.x.size(); i++) {
-        o += "{ \"type\": \"Feature\", \"properties\": { ";
-        for (size_t k = 0; k < L.fields.size(); k++) {
-            const std::string v = trim(L.values[i][k]);
-            o += (k ? ", " : "") + json_string(L.fields[k].name) + ": ";
-            o += v.empty() ? "null" : L.fields[k].type == FieldType::String ? json_string(v) : json_number(v, L.fields[k].type == FieldType::Integer);
-        }
-        char c[96];
-        snprintf(c, sizeof c, "[ %.17g, %.17g ]", L.x[i], L.y[i]);
-        o += std::string(" }, \"geometry\": { \"type\": \"Point\", \"coordinates\": ") + c + " } }" + (i + 1 < L.x.size() ? ",\n" : "\n");
+        o += feature_head(L, i) + "\"LineString\", \"coordinates\": [ ";
+        for (size_t k = 0; k < L.x[i].size(); k++) o += (k ? ", " : "") + position(L.x[i][k], L.y[i][k]);
+        o += std::string(" ] } }") + (i + 1 < L.x.size() ? ",\n" : "\n");
     }
     o += "]\n}\n";
     return spill(path, o, err);
+}
+
+// in document order, the features whose geometry is a LineString (or a MultiLineString: its first part)
+void collect_line_features(const JVal& v, std::vector<const JVal*>& feats, std::vector<const JVal*>& coords) {
+    if (v.kind == JVal::Object) {
+        const JVal* g = v.get("geometry");
+        if (g && g->kind == JVal::Object) {
+            const JVal* t = g->get("type");
+            const JVal* c = g->get("coordinates");
+            if (t && c && c->kind == JVal::Array) {
+                if (t->text == "LineString") { feats.push_back(&v); coords.push_back(c); }
+                else if (t->text == "MultiLineString" && !c->arr.empty() && c->arr[0].kind == JVal::Array) { feats.push_back(&v); coords.push_back(&c->arr[0]); }
+            }
+            return;
+        }
+        for (const auto& kv : v.obj) collect_line_features(kv.second, feats, coords);
+    } else if (v.kind == JVal::Array)
+        for (const JVal& e : v.arr) collect_line_features(e, feats, coords);
+}
+bool read_line_geojson(const std::string& path, LineLayer& L, std::string& err) {
+    std::string text;
+    if (!slurp(path, text)) { err = "cannot open " + path; return false; }
+    JParser jp(text);
+    const JVal root = jp.value();
+    if (!jp.ok) { err = "cannot parse " + path; return false; }
+    std::vector<const JVal*> feats, coords;
+    collect_line_features(root, feats, coords);
+    L.resize(feats.size());
+    for (size_t i = 0; i < feats.size(); i++)
+        for (const JVal& pt : coords[i]->arr) {
+            if (pt.kind != JVal::Array || pt.arr.size() < 2 || pt.arr[0].kind != JVal::Number || pt.arr[1].kind != JVal::Number) { err = "a position of " + path + " is not [x, y]"; return false; }
+            L.x[i].push_back(strtod(pt.arr[0].text.c_str(), nullptr));
+            L.y[i].push_back(strtod(pt.arr[1].text.c_str(), nullptr));
+        }
+    fill_properties(feats, L);
+    return true;
 }
 
 bool read_text_fields(const std::string& path, size_t n_features, PointLayer& L, std::string& err) {
@@ -359,21 +488,30 @@ bool read_text_fields(const std::string& path, size_t n_features, PointLayer& L,
 }
 }  // namespace
 
-size_t PointLayer::add_field(const std::string& name, FieldType type, int width, int decimals) {
+size_t LayerTable::add_field(const std::string& name, FieldType type, int width, int decimals) {
     LayerField f;
     f.name = name; f.type = type; f.width = width; f.decimals = decimals;
     fields.push_back(f);
     for (auto& row : values) row.resize(fields.size());
     return fields.size() - 1;
 }
-void PointLayer::set(size_t feature, size_t field, long long v) { values[feature][field] = std::to_string(v); }
-void PointLayer::set(size_t feature, size_t field, double v) {
+int LayerTable::field_index(const std::string& name) const {
+    for (size_t k = 0; k < fields.size(); k++) if (fields[k].name == name) return int(k);
+    return -1;
+}
+void LayerTable::set(size_t feature, size_t field, long long v) { values[feature][field] = std::to_string(v); }
+void LayerTable::set(size_t feature, size_t field, double v) {
     char b[64];
     snprintf(b, sizeof b, "%.17g", v);
     values[feature][field] = b;
 }
 void PointLayer::resize(size_t n) {
     x.resize(n); y.resize(n);
+    values.resize(n);
+    for (auto& row : values) row.resize(fields.size());
+}
+void LineLayer::resize(size_t n) {
+    x.assign(n, {}); y.assign(n, {});
     values.resize(n);
     for (auto& row : values) row.resize(fields.size());
 }
@@ -405,6 +543,29 @@ bool write_point_layer(const std::string& path, const PointLayer& L, std::string
     case LayerKind::Shapefile: return write_shapefile(path, L, err);
     case LayerKind::GeoJSON: return write_geojson(path, L, err);
     default: err = std::string("unsupported output ") + path + ": " + kLayerKindsMessage; return false;
+    }
+}
+
+bool write_line_layer(const std::string& path, const LineLayer& L, std::string& err) {
+    if (L.x.size() != L.y.size() || L.values.size() != L.x.size()) { err = "line layer: columns of different length"; return false; }
+    for (size_t i = 0; i < L.x.size(); i++)
+        if (L.values[i].size() != L.fields.size() || L.x[i].size() != L.y[i].size()) { err = "line layer: a feature without all fields, or with unpaired coordinates"; return false; }
+    switch (layer_kind(path)) {
+    case LayerKind::Shapefile: return write_line_shapefile(path, L, err);
+    case LayerKind::GeoJSON: return write_line_geojson(path, L, err);
+    default: err = std::string("unsupported output ") + path + ": " + kLineLayerKindsMessage; return false;
+    }
+}
+
+bool read_line_layer(const std::string& path, LineLayer& L, std::string& err) {
+    L = LineLayer();
+    switch (layer_kind(path)) {
+    case LayerKind::Shapefile:
+        if (!read_line_shapes(path, L, err)) return false;
+        L.values.assign(L.x.size(), {});
+        return read_dbf_fields(path, L.x.size(), L, err);
+    case LayerKind::GeoJSON: return read_line_geojson(path, L, err);
+    default: err = std::string("unsupported input ") + path + ": " + kLineLayerKindsMessage; return false;
     }
 }
 }  // namespace tdx

@@ -383,7 +383,17 @@ class _StripTerrainIndexStage:
         return api._setregion(self._call(), p, gw, region_id, nodata, gw_nodata, out)
 
 
-class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage, _StripTerrainIndexStage):
+class _StripEditRasterStage:
+    """StripPipeline.editraster (include/taudem_amd_editraster.h): nothing is exchanged and the halo rows of the output are not written."""
+
+    def editraster(self, raster, cols, rows, vals, row0, out=None, nodata=int(P_NODATA)):
+        """new = editraster(raster, cols, rows, vals, row0) on this strip (src/EditRaster.cpp:69): rows are GLOBAL rows, row0 is the global row of the strip's
+        first owned row; every strip is given the whole list and applies the changes of its owned rows.  out=raster edits the strip in place."""
+        return api._editraster(self._call(), raster, cols, rows, vals, nodata, out, row0=row0)
+
+
+class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage, _StripTerrainIndexStage,
+                    _StripEditRasterStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

@@ -220,13 +220,25 @@ def setregion(fdrfile, regiongwfile, newfile, regionID=1):
     return _lib.load().tdx_tool_setregion(_b(fdrfile), _b(regiongwfile), _b(newfile), int(regionID))
 
 
+def editraster(rasterfile, newfile, changefile):
+    """src/EditRaster.cpp:69 (EditRaster): the raster as int16 with the cells of the change file's "x,y,value" lines set."""
+    return _lib.load().tdx_tool_editraster(_b(rasterfile), _b(newfile), _b(changefile))
+
+
+def catchoutlets(pfile, streamnetsrc="", outletsdatasrc="", mindist=0.0, gwstartno=1, minarea=0.0, treefile="", coordfile=""):
+    """src/CatchOutlets.cpp:126 (CatchOutlets), host code: the network is the line layer streamnetsrc, or this project's streamnet -tree and -coord files
+    (treefile, coordfile) - one of the two.  The outlets go to a shapefile or GeoJSON point layer."""
+    return _lib.load().tdx_tool_catchoutlets(_b(pfile), _b(streamnetsrc), _b(treefile), _b(coordfile), _b(outletsdatasrc), float(mindist), int(gwstartno), float(minarea))
+
+
 twi = twigrid
 slopearearatio = atanbgrid
 
 
 def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, outletsds="", lyrname="", uselayername=0, lyrno=0, wfile="", streamnetsrc="",
              streamnetlyr="", useOutlets=0, ordert=1, verbose=False):
-    """src/streamnet.cpp:372 (StreamNet); ordert = 0 is -sw.  The stream network layer is not written: a non-empty streamnetsrc / streamnetlyr is refused."""
+    """src/streamnet.cpp:372 (StreamNet); ordert = 0 is -sw.  The stream network layer is not written: a non-empty streamnetsrc / streamnetlyr is refused
+    (tdx_streamnet_net_write, Context.streamnet(..., net=path), makes the layer from the links)."""
     return _lib.load().tdx_tool_streamnet(_b(pfile), _b(srcfile), _b(ordfile), _b(ad8file), _b(elevfile), _b(treefile), _b(coordfile), _b(outletsds), _b(lyrname),
                                           int(uselayername), int(lyrno), _b(wfile), _b(streamnetsrc), _b(streamnetlyr), int(useOutlets), int(ordert), int(bool(verbose)))
 
