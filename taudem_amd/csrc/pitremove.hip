@@ -7,8 +7,13 @@
 // (the minimax-path surface), so ANY schedule that runs to convergence yields
 // the same bits.  Schedule used here:
 //
-//   * pit_seed_kernel    streaming 3x3 stencil: Z -> W0                 (src/flood.cpp:243-271); with the coarse-to-fine start: Z -> first
-//                        coarse level, and later Z + relaxed coarse level -> start surface
+//   * pit_seed_kernel    streaming 3x3 stencil: Z -> W0                 (src/flood.cpp:243-271); with the coarse-to-fine start the same pass
+//                        also reduces W0 to the first coarse level (MODE 3: Z is read once)
+//   * coarse levels      relaxed coarse to fine, each across the strips (pit_finish_level)
+//   * tilek::relax_kernel<PitStartOp>  round 0 of the fine level, every tile: a cell of W0 that still holds FLT_MAX is read as the relaxed
+//                        coarse value of its 8 x 8 block (the start surface is never written out as a pass of its own), and every filled
+//                        cell is stored.  TDX_PIT_SEED=two (and TDX_RELAX_LDS / TDX_RELAX_ASYNC): a second pass over Z (MODE 1, then MODE 2)
+//                        writes the start surface, and round 0 is a round like the others
 //   * tilek::relax_kernel<PitOp>  the tile relaxation engine of tile_relax.hpp: one workgroup per
 //                        ACTIVE 64x64 tile, W and Z of a lane's 16-row column segment in registers
 //                        (neighbour columns = neighbour lanes, LDS only between the four waves),
@@ -18,6 +23,8 @@
 //
 // HBM traffic per activation of a tile = 2 tile images in + changed cells out; rounds ~ longest fill
 // path measured in tiles.
+#include <cstring>
+
 #include "context.hpp"
 #include "device_common.hpp"
 #include "strips.hpp"
@@ -27,11 +34,12 @@ namespace {
 
 // Seed surface (src/flood.cpp:243-271).  A 256-thread block covers 64 columns x 64 rows; each lane walks a 16-row
 // column segment with the 3x3 window of nodata flags in registers: 3 coalesced row loads per output row.
-// MODE 0: W0 (FLT_MAX where the cell is not a seed).  The coarse-to-fine start (below) runs the pass twice instead, with nothing written in
-// between: MODE 1 only reduces the seed surface to the first coarse level (per 8 x 8 block of the owned rows: Zc = largest valid
-// elevation, Wc = Zc if the block holds a seed cell, else FLT_MAX; TDX_FEL_NODATA for a block without valid cells - what
-// pit_coarsen_kernel derives from Z and W0), MODE 2 writes the start surface itself, W = seed ? z : Wc[block] (what pit_prolong_kernel
-// makes of W0).  6.7 GB of traffic for seed + coarsen + prolong become 3 GB.
+// MODE 0: W0 (FLT_MAX where the cell is not a seed).  MODE 1 only reduces the seed surface to the first coarse level (per 8 x 8 block of
+// the owned rows: Zc = largest valid elevation, Wc = Zc if the block holds a seed cell, else FLT_MAX; TDX_FEL_NODATA for a block without valid
+// cells - what pit_coarsen_kernel derives from Z and W0), MODE 2 writes the start surface itself, W = seed ? z : Wc[block] (what
+// pit_prolong_kernel makes of W0), MODE 3 = MODE 1 + MODE 0 from the same registers.  The coarse-to-fine start (below) runs MODE 3 once and
+// leaves the select of MODE 2 to the loads of the fine level's round 0 (PitStartOp); TDX_PIT_SEED=two runs MODE 1 and MODE 2.  At 16384^2
+// (1.07 GB per float raster): seed + coarsen + prolong moved 6.7 GB, MODE 1 + MODE 2 move 3.2 GB (0.38 + 0.50 ms), MODE 3 moves 2.1 GB (0.49 ms).
 constexpr int SEED_ROWS = 16;
 constexpr int SEED_CF = 8;   // = CF below
 template <int MODE>
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(256) void pit_seed_kernel(const float* __restrict__
         const int l = tilek::lane_left(c, 0), r = tilek::lane_right(c, 0);
         nod[j] = in ? (unsigned(lane == 0 ? e : l) | (unsigned(c) << 1) | (unsigned(lane == 63 ? e : r) << 2)) : 7u;
     }
-    float bmax[SEED_ROWS / SEED_CF];   // MODE 1: this lane's column of each block row it crosses
+    float bmax[SEED_ROWS / SEED_CF];   // MODE 1 / 3: this lane's column of each block row it crosses
     bool bany[SEED_ROWS / SEED_CF], bseed[SEED_ROWS / SEED_CF];
 #pragma unroll
     for (int q = 0; q < SEED_ROWS / SEED_CF; q++) { bmax[q] = -FLT_MAX; bany[q] = false; bseed[q] = false; }
@@ -96,8 +104,8 @@ __global__ __launch_bounds__(256) void pit_seed_kernel(const float* __restrict__
                 const bool con = (step == 2) ? (((nc & 5u) | (nn & 2u) | (ns & 2u)) != 0u) : ((nn | nc | ns) != 0u);   // (nc & 2 is clear here)
                 w = con ? zc : FLT_MAX;
             }
-            if (MODE == 0) W[idx] = w;
-            if (MODE == 1 && !c1) {
+            if (MODE == 0 || MODE == 3) W[idx] = w;
+            if ((MODE == 1 || MODE == 3) && !c1) {
                 bany[r / SEED_CF] = true;
                 bmax[r / SEED_CF] = fmaxf(bmax[r / SEED_CF], zc);
                 if (w != FLT_MAX) bseed[r / SEED_CF] = true;
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(256) void pit_seed_kernel(const float* __restrict__
             }
         }
     }
-    if (MODE == 1) {   // the 8 lanes of a block column (aligned: 64 columns per wave), then one store per block
+    if (MODE == 1 || MODE == 3) {   // the 8 lanes of a block column (aligned: 64 columns per wave), then one store per block
 #pragma unroll
         for (int q = 0; q < SEED_ROWS / SEED_CF; q++) {
             float m = bmax[q];
@@ -271,6 +279,68 @@ struct PitOp {
     static __device__ __forceinline__ float act_threshold(float z, float w) { return (w > z) ? w : act_never(); }
 };
 
+// PitOp<8> for ROUND 0 of the fine level after a coarse-to-fine start with one seed pass: W holds the unprolonged seed surface W0, and a cell that still reads
+// FLT_MAX stands at the relaxed coarse value of its 8 x 8 block - what pit_seed_kernel<2> used to write out.  tile_relax.hpp (start_fill_of) applies the select
+// to everything a tile loads and stores every filled cell; round 0 visits every tile, so every later round uses the plain PitOp<8> (RoundRunner::start_with).
+// Rows: array row y of the fine strip lies in coarse array row cy0 + (y - y_own0) / CF while it is owned; the halo row above / below (multi-strip) maps to the coarse
+// level's halo row above / below, which holds the neighbour's last / first block row (pit_relax_level ends on an exchange without changes).  RPW consecutive rows
+// cross at most four coarse rows (15 owned rows over three block rows and the halo row below them): four unconditional loads per lane, one each for the edge and
+// the side cell.  Rows beyond the array are clamped; what is loaded for them is not used.
+struct PitStartOp : PitOp<8> {
+    static constexpr int kWaves = 4;   // (a handful of rounds per call; free of scratch at 128 registers)
+    const float* Wc;                   // the coarse level's array, halo rows included
+    int nxc, ny_arr_c, cy0, nyc;       // its width, rows, first owned row, owned rows
+    int y_own0, y_own1;                // the fine strip's owned rows
+    struct Fill { float v[4]; bool aligned; };
+    // (branch-free: row y_own0 - 1, the halo row above, lands on cy0 - 1 through the arithmetic shift)
+    __device__ __forceinline__ int coarse_row(int y) const { return y >= y_own1 ? cy0 + nyc : cy0 + ((y - y_own0) >> 3); }
+    __device__ __forceinline__ float coarse_at(int x, int cr) const {
+        const int crc = cr < 0 ? 0 : (cr >= ny_arr_c ? ny_arr_c - 1 : cr);
+        return Wc[size_t(crc) * size_t(nxc) + size_t(x / CF)];   // (x is a column of the raster: x / CF < nxc)
+    }
+    __device__ __forceinline__ Fill fill_load(int x, int y) const {
+        Fill f;
+        const int c0 = coarse_row(y);
+#pragma unroll
+        for (int q = 0; q < 4; q++) f.v[q] = coarse_at(x, c0 + q);
+        f.aligned = y >= y_own0 && ((y - y_own0) & (CF - 1)) == 0 && y + tilek::RPW <= y_own1;   // RPW owned rows from a block's first: two block rows, eight rows each
+        return f;
+    }
+    // The band's rows y .. y + RPW - 1 (y a scalar): w[r] <- candidate where it is FLT_MAX; returns the rows that changed.  Every select hangs on the loaded w (a
+    // candidate picked per row ahead of it is sixteen more registers while the tile's loads are in flight); a band of whole blocks - every band of a raster that
+    // is one strip, but for its last rows - takes its candidates by the row's number.
+    __device__ __forceinline__ unsigned fill_band(const Fill& f, float (&w)[tilek::RPW], int y) const {
+        static_assert(CF == 8 && tilek::RPW == 2 * CF, "two block rows per band");
+        unsigned ch = 0;
+        if (f.aligned) {
+#pragma unroll
+            for (int r = 0; r < tilek::RPW; r++) {
+                const float nw = w[r] == FLT_MAX ? f.v[r / CF] : w[r];
+                ch = tilek::shift_in_ne(ch, nw, w[r]);
+                w[r] = nw;
+            }
+        } else {
+            const int c0 = coarse_row(y);
+#pragma unroll
+            for (int r = 0; r < tilek::RPW; r++) {
+                const int q = coarse_row(y + r) - c0;
+                const bool m = w[r] == FLT_MAX;
+                float nw = w[r];
+                nw = (m && q == 0) ? f.v[0] : nw;
+                nw = (m && q == 1) ? f.v[1] : nw;
+                nw = (m && q == 2) ? f.v[2] : nw;
+                nw = (m && q == 3) ? f.v[3] : nw;
+                ch = tilek::shift_in_ne(ch, nw, w[r]);
+                w[r] = nw;
+            }
+        }
+        return __builtin_bitreverse32(ch) >> (32 - tilek::RPW);   // (row 0 was shifted in first)
+    }
+    __device__ __forceinline__ float fill_cell(int x, int y) const { return coarse_at(x, coarse_row(y)); }
+    // (a block without valid cells holds TDX_FEL_NODATA, and a valid cell that is no seed never lies in one: wc replaces w only where w is FLT_MAX)
+    static __device__ __forceinline__ float fill(float w, float wc) { return w == FLT_MAX ? wc : w; }
+};
+
 }  // namespace
 
 static int pit_finish_level(tdx_context* ctx, const Strip& ls, float* Zc, float* Wc, int nxc, int nyc, int64_t cells_all, tilek::Sched sc, int depth,
@@ -291,13 +361,15 @@ static inline Strip pit_level_strip(const Strip& st, int nxc, int nyc) {
 // One level (fine or coarse) to its fixed point.  Multi-strip: every rank relaxes its strip to the local fixed point with the neighbours' boundary
 // rows frozen in its halo rows, then boundary rows are exchanged and the tiles that see a changed halo cell are re-activated; repeat until no halo
 // cell changed on any rank (the roles of share() + ringTerm() in src/flood.cpp:344-355,457-468).
+// start (optional): the operator of round 0 of the FIRST run (W still holds the unprolonged seed surface: PitStartOp); everything later uses the plain one.
 template <int NBR>
 static int pit_relax_level(tdx_context* ctx, const Strip& ls, const float* Z, float* W, tilek::Sched sc, int64_t* rounds, int64_t* launches, int64_t* outer,
-                           bool all_tiles = true) {
+                           bool all_tiles = true, const PitStartOp* start = nullptr) {
     const tilek::TileGeom g = tilek::make_geom(ls.nx, ls.ny_arr, ls.y0, ls.y1);
     for (;;) {
         // round 0: every tile is active (one set-up launch: tilek::all_start_kernel), otherwise / later: the tiles flagged in sc.flags
-        int rc = tile_relax_run(ctx, PitOp<NBR>{Z, W}, g, sc, rounds, launches, all_tiles);
+        int rc = tile_relax_run(ctx, PitOp<NBR>{Z, W}, g, sc, rounds, launches, all_tiles, all_tiles ? start : nullptr);
+        start = nullptr;
         all_tiles = false;
         if (rc != TDX_OK) return rc;
         if (outer) (*outer)++;
@@ -376,9 +448,15 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
     rc = strip_allreduce(ctx, st, &cells_all, 1, TDX_OP_SUM);
     if (rc != TDX_OK) return rc;
     const bool used_coarse = !fourway && !no_coarse && cells_all >= (int64_t(1) << 18);
+    // One seed pass (pit_seed_kernel<3>: first coarse level and W0 from one read of Z) and the start surface filled in when the fine level's first run loads it
+    // (PitStartOp), or TDX_PIT_SEED=two (read per call: A/B and test hook): a second pass over Z writes the start surface out.  The start operator has the register
+    // tile form and the round schedule only: TDX_RELAX_LDS / TDX_RELAX_ASYNC take the two passes as well.
+    const char* seed_env = getenv("TDX_PIT_SEED");
+    const bool one_seed_pass = used_coarse && !(seed_env && strcmp(seed_env, "two") == 0) && !getenv("TDX_RELAX_LDS") && !getenv("TDX_RELAX_ASYNC");
+    PitStartOp start_op{{d_dem, d_fel}, nullptr, 0, 0, 0, 0, st.y0, st.y1};
     int64_t level1_rounds = 0;
     if (used_coarse) {
-        // seed surface -> first coarse level -> (coarser levels, relaxed coarse to fine, each across the strips) -> start surface, without a W0 in between
+        // seed surface -> first coarse level -> (coarser levels, relaxed coarse to fine, each across the strips) -> start surface (written out by pit_seed_kernel<2>, or filled in by round 0 of the fine level from W0: one_seed_pass)
         const int nxc = (st.nx + CF - 1) / CF, nyc = (nyo + CF - 1) / CF;
         const Strip ls = pit_level_strip(st, nxc, nyc);
         const size_t nc = size_t(nxc) * size_t(ls.ny_arr), off = size_t(ls.y0) * size_t(nxc);
@@ -387,8 +465,12 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
         if (!Zc || !Wc) return TDX_ERR_NOMEM;
         {
             TdxSpan sp(ctx, TDX_K_STENCIL);
-            hipLaunchKernelGGL(pit_seed_kernel<1>, sgrid, dim3(256), 0, s, d_dem, d_mask, d_fel, st.nx, st.ny_arr, st.y0, st.y1, dem_nodata, 1, Zc + off, Wc + off, nxc, nyc, sbx, sxmap);
+            if (one_seed_pass)
+                hipLaunchKernelGGL(pit_seed_kernel<3>, sgrid, dim3(256), 0, s, d_dem, d_mask, d_fel, st.nx, st.ny_arr, st.y0, st.y1, dem_nodata, 1, Zc + off, Wc + off, nxc, nyc, sbx, sxmap);
+            else
+                hipLaunchKernelGGL(pit_seed_kernel<1>, sgrid, dim3(256), 0, s, d_dem, d_mask, d_fel, st.nx, st.ny_arr, st.y0, st.y1, dem_nodata, 1, Zc + off, Wc + off, nxc, nyc, sbx, sxmap);
             if (stats) stats->launches[TDX_K_STENCIL]++;
+            start_op.Wc = Wc; start_op.nxc = nxc; start_op.ny_arr_c = ls.ny_arr; start_op.cy0 = ls.y0; start_op.nyc = nyc;
         }
         {
             TdxSpan sp(ctx, TDX_K_RELAX);
@@ -396,7 +478,7 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
             rc = pit_finish_level(ctx, ls, Zc, Wc, nxc, nyc, cells_all / (CF * CF), sched, 0, &rounds, &launches, &level1_rounds);
             if (rc != TDX_OK) return rc;
         }
-        {
+        if (!one_seed_pass) {
             TdxSpan sp(ctx, TDX_K_STENCIL);
             hipLaunchKernelGGL(pit_seed_kernel<2>, sgrid, dim3(256), 0, s, d_dem, d_mask, d_fel, st.nx, st.ny_arr, st.y0, st.y1, dem_nodata, 1, Zc + off, Wc + off, nxc, nyc, sbx, sxmap);
             if (stats) stats->launches[TDX_K_STENCIL]++;
@@ -410,15 +492,24 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
     ctx->phase = "fine level";
     rc = strip_exchange<float>(ctx, st, d_fel, TDX_FEL_NODATA);   // start surface halo rows
     if (rc != TDX_OK) return rc;
+    if (one_seed_pass && st.multi()) {
+        // The neighbours' boundary rows arrive as W0.  Nobody owns the halo rows, so no tile stores what it fills in there, and the rounds after round 0 read them
+        // with the plain operator: the two rows are prolonged in place from the coarse level's halo rows (which hold the neighbours' last / first block row).
+        const dim3 gh((st.nx + 63) / 64, 1);
+        hipLaunchKernelGGL(pit_prolong_kernel, gh, dim3(256), 0, s, d_fel, st.nx, 1, start_op.Wc + size_t(start_op.cy0 - 1) * size_t(start_op.nxc), start_op.nxc);
+        hipLaunchKernelGGL(pit_prolong_kernel, gh, dim3(256), 0, s, d_fel + size_t(st.y1) * size_t(st.nx), st.nx, 1,
+                           start_op.Wc + size_t(start_op.cy0 + start_op.nyc) * size_t(start_op.nxc), start_op.nxc);
+    }
     {
         TdxSpan sp(ctx, TDX_K_RELAX);
-        bool all_tiles = true;
+        bool all_tiles = true, first_run_done = false;
         // one coarse correction after the first fine rounds (see pit_restrict_kernel); TDX_PIT_VCYCLE_AFTER=n: after n rounds (0: never)
         const int vc_env = getenv("TDX_PIT_VCYCLE_AFTER") ? std::max(0, atoi(getenv("TDX_PIT_VCYCLE_AFTER"))) : 8;   // (read per call: test hook)
         if (used_coarse && vc_env > 0) {
             bool left = false;
-            rc = tile_relax_run_bounded(ctx, PitOp<8>{d_dem, d_fel}, geom, sched, vc_env, &left, &rounds, &launches, true);   // (round 0: every tile)
+            rc = tile_relax_run_bounded(ctx, PitOp<8>{d_dem, d_fel}, geom, sched, vc_env, &left, &rounds, &launches, true, one_seed_pass ? &start_op : nullptr);   // (round 0: every tile)
             if (rc != TDX_OK) return rc;
+            first_run_done = true;
             all_tiles = false;   // what is still active stays flagged
             // A correction costs a pass over the fine surface, a coarse relaxation and a restart of the fine schedule (~1 ms at 16384^2): it pays when the fine
             // tail is long.  The first coarse level's own relaxation says how long - the fine level needs ~6 x its rounds (13 -> 67 on a 65536 x 8192 strip,
@@ -458,7 +549,8 @@ static int pitremove_impl(tdx_context* ctx, const Strip& st, float* d_dem, const
                 }
             }
         }
-        rc = fourway ? pit_relax_level<4>(ctx, st, d_dem, d_fel, sched, &rounds, &launches, &outer, all_tiles) : pit_relax_level<8>(ctx, st, d_dem, d_fel, sched, &rounds, &launches, &outer, all_tiles);
+        rc = fourway ? pit_relax_level<4>(ctx, st, d_dem, d_fel, sched, &rounds, &launches, &outer, all_tiles)
+                     : pit_relax_level<8>(ctx, st, d_dem, d_fel, sched, &rounds, &launches, &outer, all_tiles, (one_seed_pass && !first_run_done) ? &start_op : nullptr);
         if (rc != TDX_OK) return rc;
         if (stats) stats->launches[TDX_K_RELAX] += launches;
     }

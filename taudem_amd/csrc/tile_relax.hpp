@@ -184,6 +184,21 @@ __device__ __forceinline__ void activate_tiles_around(int x, int y, int nx, int 
         }
 }
 
+// Op::Fill (optional; register tiles only): a START operator.  The field in memory still holds a "not yet written" marker in some cells, and what such a cell
+// stands for is a function of its address alone (PitRemove: the relaxed coarse level's value of the cell's block instead of a streaming pass that writes it out).
+// Every raw value the tile loads - the lane's rows, the edge row, the side cells, and through them the halo's activation thresholds - goes through
+//   Fill op.fill_load(int x, int y) const;               the candidates for rows y .. y + RPW - 1 of column x (unconditional loads, issued with the tile's own)
+//   unsigned op.fill_band(const Fill&, Raw (&raw)[RPW], int y) const;   replaces the markers among the rows y .. y + RPW - 1 (y: a scalar); returns the rows it changed
+//   Raw  op.fill_cell(int x, int y) const;                the candidate of one cell (edge row, side column)
+//   static Raw fill(Raw raw, Raw candidate);              raw unless it is the marker
+// before anything decodes it, and the write-back stores every owned cell whose raw value was replaced, moved or not: such a cell may never be looked at again.
+// That it was filled is no news for a neighbour, which sees the same value through the same fill: only cells that MOVED enter the rim bits.
+struct NoFill {};
+template <class Op, class = void>
+struct start_fill_of { using type = NoFill; static constexpr bool value = false; };
+template <class Op>
+struct start_fill_of<Op, std::void_t<typename Op::Fill>> { using type = typename Op::Fill; static constexpr bool value = true; };
+
 constexpr int RES_CHANGED = 1 << 8;   // some cell of the tile moved (bits 0-7: which rim parts moved: N S W E NW NE SW SE)
 constexpr int RES_CAPPED = 1 << 9;    // stopped at max_sweeps before the tile-local fixed point
 
@@ -192,6 +207,7 @@ constexpr int RES_CAPPED = 1 << 9;    // stopped at max_sweeps before the tile-l
 template <class Op>
 __device__ __forceinline__ int relax_tile(const Op& op, const TileGeom& g, int tile, bool full, typename Op::T* sV, TileLds& L, unsigned long long* __restrict__ dbg) {
     using T = typename Op::T;
+    static_assert(!start_fill_of<Op>::value, "a start operator (Op::Fill) has the register form only");
     const int tid = threadIdx.x;
     const int lx = tid & 63;
     const int wv = tid >> 6;
@@ -614,7 +630,6 @@ template <class Op, class = void>
 struct cell_raw_of { using type = NoCellRaw; static constexpr bool value = false; };
 template <class Op>
 struct cell_raw_of<Op, std::void_t<typename Op::CellRaw>> { using type = typename Op::CellRaw; static constexpr bool value = true; };
-
 // Same contract as relax_tile (sV must hold REG_LDS_WORDS words).
 template <class Op>
 __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, int tile, typename Op::T* sV, TileLds& L, unsigned long long* __restrict__ dbg) {
@@ -649,6 +664,11 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
             gy++;
         }
     }
+    constexpr bool kFill = start_fill_of<Op>::value;   // a start operator (see start_fill_of)
+    typename start_fill_of<Op>::type fill_rows = {};
+    typename Op::Raw fill_edge = {}, fill_side = {};
+    int fy0 = 0;   // the band's first row as a scalar: the rows' candidates are then picked by scalar compares
+    if constexpr (kFill) { fy0 = __builtin_amdgcn_readfirstlane(y0 + ry0); fill_rows = op.fill_load(gxc, fy0); }
     const int ey = (wv == 0) ? y0 - 1 : y0 + TS;   // tile halo row above (first band) / below (last band); unused by the inner bands
     const bool edge_ok = col_ok && ey >= 0 && ey < g.ny;
     bool side_ok;
@@ -656,11 +676,25 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
         const int eyc = ey < 0 ? 0 : (ey >= g.ny ? g.ny - 1 : ey);
         raw_edge = op.load_raw(size_t((long long)eyc * row_pitch + gxc));
         if constexpr (has_act_threshold<Op>::value && !has_act_threshold_raw<Op>::value) craw_edge = op.cell_raw(size_t((long long)eyc * row_pitch + gxc));
+        if constexpr (kFill) fill_edge = op.fill_cell(gxc, __builtin_amdgcn_readfirstlane(eyc));
         const int row = (tid >> 1) < LH ? (tid >> 1) : LH - 1, right = tid & 1;
         const int sx = right ? x0 + TS : x0 - 1, sy = y0 - 1 + row;
         side_ok = tid < 2 * LH && sx >= 0 && sx < g.nx && sy >= 0 && sy < g.ny;
         const int sxc = sx < 0 ? 0 : (sx >= g.nx ? g.nx - 1 : sx), syc = sy < 0 ? 0 : (sy >= g.ny ? g.ny - 1 : sy);
         raw_side = op.load_raw(size_t((long long)syc * row_pitch + sxc));   // (132 cache lines for 132 cells - measured not to be what bounds a round: docs/experiments_r06.md section 2)
+        if constexpr (kFill) fill_side = op.fill_cell(sxc, syc);
+    }
+    // start operators: owned rows of this lane whose raw value was replaced - stored by the write-back whether they move or not (the word waits in LDS, one per
+    // thread behind the REG_LDS_WORDS of every operator: held in a register across the sweeps it cost the kernel twelve spilled registers)
+    if constexpr (kFill) {
+        static_assert(!has_act_threshold_raw<Op>::value && !has_raw_can_move<Op>::value, "the fill is written for the per-row write-back");
+        // (rows of the band that are owned, as a scalar mask: fy0 is one)
+        const int lo = g.y_own0 - fy0 < 0 ? 0 : (g.y_own0 - fy0 > RPW ? RPW : g.y_own0 - fy0), hi = g.y_own1 - fy0 < 0 ? 0 : (g.y_own1 - fy0 > RPW ? RPW : g.y_own1 - fy0);
+        const unsigned own_rows = hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
+        const unsigned filled = col_ok ? (op.fill_band(fill_rows, raw, fy0) & own_rows) : 0u;
+        raw_edge = Op::fill(raw_edge, fill_edge);
+        raw_side = Op::fill(raw_side, fill_side);
+        reinterpret_cast<unsigned*>(sV + REG_LDS_WORDS)[tid] = filled;   // (read back by the same thread)
     }
     T v[RPW], cst[RPW];
     unsigned mk[RPW / 4] = {};
@@ -778,6 +812,19 @@ __device__ __forceinline__ int relax_tile_reg(const Op& op, const TileGeom& g, i
         rows = __builtin_amdgcn_readfirstlane(nd) & rows_live;
     }
     const unsigned long long tc2 = dbg ? __builtin_readcyclecounter() : 0ull;
+    if constexpr (kFill) {
+        // A start operator's filled cells that did not move (the others are stored below): every tile gets here - a band without a live row skips its sweeps,
+        // not this - and nothing of it enters the rim bits.
+        const unsigned only = reinterpret_cast<const unsigned*>(sV + REG_LDS_WORDS)[tid] & ~moved;
+        if (__ballot(only != 0u) != 0ull) {   // (most filled cells are lowered by the first sweep: a wave rarely has one that is not)
+            size_t idx = size_t(y0 + ry0) * size_t(g.nx) + size_t(gx);   // filled cells are in-grid and owned
+#pragma unroll
+            for (int r = 0; r < RPW; r++) {
+                if ((only >> r) & 1u) op.store(idx, v[r]);
+                idx += size_t(g.nx);
+            }
+        }
+    }
     if (any_change) {   // uniform
         // Which neighbours are told (res bits 0-7: N S W E NW NE SW SE): with an activation filter (has_act_threshold) only if a cell of the neighbour that the
         // moved rim cell touches can still be improved by the new value; g.act_filter == 0: whenever a rim cell moved.
@@ -1086,7 +1133,7 @@ __global__ __launch_bounds__(NTHR, relax_waves<Op>::value) void relax_kernel(Op 
                                                     uint32_t* __restrict__ list_next, unsigned pull_max, unsigned long long* __restrict__ dbg, unsigned grid_tiles) {
     using T = typename Op::T;
     static_assert(sizeof(T) == 4, "tile engine works on 4-byte values");
-    constexpr int kLdsWords = REG ? (REG_LDS_WORDS > macro_lds_words<Op>::value ? REG_LDS_WORDS : macro_lds_words<Op>::value) : LH * LP;
+    constexpr int kLdsWords = REG ? (REG_LDS_WORDS > macro_lds_words<Op>::value ? REG_LDS_WORDS : macro_lds_words<Op>::value) + (start_fill_of<Op>::value ? NTHR : 0) : LH * LP;
     __shared__ T sV[kLdsWords];
     __shared__ TileLds L;
     if constexpr (REG && has_macro<Op>::value) {
@@ -1100,7 +1147,8 @@ __global__ __launch_bounds__(NTHR, relax_waves<Op>::value) void relax_kernel(Op 
         if constexpr (REG && has_plain<Op>::value) {   // tiles whose masks only say "may move" take the uniform form of the operator (flats.hpp)
             if (!__builtin_amdgcn_readfirstlane(int(op.tile_masked(tile)))) return relax_tile_reg(op.plain(), g, tile, sV, L, dbg);
         }
-        return REG ? relax_tile_reg(op, g, tile, sV, L, dbg) : relax_tile(op, g, tile, full, sV, L, dbg);
+        if constexpr (REG) return relax_tile_reg(op, g, tile, sV, L, dbg);
+        else return relax_tile(op, g, tile, full, sV, L, dbg);
     }, blockIdx.x, nblocks);
 }
 
@@ -1382,6 +1430,7 @@ struct RoundSchedule {
                                       uint32_t* flags_next, uint32_t* list_next, unsigned pull_max)>;
     tdx_context* ctx; hipStream_t s; tilek::TileGeom g; tilek::Sched sc; uint64_t* h;
     Launch launch;
+    Launch first_launch;                 // (optional) the schedule's very first launch - round 0 - goes through this one: a start operator (tilek::start_fill_of)
     int ntiles; unsigned cgrid, grid_full, grid_small;
     bool print_counts = false;
     int ring_len;                        // rounds that fit the count ring before it wraps (TDX_RELAX_RING: test hook)
@@ -1470,7 +1519,7 @@ struct RoundSchedule {
         for (int b = 0; b < batch; b++) {
             const int p = (parity + b) & 1;
             const int sp = timed ? ctx->span_begin(TDX_K_TILEK) : -1;   // this kernel alone: what bench.py's roofline is computed from
-            launch(g, grid, s, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1), list_of(p ^ 1), pull_max);
+            ((first_launch && launches == 0 && b == 0) ? first_launch : launch)(g, grid, s, list_of(p), sc.counts + r + b, flags_of(p), flags_of(p ^ 1), list_of(p ^ 1), pull_max);
             ctx->span_end(sp);
             if (timed && ctx->cur_stats) ctx->cur_stats->launches[TDX_K_TILEK]++;
         }
@@ -1574,6 +1623,17 @@ struct RoundRunner : RoundSchedule {
                 const unsigned gm = (has_macro<Op>::value && rg.blk_k != nullptr) ? std::max(unsigned(macro_wgs * ctx->num_cus), MACRO_WGS_MIN) : 0u;
                 hipLaunchKernelGGL((relax_kernel<Op, true>), dim3(grid + gm), dim3(NTHR), 0, ls, op, rg, list, count, fcur, fnext, lnext, pm, dbg, gm ? grid : 0u);
             }
+        };
+    }
+    // round 0 with a start operator (register form; the caller keeps away from TDX_RELAX_LDS), every later round with `op`: after a round over EVERY tile the
+    // start operator has stored whatever it filled in, and the field in memory is one the plain operator reads as it is
+    template <class StartOp>
+    void start_with(StartOp sop) {
+        static_assert(tilek::start_fill_of<StartOp>::value, "a start operator");
+        first_launch = [this, sop](const tilek::TileGeom& rg, unsigned grid, hipStream_t ls, const uint32_t* list, unsigned long long* count, uint32_t* fcur, uint32_t* fnext,
+                                   uint32_t* lnext, unsigned pm) {
+            using namespace tilek;
+            hipLaunchKernelGGL((relax_kernel<StartOp, true>), dim3(grid), dim3(NTHR), 0, ls, sop, rg, list, count, fcur, fnext, lnext, pm, dbg, 0u);
         };
     }
 };
@@ -1695,11 +1755,13 @@ static int tile_relax_run_pair(tdx_context* ctx, Op opA, tilek::Sched scA, Op op
 // active - their flags are then in sc.flags, where the next schedule (this function again, after a halo exchange has added its own activations) starts.
 // For multi-strip callers whose fronts are many and independent (the upstream closure of outlets): exchanging every few dozen rounds lets the fronts of
 // all strips advance side by side instead of strip-local fixed point after strip-local fixed point.
-template <class Op>
+// start (optional, with all_tiles): the operator of round 0 (RoundRunner::start_with).
+template <class Op, class StartOp = Op>
 static int tile_relax_run_bounded(tdx_context* ctx, Op op, tilek::TileGeom g, tilek::Sched sc, int max_rounds, bool* active_left, int64_t* rounds_out,
-                                  int64_t* launches_out, bool all_tiles = false) {
+                                  int64_t* launches_out, bool all_tiles = false, const StartOp* start = nullptr) {
     RoundRunner<Op> run(ctx, ctx->stream, op, g, sc, ctx->h_mail + TDX_MAIL_RUN_A, nullptr);
     run.all_tiles = all_tiles;
+    if constexpr (tilek::start_fill_of<StartOp>::value) { if (start) run.start_with(*start); }
     run.batch = run.batch_max = std::max(2, std::min(max_rounds, 64));
     static const int debug_level = getenv("TDX_DEBUG_ROUNDS") ? atoi(getenv("TDX_DEBUG_ROUNDS")) : 0;   // (as in tile_relax_run: active tiles per round on stderr)
     run.print_counts = debug_level > 0;
@@ -1725,8 +1787,10 @@ static int tile_relax_run_bounded(tdx_context* ctx, Op op, tilek::TileGeom g, ti
 // Runs the relaxation until no tile is active.  `flags` must hold the initially active tiles.
 // Default schedule: rounds.  TDX_RELAX_ASYNC=1 selects the asynchronous worklist (one launch); a worklist that gave
 // up on a bounded spin continues with rounds (values only ever decrease, so restarting from "all tiles active" is safe).
-template <class Op>
-static int tile_relax_run(tdx_context* ctx, Op op, tilek::TileGeom g, tilek::Sched sc, int64_t* rounds_out, int64_t* launches_out, bool all_tiles = false) {
+// start (optional, with all_tiles): the operator of round 0 (RoundRunner::start_with); the round schedule is then taken whatever TDX_RELAX_ASYNC says.
+template <class Op, class StartOp = Op>
+static int tile_relax_run(tdx_context* ctx, Op op, tilek::TileGeom g, tilek::Sched sc, int64_t* rounds_out, int64_t* launches_out, bool all_tiles = false,
+                          const StartOp* start = nullptr) {
     using namespace tilek;
     hipStream_t s = ctx->stream;
     const int ntiles = g.tiles_x * g.tiles_y;
@@ -1744,7 +1808,8 @@ static int tile_relax_run(tdx_context* ctx, Op op, tilek::TileGeom g, tilek::Sch
     }
     int64_t rounds = 0, launches = 0;
     bool need_rounds = force_rounds;
-    if (!force_rounds) {
+    if (start != nullptr) need_rounds = true;   // (round 0 is the start operator's: the round schedule)
+    else if (!force_rounds) {
         bool gave_up = false;
         int rc = tile_relax_async_finish(ctx, s, op, g, sc, TDX_S_Q, ctx->h_mail, dbg, &gave_up);
         if (rc != TDX_OK) return rc;
@@ -1754,7 +1819,8 @@ static int tile_relax_run(tdx_context* ctx, Op op, tilek::TileGeom g, tilek::Sch
     }
     if (need_rounds) {
         RoundRunner<Op> run(ctx, s, op, g, sc, ctx->h_mail + TDX_MAIL_RUN_A, dbg);
-        run.all_tiles = all_tiles && force_rounds;   // (the worklist schedule starts from the flags)
+        run.all_tiles = all_tiles && (force_rounds || start != nullptr);   // (the worklist schedule starts from the flags)
+        if constexpr (tilek::start_fill_of<StartOp>::value) { if (start) run.start_with(*start); }
         run.print_counts = debug_level > 0;
         if (debug_level == 2) fprintf(stderr, "\nrounds(%d tiles):", ntiles);
         int rc = run.drive();
