@@ -674,6 +674,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* Line layers and CatchOutlets (host code throughout): likewise */
 #include "taudem_amd_catchoutlets.h"
 
+/* Watershed polygons (compute entry points, the ring builder, the polygon layer and the file-level tool function): likewise */
+#include "taudem_amd_polygonize.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -408,6 +408,33 @@ NET_FIELDS = (("LINKNO", 0, 6, 0), ("DSLINKNO", 0, 6, 0), ("USLINKNO1", 0, 6, 0)
 NET_TREE_COLUMN = {"LINKNO": 0, "DSLINKNO": 3, "USLINKNO1": 4, "USLINKNO2": 5, "DSNODEID": 7, "strmOrder": 6, "Magnitude": 8, "WSNO": 0}   # of the -tree file
 CATCHOUTLETS_FIELDS = (("LINKNO", 0, 6, 0), ("DSLINKNO", 0, 6, 0), ("USLINKNO1", 0, 6, 0), ("USLINKNO2", 0, 6, 0), ("DOUTEND", 1, 16, 1), ("Id", 0, 10, 0))
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_polygonize.h declares, the tenth extension header
+_POLYGONIZE_SIGNATURES = {
+    # ctx, w, nx, ny, w_nodata, &polygons, stats
+    "tdx_polygonize": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    "tdx_polygonize_dev": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    # ctx, comm, w, nx, ny_local, row0, ny_total, w_nodata, &part, stats
+    "tdx_polygonize_edges_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    # keys, next_keys, ids, n, &part
+    "tdx_polygonize_edges_create": (C.c_int, [_P, _P, _P, _I64, C.POINTER(_P)]),
+    "tdx_polygonize_edges_count": (_I64, [_P]),
+    # part, keys, next_keys, ids, phase_ms
+    "tdx_polygonize_edges_copy": (None, [_P] * 5),
+    "tdx_polygonize_edges_free": (None, [_P]),
+    # parts, n_parts, nx, ny, &polygons
+    "tdx_polygonize_rings": (C.c_int, [_P, _I64, _I64, _I64, C.POINTER(_P)]),
+    # polygons, &n_polygons, &n_rings, &n_vertices, &n_edges
+    "tdx_polygons_count": (_I64, [_P] + [C.POINTER(_I64)] * 4),
+    # polygons, ids, cells, poly_first, ring_first, vert_first, vertices, phase_ms
+    "tdx_polygons_copy": (None, [_P] * 8),
+    "tdx_polygons_free": (None, [_P]),
+    # path, polygons, gt
+    "tdx_polygons_write": (C.c_int, [C.c_char_p, _P, _P]),
+    "tdx_tool_watershedgridtoshp": (C.c_int, [C.c_char_p] * 2),
+}
+POLYGONIZE_SYMBOLS = tuple(_POLYGONIZE_SIGNATURES)
+POLYGONIZE_PHASES = ("count", "scan", "emit", "download", "rings")
+
 _lib = None
 
 
@@ -432,7 +459,8 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
-                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES, **_EDITRASTER_SIGNATURES, **_CATCHOUTLETS_SIGNATURES}.items():
+                                   **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES, **_EDITRASTER_SIGNATURES, **_CATCHOUTLETS_SIGNATURES,
+                                   **_POLYGONIZE_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -287,7 +287,18 @@ class _EditRasterStage:
         return _ret(_editraster(_Call(self), raster, cols, rows, vals, nodata, out), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage, _EditRasterStage):
+class _PolygonizeStage:
+    """Context.polygonize; its entry points are those of include/taudem_amd_polygonize.h."""
+
+    def polygonize(self, w, nodata=-2147483647, *, stats=False):
+        """polygons = polygonize(w): the watershed polygons of the id grid w (int32; every value that is not nodata is an id), what the toolbox step
+        "Watershed Grid To Shapefile" makes of the w grid of streamnet or gagewatershed.  The boundary edges come off the device (a tensor is read where
+        it is), the rings are closed on the host.  Returns a Polygons object: numpy arrays and write(path, geotransform); it owns a handle of the
+        library, so use it as a context manager or close() it."""
+        return _ret(_polygonize(_Call(self), w, nodata), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage, _EditRasterStage, _PolygonizeStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -995,6 +1006,110 @@ class StreamNetLinks:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _polygonize(f, w, nodata):
+    pw = f.raster(w, np.int32, "w")
+    handle = C.c_void_p()
+    st = f.call("tdx_polygonize", pw, f.nx, f.ny, int(nodata), C.byref(handle))
+    return Polygons(handle=handle), st
+
+
+def _polygonize_edges_strip(f, w, row0, ny_total, nodata):
+    """A strip's part of the boundary edges (a handle: Polygons takes the parts of all strips).  The halo rows of w are the caller's: they hold the
+    neighbouring strips' rows, are read, and are not written."""
+    pw = f.raster(w, np.int32, "w")
+    part = C.c_void_p()
+    st = f.call("tdx_polygonize_edges", pw, f.nx, f.ny, int(row0), int(ny_total), int(nodata), C.byref(part))
+    return part, st
+
+
+def polygonize_edges(part):
+    """keys, next_keys (int64) and ids (int32) of a part of boundary edges (StripPipeline.polygonize_edges)."""
+    lib = _lib.load()
+    n = int(lib.tdx_polygonize_edges_count(part))
+    keys, nxt, ids = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+    lib.tdx_polygonize_edges_copy(part, _v(keys), _v(nxt), _v(ids), None)
+    return keys, nxt, ids
+
+
+def polygonize_edges_create(keys, next_keys, ids):
+    """A part of boundary edges from arrays (host code): what drives the ring builder without a device."""
+    lib = _lib.load()
+    keys, nxt, ids = _flat(keys, np.int64), _flat(next_keys, np.int64), _flat(ids, np.int32)
+    if not (keys.size == nxt.size == ids.size):
+        raise ValueError("polygonize_edges_create: need three arrays of one length")
+    part = C.c_void_p()
+    n = int(keys.size)
+    check(lib.tdx_polygonize_edges_create(_v(keys) if n else None, _v(nxt) if n else None, _v(ids) if n else None, n, C.byref(part)))
+    return part
+
+
+class Polygons:
+    """The watershed polygons of an id grid: of Context.polygonize (handle=), or from the edge parts of ALL strips of a raster in strip order
+    (parts=, nx=, ny=: StripPipeline.polygonize_edges; host code, no device).  features -> polygons -> rings -> vertices as offset lists:
+    ids int32 [F] ascending; cells int64 [F]; poly_first int64 [F + 1]; ring_first int64 [P + 1] (the outer ring of a polygon first, then its holes);
+    vert_first int64 [R + 1]; vertices int32 [V, 2] (column, row), every ring closed; phases: the milliseconds of count, scan, emit, download, rings.
+    Owns its handle and the parts: close() frees them."""
+
+    def __init__(self, handle=None, parts=None, nx=None, ny=None):
+        self._lib = _lib.load()
+        self.parts = list(parts) if parts is not None else []
+        if handle is None:
+            if not self.parts or nx is None or ny is None:
+                raise ValueError("Polygons: need a handle, or parts with nx and ny")
+            arr = (C.c_void_p * len(self.parts))(*[p.value for p in self.parts])
+            handle = C.c_void_p()
+            check(self._lib.tdx_polygonize_rings(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), C.byref(handle)))
+        self.handle = handle
+        lib = self._lib
+        npoly, nring, nvert, nedge = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        nf = int(lib.tdx_polygons_count(handle, C.byref(npoly), C.byref(nring), C.byref(nvert), C.byref(nedge)))
+        self.edges = int(nedge.value)
+        self.ids, self.cells = np.zeros(nf, np.int32), np.zeros(nf, np.int64)
+        self.poly_first, self.ring_first = np.zeros(nf + 1, np.int64), np.zeros(npoly.value + 1, np.int64)
+        self.vert_first, self.vertices = np.zeros(nring.value + 1, np.int64), np.zeros((nvert.value, 2), np.int32)
+        ms = np.zeros(len(_lib.POLYGONIZE_PHASES), np.float64)
+        lib.tdx_polygons_copy(handle, _v(self.ids), _v(self.cells), _v(self.poly_first), _v(self.ring_first), _v(self.vert_first), _v(self.vertices), _v(ms))
+        self.phases = dict(zip(_lib.POLYGONIZE_PHASES, ms.tolist()))
+
+    def features(self):
+        """[(id, cells, [polygon, ...])] with polygon = [ring, ...] (the outer ring first) and ring = [(column, row), ...], closed."""
+        out = []
+        for f in range(self.ids.size):
+            polys = []
+            for p in range(self.poly_first[f], self.poly_first[f + 1]):
+                polys.append([[tuple(int(v) for v in xy) for xy in self.vertices[self.vert_first[q]:self.vert_first[q + 1]]]
+                              for q in range(self.ring_first[p], self.ring_first[p + 1])])
+            out.append((int(self.ids[f]), int(self.cells[f]), polys))
+        return out
+
+    def write(self, path, geotransform=(0.0, 1.0, 0.0, 0.0, 0.0, -1.0)):
+        """The polygon layer (tdx_polygons_write): ESRI shapefile or GeoJSON by the extension of path, x = gt[0] + column * gt[1], y = gt[3] + row * gt[5]."""
+        gt = np.asarray([float(v) for v in geotransform], np.float64)
+        if gt.size != 6:
+            raise ValueError("geotransform: need GDAL's six numbers")
+        check(self._lib.tdx_polygons_write(os.fsencode(path), self.handle, _v(gt)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.tdx_polygons_free(self.handle)
+            self.handle = None
+            for p in self.parts:
+                self._lib.tdx_polygonize_edges_free(p)
+            self.parts = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def polygonize(w, nodata=-2147483647, device=0, **kw):
+    """Context(device).polygonize(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.polygonize(w, nodata, **kw)
 
 
 def _point_lists(outlets):

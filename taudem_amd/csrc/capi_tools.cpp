@@ -1908,4 +1908,54 @@ int tdx_tool_catchoutlets(const char* pfile, const char* streamnetsrc, const cha
     return 0;
 }
 
+// Watershed Grid To Shapefile (pyfiles/WatershedGridToShapefile.py: arcpy.RasterToPolygon_conversion(w, shp, "NO_SIMPLIFY", "Value")).  With --gpus N
+// every rank uploads its rows WITH the neighbouring strips' rows as halo rows (the host holds the whole raster: no exchange), takes the edges of its
+// owned rows, and rank 0 closes the rings over the parts in strip order.
+int tdx_tool_watershedgridtoshp(const char* wfile, const char* polyfile) {
+    if (!wfile || !polyfile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_watershedgridtoshp: bad argument");
+    if (tdx::layer_kind(polyfile) == tdx::LayerKind::None) return refuse_layer("watershedgridtoshp", polyfile);
+    ToolRun t("WatershedGridToShapefile");
+    Raster w;
+    t.input(wfile, I32, w);
+    if (t.rc == TDX_OK) { fprintf(stderr, "Time estimate not available.\n"); fflush(stderr); }
+    if (!t.read_done()) return t.rc;
+    const int64_t nx = w.info.nx, ny = w.info.ny;
+    const int32_t w_nd = (int32_t)w.info.nodata;
+    tdx_polygons* polys = nullptr;
+    const int nranks = int(std::max<int64_t>(1, std::min<int64_t>(tool_gpus(), ny)));
+    RankMeet meet; meet.n = nranks;
+    std::atomic<int> failed{0};
+    std::vector<tdx_polygonize_edges*> parts(size_t(nranks), nullptr);
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) { return tdx_polygonize(c, w.l.data(), nx, ny, w_nd, &polys, s); },
+        [&](RankJob& j, tdx_stats* s) {
+            int32_t* d_w = j.strip<int32_t>(nullptr);
+            int e = d_w ? TDX_OK : TDX_ERR_NOMEM;
+            if (e == TDX_OK) {   // rows y0 - 1 .. y1 of the raster, as far as they exist
+                const int64_t r0 = std::max<int64_t>(j.y0 - 1, 0), r1 = std::min<int64_t>(j.y1 + 1, j.ny);
+                if (hipMemcpyAsync(d_w + size_t(r0 - (j.y0 - 1)) * size_t(nx), w.l.data() + size_t(r0) * size_t(nx), size_t(r1 - r0) * size_t(nx) * 4, hipMemcpyHostToDevice,
+                                   j.ctx->stream) != hipSuccess)
+                    e = TDX_ERR_HIP;
+            }
+            if (e == TDX_OK) e = tdx_polygonize_edges_strip(j.ctx, j.comm, d_w, j.nx, j.nyl, j.y0, j.ny, w_nd, &parts[size_t(j.rank)], s);
+            if (e != TDX_OK) failed = e;
+            meet.wait();
+            if (failed == 0 && j.rank == 0) {
+                const int em = tdx_polygonize_rings(parts.data(), j.size, nx, ny, &polys);
+                if (em != TDX_OK) { failed = em; e = em; }
+            }
+            meet.wait();
+            return e != TDX_OK ? e : int(failed);
+        });
+    for (tdx_polygonize_edges* part : parts) tdx_polygonize_edges_free(part);
+    if (!ok) { tdx_polygons_free(polys); return t.rc; }
+    int64_t np = 0, nr = 0, nv = 0;
+    const int64_t nf = tdx_polygons_count(polys, &np, &nr, &nv, nullptr);
+    const int wrc = tdx_polygons_write(polyfile, polys, w.info.gt);
+    tdx_polygons_free(polys);
+    if (wrc != TDX_OK) { printf("Error opening file %s.\n", polyfile); fflush(stdout); return wrc; }
+    printf("Polygons: %lld features, %lld polygons, %lld rings, %lld vertices\n", (long long)nf, (long long)np, (long long)nr, (long long)nv);
+    return t.finish("Processes", "watershedgridtoshp");
+}
+
 }  // extern "C"

@@ -14,6 +14,7 @@
 namespace tdx {
 const char* const kLayerKindsMessage = "supported point layers: ESRI shapefile (.shp) and GeoJSON (.json, .geojson)";
 const char* const kLineLayerKindsMessage = "supported line layers: ESRI shapefile (.shp) and GeoJSON (.json, .geojson)";
+const char* const kPolygonLayerKindsMessage = "supported polygon layers: ESRI shapefile (.shp) and GeoJSON (.json, .geojson)";
 
 namespace {
 std::string lower_ext(const std::string& p) {
@@ -165,6 +166,43 @@ bool write_line_shapefile(const std::string& path, const LineLayer& L, std::stri
         for (double v : b.b) put_le64f(shp, v);
         put_le32(shp, 1); put_le32(shp, uint32_t(np)); put_le32(shp, 0);
         for (size_t k = 0; k < np; k++) { put_le64f(shp, L.x[i][k]); put_le64f(shp, L.y[i][k]); }
+        at += 4 + len;
+    }
+    return dbf_bytes(L, n, dbf, err) && spill(path, shp, err) && spill(with_ext(path, ".shx"), shx, err) && spill(with_ext(path, ".dbf"), dbf, err);
+}
+
+// Polygon records: shape type, box, the part and point counts, the first point of every part (ring), the points - 22 + 2 * parts + 8 * points 16-bit words each
+bool write_polygon_shapefile(const std::string& path, const PolygonLayer& L, std::string& err) {
+    const size_t n = L.polygons.size();
+    size_t words = 50;
+    Box all;
+    std::vector<size_t> nparts(n, 0), npoints(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        for (const PolygonLayer::Polygon& pg : L.polygons[i])
+            for (const PolygonLayer::Ring& rg : pg) { nparts[i]++; npoints[i] += rg.x.size(); all.add(rg.x, rg.y); }
+        if (npoints[i] > 0x7000000u) { err = "too many vertices for a shapefile"; return false; }
+        words += 4 + 22 + 2 * nparts[i] + 8 * npoints[i];
+    }
+    if (n > 0x7000000u || words > 0x7fffffffu) { err = "too many vertices for a shapefile"; return false; }
+    std::string shp = shape_header(uint32_t(words), 5, all), shx = shape_header(uint32_t(50 + 4 * n), 5, all), dbf;
+    shp.reserve(words * 2);
+    size_t at = 50;
+    for (size_t i = 0; i < n; i++) {
+        const size_t len = 22 + 2 * nparts[i] + 8 * npoints[i];
+        put_be32(shx, uint32_t(at)); put_be32(shx, uint32_t(len));
+        put_be32(shp, uint32_t(i + 1)); put_be32(shp, uint32_t(len));
+        put_le32(shp, 5);
+        Box b;
+        for (const PolygonLayer::Polygon& pg : L.polygons[i])
+            for (const PolygonLayer::Ring& rg : pg) b.add(rg.x, rg.y);
+        for (double v : b.b) put_le64f(shp, v);
+        put_le32(shp, uint32_t(nparts[i])); put_le32(shp, uint32_t(npoints[i]));
+        size_t first = 0;
+        for (const PolygonLayer::Polygon& pg : L.polygons[i])
+            for (const PolygonLayer::Ring& rg : pg) { put_le32(shp, uint32_t(first)); first += rg.x.size(); }
+        for (const PolygonLayer::Polygon& pg : L.polygons[i])
+            for (const PolygonLayer::Ring& rg : pg)
+                for (size_t k = 0; k < rg.x.size(); k++) { put_le64f(shp, rg.x[k]); put_le64f(shp, rg.y[k]); }
         at += 4 + len;
     }
     return dbf_bytes(L, n, dbf, err) && spill(path, shp, err) && spill(with_ext(path, ".shx"), shx, err) && spill(with_ext(path, ".dbf"), dbf, err);
@@ -430,6 +468,34 @@ bool write_line_geojson(const std::string& path, const LineLayer& L, std::string
     return spill(path, o, err);
 }
 
+// the rings of one polygon, each reversed (RFC 7946)
+void polygon_json(std::string& o, const PolygonLayer::Polygon& pg) {
+    o += "[ ";
+    for (size_t q = 0; q < pg.size(); q++) {
+        o += q ? ", [ " : "[ ";
+        for (size_t k = pg[q].x.size(); k-- > 0;) { o += position(pg[q].x[k], pg[q].y[k]); if (k) o += ", "; }
+        o += " ]";
+    }
+    o += " ]";
+}
+bool write_polygon_geojson(const std::string& path, const PolygonLayer& L, std::string& err) {
+    std::string o = "{\n\"type\": \"FeatureCollection\",\n\"features\": [\n";
+    const size_t n = L.polygons.size();
+    for (size_t i = 0; i < n; i++) {
+        const std::vector<PolygonLayer::Polygon>& f = L.polygons[i];
+        o += feature_head(L, i);
+        if (f.size() == 1) { o += "\"Polygon\", \"coordinates\": "; polygon_json(o, f[0]); }
+        else {
+            o += "\"MultiPolygon\", \"coordinates\": [ ";
+            for (size_t p = 0; p < f.size(); p++) { if (p) o += ", "; polygon_json(o, f[p]); }
+            o += " ]";
+        }
+        o += std::string(" } }") + (i + 1 < n ? ",\n" : "\n");
+    }
+    o += "]\n}\n";
+    return spill(path, o, err);
+}
+
 // in document order, the features whose geometry is a LineString (or a MultiLineString: its first part)
 void collect_line_features(const JVal& v, std::vector<const JVal*>& feats, std::vector<const JVal*>& coords) {
     if (v.kind == JVal::Object) {
@@ -510,6 +576,11 @@ void PointLayer::resize(size_t n) {
     values.resize(n);
     for (auto& row : values) row.resize(fields.size());
 }
+void PolygonLayer::resize(size_t n) {
+    polygons.assign(n, {});
+    values.resize(n);
+    for (auto& row : values) row.resize(fields.size());
+}
 void LineLayer::resize(size_t n) {
     x.assign(n, {}); y.assign(n, {});
     values.resize(n);
@@ -554,6 +625,21 @@ bool write_line_layer(const std::string& path, const LineLayer& L, std::string& 
     case LayerKind::Shapefile: return write_line_shapefile(path, L, err);
     case LayerKind::GeoJSON: return write_line_geojson(path, L, err);
     default: err = std::string("unsupported output ") + path + ": " + kLineLayerKindsMessage; return false;
+    }
+}
+
+bool write_polygon_layer(const std::string& path, const PolygonLayer& L, std::string& err) {
+    if (L.values.size() != L.polygons.size()) { err = "polygon layer: columns of different length"; return false; }
+    for (size_t i = 0; i < L.polygons.size(); i++) {
+        if (L.values[i].size() != L.fields.size()) { err = "polygon layer: a feature without all fields"; return false; }
+        for (const PolygonLayer::Polygon& pg : L.polygons[i])
+            for (const PolygonLayer::Ring& rg : pg)
+                if (rg.x.size() != rg.y.size()) { err = "polygon layer: a ring with unpaired coordinates"; return false; }
+    }
+    switch (layer_kind(path)) {
+    case LayerKind::Shapefile: return write_polygon_shapefile(path, L, err);
+    case LayerKind::GeoJSON: return write_polygon_geojson(path, L, err);
+    default: err = std::string("unsupported output ") + path + ": " + kPolygonLayerKindsMessage; return false;
     }
 }
 

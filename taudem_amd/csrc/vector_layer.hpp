@@ -6,6 +6,7 @@
 //                   default to: Integer 9 (widened to the longest value), Real 24 with 15 decimals, String 80.  No .prj: the GeoTIFF reader keeps no WKT.
 //   GeoJSON         .json / .geojson, a FeatureCollection of Point or LineString features with properties; coordinates and Real values with 17
 //                   significant digits.
+// The watershed polygons (polygonize.hip) are a third geometry, written only: shape type Polygon with every ring a part, GeoJSON Polygon / MultiPolygon.
 // Any other extension is refused (layer_kind() == LayerKind::None) before a tool reads anything.
 // Carry-over: a field read from a .dbf keeps its 32-byte descriptor and the bytes of every record, so that .dbf -> .dbf is byte-faithful per column;
 // across formats N / F with 0 decimals is Integer, N / F with decimals Real, anything else String.
@@ -43,9 +44,19 @@ struct LineLayer : LayerTable {
     void resize(size_t n);   // n features, without vertices
 };
 
+// features -> polygons -> rings -> vertices.  A ring repeats its first vertex at its end; the outer ring of a polygon comes first and runs clockwise
+// (the shapefile convention), its holes follow and run counter-clockwise.
+struct PolygonLayer : LayerTable {
+    struct Ring { std::vector<double> x, y; };
+    typedef std::vector<Ring> Polygon;
+    std::vector<std::vector<Polygon>> polygons;   // [feature][polygon][ring]
+    void resize(size_t n);   // n features, without polygons
+};
+
 LayerKind layer_kind(const std::string& path);
 extern const char* const kLayerKindsMessage;   // names the two supported kinds
 extern const char* const kLineLayerKindsMessage;
+extern const char* const kPolygonLayerKindsMessage;
 // All fields of an outlet source, one row per feature that read_outlets() returns for the same file (n_features of them, else an error): the
 // descriptors and records of the .dbf next to a .shp, the properties of GeoJSON Point features, the id column of a text file (an Integer field "id").
 bool read_point_fields(const std::string& path, size_t n_features, PointLayer& layer, std::string& err);
@@ -55,6 +66,10 @@ bool write_line_layer(const std::string& path, const LineLayer& layer, std::stri
 // Shapefile: shape types 3, 13 and 23 (Z and M are ignored, of several parts the first is taken, a null shape is a line without vertices) with the .dbf
 // next to it.  GeoJSON: the LineString features in document order (of a MultiLineString the first part) with their properties.
 bool read_line_layer(const std::string& path, LineLayer& layer, std::string& err);
-// the files write_point_layer(path) / write_line_layer(path) create
+// Shapefile: shape type 5 (Polygon), every ring of a feature a part, in the layer's order.  GeoJSON: a Polygon for a feature of one polygon, else a
+// MultiPolygon; every ring is written REVERSED (RFC 7946: exterior rings counter-clockwise, holes clockwise), from and to the same start vertex.  A layer
+// without features is a valid empty file.
+bool write_polygon_layer(const std::string& path, const PolygonLayer& layer, std::string& err);
+// the files write_point_layer(path) / write_line_layer(path) / write_polygon_layer(path) create
 std::vector<std::string> layer_files(const std::string& path);
 }  // namespace tdx

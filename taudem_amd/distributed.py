@@ -392,8 +392,18 @@ class _StripEditRasterStage:
         return api._editraster(self._call(), raster, cols, rows, vals, nodata, out, row0=row0)
 
 
+class _StripPolygonizeStage:
+    """StripPipeline.polygonize_edges (include/taudem_amd_polygonize.h).  Nothing is exchanged: the CALLER fills the halo rows of w with the neighbouring
+    strips' rows; they are read and never written.  The parts of all strips meet in taudem_amd.api.Polygons (strip order = key order)."""
+
+    def polygonize_edges(self, w, row0, ny_total, nodata=-2147483647):
+        """part = polygonize_edges(w, row0, ny_total) on this strip: the handle of the boundary edges of its owned rows, with the keys of the whole raster.
+        A halo row that lies outside rows 0 .. ny_total - 1 is off the raster whatever it holds."""
+        return api._polygonize_edges_strip(self._call(), w, row0, ny_total, nodata)
+
+
 class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage, _StripTerrainIndexStage,
-                    _StripEditRasterStage):
+                    _StripEditRasterStage, _StripPolygonizeStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

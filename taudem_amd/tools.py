@@ -231,6 +231,12 @@ def catchoutlets(pfile, streamnetsrc="", outletsdatasrc="", mindist=0.0, gwstart
     return _lib.load().tdx_tool_catchoutlets(_b(pfile), _b(streamnetsrc), _b(treefile), _b(coordfile), _b(outletsdatasrc), float(mindist), int(gwstartno), float(minarea))
 
 
+def watershedgridtoshp(wfile, polyfile):
+    """pyfiles/WatershedGridToShapefile.py (the toolbox step Watershed Grid To Shapefile): the polygons of the watershed grid wfile (read as int32) as a
+    shapefile (.shp) or GeoJSON (.json / .geojson) polygon layer with the fields gridcode and cells; any other output is refused before anything is read."""
+    return _lib.load().tdx_tool_watershedgridtoshp(_b(wfile), _b(polyfile))
+
+
 twi = twigrid
 slopearearatio = atanbgrid
 
