@@ -677,6 +677,9 @@ int tdx_tool_set_gpus(int ngpus);
 /* Watershed polygons (compute entry points, the ring builder, the polygon layer and the file-level tool function): likewise */
 #include "taudem_amd_polygonize.h"
 
+/* The SINMAP parameter region grid (polygons, resampling or one region to the calibration grid; the region table): likewise */
+#include "taudem_amd_regions.h"
+
 #ifdef __cplusplus
 }
 #endif

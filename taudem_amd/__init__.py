@@ -14,5 +14,6 @@ from .api import lengtharea, setregion, terrain_indices  # noqa: F401
 from .api import editraster, read_changes  # noqa: F401
 from .api import catchoutlets, read_lines, streamnet_net, write_lines  # noqa: F401
 from .api import Polygons, polygonize  # noqa: F401
+from .api import PackedPolygons, PolygonLayer, read_polygons, regiongrid, write_calpar  # noqa: F401
 
 __version__ = "0.1.0"

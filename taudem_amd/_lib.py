@@ -435,6 +435,42 @@ _POLYGONIZE_SIGNATURES = {
 POLYGONIZE_SYMBOLS = tuple(_POLYGONIZE_SIGNATURES)
 POLYGONIZE_PHASES = ("count", "scan", "emit", "download", "rings")
 
+# name -> (restype, argtypes): the symbols include/taudem_amd_regions.h declares, the eleventh extension header
+_RG_POLYGONS = [_P, _P, _P, _I64, _P, _P, _I64, _P, _I64]   # x, y, ring_first, n_rings, feature_first, values, n_features, gt, workspace_words
+_RG_SOURCE = [_P, _I64, _I64, _P, _I32, _P]                  # src, snx, sny, sgt, src_nodata, gt
+_REGIONS_SIGNATURES = {
+    # ctx, [comm,] polygons..., nx, ny [ny_local, row0, ny_total], out, ids, &n_ids, phase_ms, &workspace_bytes, stats
+    "tdx_regiongrid": (C.c_int, [_P] + _RG_POLYGONS + [_I64, _I64, _P, _P, C.POINTER(_I32), _P, C.POINTER(_I64), _P]),
+    "tdx_regiongrid_dev": (C.c_int, [_P] + _RG_POLYGONS + [_I64, _I64, _P, _P, C.POINTER(_I32), _P, C.POINTER(_I64), _P]),
+    "tdx_regiongrid_strip": (C.c_int, [_P, _P] + _RG_POLYGONS + [_I64, _I64, _I64, _I64, _P, _P, C.POINTER(_I32), _P, C.POINTER(_I64), _P]),
+    # ctx, [comm,] source..., nx, ny [ny_local, row0, ny_total], out, ids, &n_ids, phase_ms, stats
+    "tdx_regiongrid_resample": (C.c_int, [_P] + _RG_SOURCE + [_I64, _I64, _P, _P, C.POINTER(_I32), _P, _P]),
+    "tdx_regiongrid_resample_dev": (C.c_int, [_P] + _RG_SOURCE + [_I64, _I64, _P, _P, C.POINTER(_I32), _P, _P]),
+    "tdx_regiongrid_resample_strip": (C.c_int, [_P, _P] + _RG_SOURCE + [_I64, _I64, _I64, _I64, _P, _P, C.POINTER(_I32), _P, _P]),
+    # ctx, [comm,] nx, ny [ny_local, row0, ny_total], out, ids, &n_ids, stats
+    "tdx_regiongrid_constant": (C.c_int, [_P, _I64, _I64, _P, _P, C.POINTER(_I32), _P]),
+    "tdx_regiongrid_constant_dev": (C.c_int, [_P, _I64, _I64, _P, _P, C.POINTER(_I32), _P]),
+    "tdx_regiongrid_constant_strip": (C.c_int, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, C.POINTER(_I32), _P]),
+    # path, ids, n_ids, seven_texts
+    "tdx_regiongrid_write_calpar": (C.c_int, [C.c_char_p, _P, _I32, _P]),
+    # path, &layer
+    "tdx_polygon_layer_read": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
+    # layer, &n_rings, &n_vertices, &n_fields
+    "tdx_polygon_layer_count": (_I64, [_P] + [C.POINTER(_I64)] * 3),
+    # layer, feature_first, ring_first, x, y
+    "tdx_polygon_layer_copy": (None, [_P] * 5),
+    "tdx_polygon_layer_field": (C.c_char_p, [_P, _I64]),
+    "tdx_polygon_layer_value": (C.c_char_p, [_P, _I64, _I64]),
+    # layer, field, values
+    "tdx_polygon_layer_values": (C.c_int, [_P, C.c_char_p, _P]),
+    "tdx_polygon_layer_free": (None, [_P]),
+    # dem, parreg, att, parreg_in, shp, shp_att_name, seven_texts
+    "tdx_tool_siregiontool": (C.c_int, [C.c_char_p] * 6 + [_P]),
+}
+REGIONS_SYMBOLS = tuple(_REGIONS_SIGNATURES)
+REGIONGRID_PHASES = ("prepare", "cross", "fill", "write")
+REGIONGRID_MAX_IDS = 32767
+
 _lib = None
 
 
@@ -460,7 +496,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**_SIGNATURES, **_DROPAN_SIGNATURES, **_PEUKER_SIGNATURES, **_AD8_SIGNATURES, **_STREAMNET_SIGNATURES,
                                    **_OUTLETS_SIGNATURES, **_SINMAP_SIGNATURES, **_INDICES_SIGNATURES, **_EDITRASTER_SIGNATURES, **_CATCHOUTLETS_SIGNATURES,
-                                   **_POLYGONIZE_SIGNATURES}.items():
+                                   **_POLYGONIZE_SIGNATURES, **_REGIONS_SIGNATURES}.items():
         fn = getattr(lib, name)   # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -298,7 +298,23 @@ class _PolygonizeStage:
         return _ret(_polygonize(_Call(self), w, nodata), stats)
 
 
-class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage, _EditRasterStage, _PolygonizeStage):
+class _RegionGridStage:
+    """Context.regiongrid; its entry points are those of include/taudem_amd_regions.h."""
+
+    def regiongrid(self, shape, gt, polygons=None, values=None, source=None, source_gt=None, source_nodata=-2147483647, out=None, *, workspace_words=0,
+                   stats=False):
+        """grid, ids = regiongrid((ny, nx), gt): the SINMAP parameter region grid on the DEM's grid (pyfiles/SIRegionTool.py), int16 with nodata 0, and
+        the sorted values that occur in it.  polygons (with values, one in 1 .. 32767 per feature): a list of features, each a list of rings, each an
+        (n, 2) array of x, y; a cell takes the value of the last feature whose rings hold its centre by the even-odd rule.  source (int32, with
+        source_gt and source_nodata): an existing region grid, resampled by nearest neighbour without reprojection.  Neither: one region, 1 everywhere.
+        gt / source_gt: GDAL's six numbers, unrotated.  The grid is a numpy array, or a tensor on this device if out= or source is one.
+        workspace_words bounds the parity bitmap words of a batch of features (0: the library's default).  stats=True also asks for the phase times
+        (stats["phases"]), which drains the stream at the end of every phase of every batch; without it nothing is drained between the kernels."""
+        return _ret(_regiongrid(_Call(self), shape, gt, polygons, values, source, source_gt, source_nodata, out, workspace_words, phases=stats), stats)
+
+
+class Context(_DropAnalysisStage, _PeukerDouglasStage, _StreamNetStage, _OutletToolsStage, _SinmapStage, _TerrainIndexStage, _EditRasterStage, _PolygonizeStage,
+              _RegionGridStage):
     """Owns a HIP stream, a scratch arena and timing events on one device."""
 
     def __init__(self, device: int = 0):
@@ -1091,6 +1107,13 @@ class Polygons:
             raise ValueError("geotransform: need GDAL's six numbers")
         check(self._lib.tdx_polygons_write(os.fsencode(path), self.handle, _v(gt)))
 
+    def packed(self, geotransform=(0.0, 1.0, 0.0, 0.0, 0.0, -1.0)):
+        """The features as PackedPolygons in map coordinates (x = gt[0] + column * gt[1], y = gt[3] + row * gt[5]): what Context.regiongrid burns back
+        by the ids, without a file in between."""
+        gt = [float(v) for v in geotransform]
+        v = self.vertices.astype(np.float64)
+        return PackedPolygons(gt[0] + v[:, 0] * gt[1], gt[3] + v[:, 1] * gt[5], self.vert_first, self.ring_first[self.poly_first])
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.tdx_polygons_free(self.handle)
@@ -1110,6 +1133,179 @@ def polygonize(w, nodata=-2147483647, device=0, **kw):
     """Context(device).polygonize(...) for a single call."""
     with Context(device) as ctx:
         return ctx.polygonize(w, nodata, **kw)
+
+
+class PackedPolygons:
+    """Polygons as the flat arrays the library takes, for layers too large for lists: x, y float64 [vertices]; ring_first int64 [rings + 1] (the vertices
+    of a ring); feature_first int64 [features + 1] (the rings of a feature).  Context.regiongrid takes one as polygons=."""
+
+    def __init__(self, x, y, ring_first, feature_first):
+        self.x, self.y = _flat(x, np.float64), _flat(y, np.float64)
+        self.ring_first, self.feature_first = _flat(ring_first, np.int64), _flat(feature_first, np.int64)
+        if self.x.size != self.y.size or self.ring_first.size < 1 or self.feature_first.size < 1 or self.ring_first[-1] != self.x.size \
+                or self.feature_first[-1] != self.ring_first.size - 1:
+            raise ValueError("PackedPolygons: offsets that do not cover the vertices and rings")
+
+    def __len__(self):
+        return int(self.feature_first.size - 1)
+
+
+def _pack_polygons(polygons, values):
+    """x, y, ring_first, feature_first, values as the flat host arrays the library takes."""
+    if isinstance(polygons, PackedPolygons):
+        v64 = _flat(values, np.int64)
+        if v64.size != len(polygons):
+            raise ValueError("values: need one value per feature")
+        lim = np.iinfo(np.int32)
+        return polygons.x, polygons.y, polygons.ring_first, polygons.feature_first, np.ascontiguousarray(np.clip(v64, lim.min, lim.max).astype(np.int32))
+    xs, ys, ring_first, feature_first = [], [], [0], [0]
+    for feat in polygons:
+        for ring in feat:
+            r = np.asarray(ring, np.float64).reshape(-1, 2)
+            xs.append(r[:, 0])
+            ys.append(r[:, 1])
+            ring_first.append(ring_first[-1] + r.shape[0])
+        feature_first.append(len(ring_first) - 1)
+    x = np.ascontiguousarray(np.concatenate(xs)) if xs else np.zeros(0, np.float64)
+    y = np.ascontiguousarray(np.concatenate(ys)) if ys else np.zeros(0, np.float64)
+    v64 = _flat(values, np.int64)
+    if v64.size != len(feature_first) - 1:
+        raise ValueError("values: need one value per feature")
+    lim = np.iinfo(np.int32)   # a value beyond int32 is for the library to refuse: it keeps that meaning after the clip
+    return x, y, np.asarray(ring_first, np.int64), np.asarray(feature_first, np.int64), np.ascontiguousarray(np.clip(v64, lim.min, lim.max).astype(np.int32))
+
+
+def _gt6(gt, name):
+    g = np.ascontiguousarray(np.asarray([float(v) for v in gt], np.float64))
+    if g.size != 6:
+        raise ValueError(f"{name}: need GDAL's six numbers")
+    return g
+
+
+def _regiongrid(f, shape, gt, polygons, values, source, source_gt, source_nodata, out, workspace_words=0, row0=None, ny_total=None, phases=False):
+    """row0, ny_total: a strip's first owned row and the raster's rows (gt is the whole raster's); None for a Context.  phases: ask for the phase times."""
+    if polygons is not None and source is not None:
+        raise ValueError("regiongrid: polygons and source exclude each other")
+    g = _gt6(gt, "gt")
+    f.keep.append(g)
+    if not f.strip:
+        ny, nx = (int(v) for v in shape)
+        if nx <= 0 or ny <= 0:
+            raise ValueError("shape: need (ny, nx) > 0")
+        f.shape = (ny, nx)
+    if out is None:
+        if f.strip or _is_torch(source):
+            import torch
+
+            out = torch.empty(f.shape, dtype=torch.int16, device=f"cuda:{f.ctx.device}")
+        else:
+            out = np.empty(f.shape, np.int16)
+    po = f.raster(out, np.int16, "out")
+    where = (f.nx, f.ny) if row0 is None else (f.nx, f.ny, int(row0), int(ny_total))
+    ids, n_ids = np.zeros(_lib.REGIONGRID_MAX_IDS, np.int32), C.c_int32(0)
+    ms, ws = np.zeros(len(_lib.REGIONGRID_PHASES), np.float64), C.c_int64(0)
+    pms = _v(ms) if phases else None
+    if polygons is not None:
+        if values is None:
+            raise ValueError("regiongrid: polygons need values")
+        x, y, ring_first, feature_first, vals = _pack_polygons(polygons, values)
+        f.keep += [x, y, ring_first, feature_first, vals]
+        st = f.call("tdx_regiongrid", _v(x) if x.size else None, _v(y) if y.size else None, _v(ring_first), int(ring_first.size - 1), _v(feature_first),
+                    _v(vals) if vals.size else None, int(vals.size), _v(g), int(workspace_words), *where, po, _v(ids), C.byref(n_ids), pms, C.byref(ws))
+    elif source is not None:
+        if source_gt is None:
+            raise ValueError("regiongrid: source needs source_gt")
+        sg = _gt6(source_gt, "source_gt")
+        dev = _is_torch(source)
+        if dev != f.dev:
+            raise ValueError("source: all rasters must be on the same side (host or device)")
+        if dev:
+            if not source.is_cuda or source.device.index != f.ctx.device or source.dtype != _torch_dtype(np.int32) or not source.is_contiguous() or source.dim() != 2:
+                raise ValueError(f"source: need a contiguous 2-D int32 tensor on cuda:{f.ctx.device}")
+            ps = C.c_void_p(source.data_ptr())
+        else:
+            if not isinstance(source, np.ndarray) or source.dtype != np.int32 or not source.flags.c_contiguous or source.ndim != 2:
+                raise ValueError("source: need a C-contiguous 2-D numpy int32 array")
+            ps = C.c_void_p(source.ctypes.data)
+        sny, snx = (int(v) for v in source.shape)
+        f.keep += [sg, source]
+        st = f.call("tdx_regiongrid_resample", ps, snx, sny, _v(sg), int(source_nodata), _v(g), *where, po, _v(ids), C.byref(n_ids), pms)
+    else:
+        st = f.call("tdx_regiongrid_constant", *where, po, _v(ids), C.byref(n_ids))
+    if phases:
+        st["phases"] = dict(zip(_lib.REGIONGRID_PHASES, ms.tolist()))
+    st["workspace_bytes"] = int(ws.value)
+    return out, ids[:n_ids.value].copy(), st
+
+
+def regiongrid(shape, gt, polygons=None, values=None, source=None, source_gt=None, source_nodata=-2147483647, device=0, **kw):
+    """Context(device).regiongrid(...) for a single call."""
+    with Context(device) as ctx:
+        return ctx.regiongrid(shape, gt, polygons, values, source, source_gt, source_nodata, **kw)
+
+
+class PolygonLayer:
+    """A polygon layer read from a file (read_polygons): polygons - a list of features, each a list of rings, each a float64 (n, 2) array of x, y, what
+    Context.regiongrid takes; fields - {name: [text per feature]} with "" for a null; values(field) - the region ids of a field, checked by the
+    library.  It owns a handle of the library: close() it or use it as a context manager (the arrays stay valid afterwards; values() does not)."""
+
+    def __init__(self, handle):
+        lib = self._lib = _lib.load()
+        self.handle = handle
+        nr, nv, nf = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        n = int(lib.tdx_polygon_layer_count(handle, C.byref(nr), C.byref(nv), C.byref(nf)))
+        feature_first, ring_first = np.zeros(n + 1, np.int64), np.zeros(nr.value + 1, np.int64)
+        xy = np.zeros((2, max(nv.value, 1)), np.float64)
+        lib.tdx_polygon_layer_copy(handle, _v(feature_first), _v(ring_first), _v(xy[0]), _v(xy[1]))
+        pts = np.ascontiguousarray(xy[:, :nv.value].T)
+        self.polygons = [[pts[ring_first[q]:ring_first[q + 1]] for q in range(feature_first[f], feature_first[f + 1])] for f in range(n)]
+        names = [lib.tdx_polygon_layer_field(handle, k).decode() for k in range(nf.value)]
+        self.fields = {name: [(lib.tdx_polygon_layer_value(handle, f, k) or b"").decode(errors="replace").strip(" \0") for f in range(n)] for k, name in enumerate(names)}
+
+    def values(self, field="ID"):
+        """int32 per feature: the integer values of `field`, each in 1 .. 32767 (tdx_polygon_layer_values).  TdxError naming the feature: no such field,
+        the field name FID, a null, a value that is no integer, a value outside the range."""
+        if not self.handle:
+            raise ValueError("PolygonLayer.values: the layer is closed")
+        v = np.zeros(max(len(self.polygons), 1), np.int32)
+        check(self._lib.tdx_polygon_layer_values(self.handle, os.fsencode(field), _v(v)))
+        return v[:len(self.polygons)].copy()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.tdx_polygon_layer_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def __len__(self):
+        return len(self.polygons)
+
+
+def read_polygons(path):
+    """The polygon layer of an ESRI shapefile (shape types 5, 15, 25 with the .dbf beside it; Z and M ignored) or of a GeoJSON file (Polygon and
+    MultiPolygon features in document order): a PolygonLayer.  Every part is a ring; nesting is not rebuilt, the even-odd fill of regiongrid does not
+    need it.  No GPU is needed.  TdxError: an unsupported extension, an unreadable file, or one whose headers, lengths, counts or part indices lie."""
+    h = C.c_void_p()
+    check(_lib.load().tdx_polygon_layer_read(os.fsencode(path), C.byref(h)))
+    return PolygonLayer(h)
+
+
+def write_calpar(path, ids, tmin=2.708, tmax=2.708, cmin=0.0, cmax=0.25, phimin=30.0, phimax=45.0, soildens=2000.0):
+    """The region table sinmapsi reads as -calpar: the header line, then id,tmin,tmax,cmin,cmax,phimin,phimax,soildens per id in the order given, the
+    seven parameters as repr(float(value)) (the defaults are those of pyfiles/SIRegionTool.py).  No GPU is needed; read_calpar() reads the file back."""
+    lib = _lib.load()
+    ids = _flat(ids, np.int32)
+    texts = [repr(float(v)).encode() for v in (tmin, tmax, cmin, cmax, phimin, phimax, soildens)]
+    arr = (C.c_char_p * 7)(*texts)
+    check(lib.tdx_regiongrid_write_calpar(os.fsencode(path), _v(ids) if ids.size else None, int(ids.size), C.cast(arr, C.c_void_p)))
 
 
 def _point_lists(outlets):

@@ -67,6 +67,8 @@
 #include "sinmap_table.hpp"
 #include "tool_strips.hpp"
 #include "vector_layer.hpp"
+#include "region_table.hpp"
+#include <sys/stat.h>
 
 #define TDVERSION "5.4.0"   /* src/commonLib.h:63 */
 
@@ -1957,5 +1959,159 @@ int tdx_tool_watershedgridtoshp(const char* wfile, const char* polyfile) {
     printf("Polygons: %lld features, %lld polygons, %lld rings, %lld vertices\n", (long long)nf, (long long)np, (long long)nr, (long long)nv);
     return t.finish("Processes", "watershedgridtoshp");
 }
+
+// Create Parameter Region Grid (pyfiles/SIRegionTool.py): the calibration region grid on the DEM's grid - one region, a polygon layer burned in by an
+// attribute, or an existing region grid resampled by nearest neighbour - and the region table with one line per id that occurs.  With --gpus N every
+// rank computes its row strip (a resampled source is uploaded whole to every rank); the ids of the strips are united on the host.
+namespace {
+bool parent_exists(const std::string& path) {
+    const size_t k = path.find_last_of('/');
+    if (k == std::string::npos) return true;
+    struct stat sb;
+    const std::string dir = k == 0 ? std::string("/") : path.substr(0, k);
+    return stat(dir.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode);
+}
+}  // namespace
+
+int tdx_tool_siregiontool(const char* demfile, const char* parregfile, const char* attfile, const char* parreg_infile, const char* shpfile, const char* shp_att_name,
+                          const char* const* seven_texts) {
+    if (!demfile || !parregfile || !attfile || !seven_texts) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_siregiontool: bad argument");
+    for (int k = 0; k < 7; k++)
+        if (!seven_texts[k]) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_siregiontool: bad argument");
+    const bool have_src = parreg_infile && *parreg_infile, have_shp = shpfile && *shpfile;
+    if (have_src && have_shp) return tdx_fail(nullptr, TDX_ERR_ARG, "siregiontool: a region grid and a region polygon layer were both given: give one, or neither");
+    if (have_shp && tdx::layer_kind(shpfile) == tdx::LayerKind::None)
+        return tdx_fail(nullptr, TDX_ERR_ARG, std::string("siregiontool: unsupported input ") + shpfile + ": " + tdx::kPolygonLayerKindsMessage);
+    for (const char* out : {parregfile, attfile})
+        if (!parent_exists(out)) return tdx_fail(nullptr, TDX_ERR_ARG, std::string("siregiontool: the directory of ") + out + " does not exist");
+    ToolRun t("SIRegionTool");
+    Raster dem, src;
+    t.input(demfile, F32, dem);
+    if (t.rc == TDX_OK && have_src) t.rc = load_raster(parreg_infile, I32, src);
+    std::vector<double> x, y;
+    std::vector<int64_t> ring_first{0}, feature_first{0};
+    std::vector<int32_t> values;
+    if (t.rc == TDX_OK && have_shp) {
+        tdx::PolygonLayer L;
+        std::string err;
+        if (!tdx::read_polygon_layer(shpfile, L, err)) return tdx_fail(nullptr, TDX_ERR_FILE, "siregiontool: " + err);
+        if (!regions::attribute_values(L, shp_att_name && *shp_att_name ? shp_att_name : "ID", values, err)) return tdx_fail(nullptr, TDX_ERR_ARG, "siregiontool: " + err);
+        for (const auto& feat : L.polygons) {
+            for (const auto& pg : feat)
+                for (const auto& rg : pg) {
+                    x.insert(x.end(), rg.x.begin(), rg.x.end());
+                    y.insert(y.end(), rg.y.begin(), rg.y.end());
+                    ring_first.push_back(int64_t(x.size()));
+                }
+            feature_first.push_back(int64_t(ring_first.size()) - 1);
+        }
+    }
+    if (!t.read_done()) return t.rc;
+    const int64_t nx = dem.info.nx, ny = dem.info.ny;
+    const double* gt = dem.info.gt;
+    const int64_t n_rings = int64_t(ring_first.size()) - 1, n_features = int64_t(values.size());
+    const int32_t src_nd = have_src ? (int32_t)src.info.nodata : 0;
+    std::vector<int16_t> out(t.cells());
+    const int nranks = int(std::max<int64_t>(1, std::min<int64_t>(tool_gpus(), ny)));
+    std::vector<std::vector<int32_t>> ids(size_t(nranks), std::vector<int32_t>(TDX_REGIONGRID_MAX_IDS));
+    std::vector<int32_t> n_ids(size_t(nranks), 0);
+    const bool ok = t.compute(
+        [&](tdx_context* c, tdx_stats* s) {
+            if (have_shp)
+                return tdx_regiongrid(c, x.data(), y.data(), ring_first.data(), n_rings, feature_first.data(), values.data(), n_features, gt, 0, nx, ny, out.data(),
+                                      ids[0].data(), &n_ids[0], nullptr, nullptr, s);
+            if (have_src)
+                return tdx_regiongrid_resample(c, src.l.data(), src.info.nx, src.info.ny, src.info.gt, src_nd, gt, nx, ny, out.data(), ids[0].data(), &n_ids[0], nullptr, s);
+            return tdx_regiongrid_constant(c, nx, ny, out.data(), ids[0].data(), &n_ids[0], s);
+        },
+        [&](RankJob& j, tdx_stats* s) {
+            int16_t* d_out = j.out(out);
+            if (j.error) return j.error;
+            const size_t r = size_t(j.rank);
+            if (have_shp)
+                return tdx_regiongrid_strip(j.ctx, j.comm, x.data(), y.data(), ring_first.data(), n_rings, feature_first.data(), values.data(), n_features, gt, 0, j.nx,
+                                            j.nyl, j.y0, j.ny, d_out, ids[r].data(), &n_ids[r], nullptr, nullptr, s);
+            if (have_src) {
+                void* d_src = nullptr;
+                const size_t bytes = src.l.size() * 4;
+                if (hipMalloc(&d_src, bytes) != hipSuccess) { (void)hipGetLastError(); return int(TDX_ERR_NOMEM); }
+                j.owned.push_back(d_src);
+                if (hipMemcpyAsync(d_src, src.l.data(), bytes, hipMemcpyHostToDevice, j.ctx->stream) != hipSuccess) return int(TDX_ERR_HIP);
+                return tdx_regiongrid_resample_strip(j.ctx, j.comm, static_cast<const int32_t*>(d_src), src.info.nx, src.info.ny, src.info.gt, src_nd, gt, j.nx, j.nyl, j.y0,
+                                                     j.ny, d_out, ids[r].data(), &n_ids[r], nullptr, s);
+            }
+            return tdx_regiongrid_constant_strip(j.ctx, j.comm, j.nx, j.nyl, j.y0, j.ny, d_out, ids[r].data(), &n_ids[r], s);
+        });
+    if (!ok) return t.rc;
+    std::vector<int32_t> all;
+    for (size_t r = 0; r < ids.size(); r++) all.insert(all.end(), ids[r].begin(), ids[r].begin() + n_ids[r]);
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    t.output(parregfile, out, dem, 0.0);
+    if (t.rc == TDX_OK) {
+        std::string err;
+        if (!regions::write_table(attfile, all.data(), int32_t(all.size()), seven_texts, err)) return tdx_fail(nullptr, TDX_ERR_FILE, "siregiontool: " + err);
+    }
+    printf("Regions: %lld\n", (long long)all.size());
+    return t.finish("Processes", "siregiontool");
+}
+
+// ---- a polygon layer read from a file (host code, no context)
+struct tdx_polygon_layer { tdx::PolygonLayer L; };
+
+int tdx_polygon_layer_read(const char* path, tdx_polygon_layer** layer) {
+    if (!path || !layer) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_polygon_layer_read: bad argument");
+    *layer = nullptr;
+    tdx_polygon_layer* res = new tdx_polygon_layer;
+    std::string err;
+    const bool known = tdx::layer_kind(path) != tdx::LayerKind::None;
+    if (!tdx::read_polygon_layer(path, res->L, err)) { delete res; return tdx_fail(nullptr, known ? TDX_ERR_FILE : TDX_ERR_ARG, "tdx_polygon_layer_read: " + err); }
+    *layer = res;
+    return TDX_OK;
+}
+int64_t tdx_polygon_layer_count(const tdx_polygon_layer* layer, int64_t* n_rings, int64_t* n_vertices, int64_t* n_fields) {
+    int64_t nr = 0, nv = 0;
+    if (layer)
+        for (const auto& feat : layer->L.polygons)
+            for (const auto& pg : feat)
+                for (const auto& rg : pg) { nr++; nv += int64_t(rg.x.size()); }
+    if (n_rings) *n_rings = nr;
+    if (n_vertices) *n_vertices = nv;
+    if (n_fields) *n_fields = layer ? int64_t(layer->L.fields.size()) : 0;
+    return layer ? int64_t(layer->L.polygons.size()) : 0;
+}
+void tdx_polygon_layer_copy(const tdx_polygon_layer* layer, int64_t* feature_first, int64_t* ring_first, double* x, double* y) {
+    if (!layer) return;
+    int64_t nr = 0, nv = 0;
+    size_t f = 0;
+    if (feature_first) feature_first[0] = 0;
+    if (ring_first) ring_first[0] = 0;
+    for (const auto& feat : layer->L.polygons) {
+        for (const auto& pg : feat)
+            for (const auto& rg : pg) {
+                for (size_t k = 0; k < rg.x.size(); k++, nv++) { if (x) x[nv] = rg.x[k]; if (y) y[nv] = rg.y[k]; }
+                nr++;
+                if (ring_first) ring_first[nr] = nv;
+            }
+        f++;
+        if (feature_first) feature_first[f] = nr;
+    }
+}
+const char* tdx_polygon_layer_field(const tdx_polygon_layer* layer, int64_t k) {
+    return layer && k >= 0 && size_t(k) < layer->L.fields.size() ? layer->L.fields[size_t(k)].name.c_str() : nullptr;
+}
+const char* tdx_polygon_layer_value(const tdx_polygon_layer* layer, int64_t feature, int64_t k) {
+    if (!layer || feature < 0 || size_t(feature) >= layer->L.values.size() || k < 0 || size_t(k) >= layer->L.values[size_t(feature)].size()) return nullptr;
+    return layer->L.values[size_t(feature)][size_t(k)].c_str();
+}
+int tdx_polygon_layer_values(const tdx_polygon_layer* layer, const char* field, int32_t* values) {
+    if (!layer || !field) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_polygon_layer_values: bad argument");
+    std::vector<int32_t> v;
+    std::string err;
+    if (!regions::attribute_values(layer->L, field, v, err)) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_polygon_layer_values: " + err);
+    if (values && !v.empty()) memcpy(values, v.data(), v.size() * 4);
+    return TDX_OK;
+}
+void tdx_polygon_layer_free(tdx_polygon_layer* layer) { delete layer; }
 
 }  // extern "C"

@@ -245,6 +245,44 @@ bool read_line_shapes(const std::string& path, LineLayer& L, std::string& err) {
     return true;
 }
 
+// The records of a .shp of type Polygon, PolygonZ or PolygonM: every record is a feature (a null shape, or one of another type, without rings, so that
+// the rows of the .dbf stay with their records); every part is a ring of a polygon of its own.  Record lengths, counts and part indices are checked
+// against what was read before a vertex is taken; Z and M, which follow the points, are not looked at
+bool read_polygon_shapes(const std::string& path, PolygonLayer& L, std::string& err) {
+    std::string bytes;
+    if (!slurp(path, bytes)) { err = "cannot open " + path; return false; }
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(bytes.data());
+    if (bytes.size() < 100 || rd_be32(u) != 9994) { err = "not a shapefile: " + path; return false; }
+    const uint32_t type = rd_le32(u + 32);
+    if (!(type == 5 || type == 15 || type == 25)) { err = "shapefile layer is not a polygon layer: " + path; return false; }
+    size_t pos = 100;
+    while (pos < bytes.size()) {
+        if (bytes.size() - pos < 8) { err = "truncated record header in " + path; return false; }
+        const size_t clen = size_t(rd_be32(u + pos + 4)) * 2;
+        pos += 8;
+        if (clen > bytes.size() - pos) { err = "truncated record in " + path; return false; }
+        std::vector<PolygonLayer::Polygon> polys;
+        const uint32_t t = clen >= 4 ? rd_le32(u + pos) : 0;
+        if (t == 5 || t == 15 || t == 25) {
+            if (clen < 44) { err = "short polygon record in " + path; return false; }
+            const size_t nparts = rd_le32(u + pos + 36), npoints = rd_le32(u + pos + 40);
+            if (nparts > clen / 4 || npoints > clen / 16 || 44 + 4 * nparts + 16 * npoints > clen) { err = "polygon record with impossible counts in " + path; return false; }
+            const unsigned char* parts = u + pos + 44;
+            const unsigned char* pts = parts + 4 * nparts;
+            for (size_t q = 0; q < nparts; q++) {
+                const size_t first = rd_le32(parts + 4 * q), last = q + 1 < nparts ? size_t(rd_le32(parts + 4 * (q + 1))) : npoints;
+                if (first > last || last > npoints) { err = "polygon record with impossible parts in " + path; return false; }
+                PolygonLayer::Ring rg;
+                for (size_t k = first; k < last; k++) { rg.x.push_back(rd_le64f(pts + 16 * k)); rg.y.push_back(rd_le64f(pts + 16 * k + 8)); }
+                polys.push_back(PolygonLayer::Polygon{std::move(rg)});
+            }
+        }
+        L.polygons.push_back(std::move(polys));
+        pos += clen;
+    }
+    return true;
+}
+
 bool read_dbf_fields(const std::string& shp_path, size_t n_features, LayerTable& L, std::string& err) {
     std::string b;
     if (!slurp(with_ext(shp_path, ".dbf"), b) && !slurp(with_ext(shp_path, ".DBF"), b)) return true;   // a .shp without attributes: no field
@@ -532,6 +570,64 @@ bool read_line_geojson(const std::string& path, LineLayer& L, std::string& err) 
     return true;
 }
 
+// in document order, the features whose geometry is a Polygon or a MultiPolygon
+void collect_polygon_features(const JVal& v, std::vector<const JVal*>& feats) {
+    if (v.kind == JVal::Object) {
+        const JVal* g = v.get("geometry");
+        if (g && g->kind == JVal::Object) {
+            const JVal* t = g->get("type");
+            const JVal* c = g->get("coordinates");
+            if (t && c && c->kind == JVal::Array && (t->text == "Polygon" || t->text == "MultiPolygon")) feats.push_back(&v);
+            return;
+        }
+        for (const auto& kv : v.obj) collect_polygon_features(kv.second, feats);
+    } else if (v.kind == JVal::Array)
+        for (const JVal& e : v.arr) collect_polygon_features(e, feats);
+}
+bool number_of(const JVal& v, double& out) {   // a JSON number all of whose text is one
+    if (v.kind != JVal::Number || v.text.empty()) return false;
+    char* end = nullptr;
+    out = strtod(v.text.c_str(), &end);
+    return end == v.text.c_str() + v.text.size();
+}
+bool ring_of(const JVal& r, PolygonLayer::Ring& rg) {
+    if (r.kind != JVal::Array) return false;
+    for (const JVal& pt : r.arr) {
+        double x, y;
+        if (pt.kind != JVal::Array || pt.arr.size() < 2 || !number_of(pt.arr[0], x) || !number_of(pt.arr[1], y)) return false;
+        rg.x.push_back(x); rg.y.push_back(y);
+    }
+    return true;
+}
+bool read_polygon_geojson(const std::string& path, PolygonLayer& L, std::string& err) {
+    std::string text;
+    if (!slurp(path, text)) { err = "cannot open " + path; return false; }
+    JParser jp(text);
+    const JVal root = jp.value();
+    jp.ws();
+    if (!jp.ok || jp.p != text.size()) { err = "cannot parse " + path; return false; }
+    std::vector<const JVal*> feats;
+    collect_polygon_features(root, feats);
+    L.resize(feats.size());
+    for (size_t i = 0; i < feats.size(); i++) {
+        const JVal* g = feats[i]->get("geometry");
+        const JVal* c = g->get("coordinates");
+        const bool multi = g->get("type")->text == "MultiPolygon";
+        for (const JVal& a : c->arr) {
+            if (multi && a.kind != JVal::Array) { err = "a polygon of " + path + " is not a list of rings"; return false; }
+            const std::vector<JVal>& rings = multi ? a.arr : c->arr;
+            for (const JVal& r : rings) {
+                PolygonLayer::Ring rg;
+                if (!ring_of(r, rg)) { err = "a position of " + path + " is not [x, y]"; return false; }
+                L.polygons[i].push_back(PolygonLayer::Polygon{std::move(rg)});
+            }
+            if (!multi) break;
+        }
+    }
+    fill_properties(feats, L);
+    return true;
+}
+
 bool read_text_fields(const std::string& path, size_t n_features, PointLayer& L, std::string& err) {
     std::ifstream f(path);
     if (!f) { err = "cannot open " + path; return false; }
@@ -652,6 +748,18 @@ bool read_line_layer(const std::string& path, LineLayer& L, std::string& err) {
         return read_dbf_fields(path, L.x.size(), L, err);
     case LayerKind::GeoJSON: return read_line_geojson(path, L, err);
     default: err = std::string("unsupported input ") + path + ": " + kLineLayerKindsMessage; return false;
+    }
+}
+
+bool read_polygon_layer(const std::string& path, PolygonLayer& L, std::string& err) {
+    L = PolygonLayer();
+    switch (layer_kind(path)) {
+    case LayerKind::Shapefile:
+        if (!read_polygon_shapes(path, L, err)) return false;
+        L.values.assign(L.polygons.size(), {});
+        return read_dbf_fields(path, L.polygons.size(), L, err);
+    case LayerKind::GeoJSON: return read_polygon_geojson(path, L, err);
+    default: err = std::string("unsupported input ") + path + ": " + kPolygonLayerKindsMessage; return false;
     }
 }
 }  // namespace tdx

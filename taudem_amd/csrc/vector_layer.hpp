@@ -70,6 +70,10 @@ bool read_line_layer(const std::string& path, LineLayer& layer, std::string& err
 // MultiPolygon; every ring is written REVERSED (RFC 7946: exterior rings counter-clockwise, holes clockwise), from and to the same start vertex.  A layer
 // without features is a valid empty file.
 bool write_polygon_layer(const std::string& path, const PolygonLayer& layer, std::string& err);
+// Shapefile: shape types 5, 15 and 25 (Z and M are ignored, a null shape is a feature without rings) with the .dbf next to it.  GeoJSON: the Polygon
+// and MultiPolygon features in document order with their properties.  Every part / ring becomes the one ring of a polygon of its own: nesting is not
+// rebuilt (an even-odd fill does not need it).  Files whose headers, record lengths, counts, part indices or .dbf record counts lie are refused.
+bool read_polygon_layer(const std::string& path, PolygonLayer& layer, std::string& err);
 // the files write_point_layer(path) / write_line_layer(path) / write_polygon_layer(path) create
 std::vector<std::string> layer_files(const std::string& path);
 }  // namespace tdx

@@ -402,8 +402,18 @@ class _StripPolygonizeStage:
         return api._polygonize_edges_strip(self._call(), w, row0, ny_total, nodata)
 
 
+class _StripRegionGridStage:
+    """StripPipeline.regiongrid (include/taudem_amd_regions.h).  Nothing is exchanged and the halo rows of the output are left unwritten."""
+
+    def regiongrid(self, gt, row0, ny_total, polygons=None, values=None, source=None, source_gt=None, source_nodata=-2147483647, out=None, workspace_words=0, phases=False):
+        """grid, ids, stats = regiongrid(gt, row0, ny_total, ...) on this strip: its owned rows of the region grid of a raster of ny_total rows whose
+        geotransform is gt, and the values that occur in them.  source: the WHOLE source grid as a tensor on this device.  phases=True: stats["phases"],
+        at the price of a drained stream after every phase."""
+        return api._regiongrid(self._call(), None, gt, polygons, values, source, source_gt, source_nodata, out, workspace_words, row0=row0, ny_total=ny_total, phases=phases)
+
+
 class StripPipeline(_StripDropAnalysisStage, _StripPeukerDouglasStage, _StripStreamNetStage, _StripOutletToolsStage, _StripSinmapStage, _StripTerrainIndexStage,
-                    _StripEditRasterStage, _StripPolygonizeStage):
+                    _StripEditRasterStage, _StripPolygonizeStage, _StripRegionGridStage):
     """The tools of taudem_amd.api.Context on one strip of a row-partitioned raster.  All rasters are CUDA
     tensors of shape (ny_local + 2, nx): row 0 / row -1 are the halo rows the library maintains.  Every method
     runs the marshalling body of the Context method of its name (taudem_amd/api.py) on a strip frame, takes

@@ -237,6 +237,19 @@ def watershedgridtoshp(wfile, polyfile):
     return _lib.load().tdx_tool_watershedgridtoshp(_b(wfile), _b(polyfile))
 
 
+def siregiontool(dem, parreg, att, parreg_in="", shp="", shp_att_name="ID", att_tmin=2.708, att_tmax=2.708, att_cmin=0.0, att_cmax=0.25, att_phimin=30.0,
+                 att_phimax=45.0, att_soildens=2000.0):
+    """pyfiles/SIRegionTool.py (the toolbox step Create Parameter Region Grid): the calibration region grid parreg (int16 GeoTIFF, nodata 0) on the grid
+    of dem - the polygon layer shp burned in by the field shp_att_name, the region grid parreg_in resampled by nearest neighbour, or one region - and the
+    region table att with one line per id that occurs, the seven parameters written as repr(float(value)).  Both sources, an output directory that does
+    not exist and a polygon source without a reader are refused before anything is read."""
+    import ctypes as C
+
+    texts = [repr(float(v)).encode() for v in (att_tmin, att_tmax, att_cmin, att_cmax, att_phimin, att_phimax, att_soildens)]
+    arr = (C.c_char_p * 7)(*texts)
+    return _lib.load().tdx_tool_siregiontool(_b(dem), _b(parreg), _b(att), _b(parreg_in), _b(shp), _b(shp_att_name), C.cast(arr, C.c_void_p))
+
+
 twi = twigrid
 slopearearatio = atanbgrid
 
