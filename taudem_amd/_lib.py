@@ -413,6 +413,9 @@ _POLYGONIZE_SIGNATURES = {
     # ctx, w, nx, ny, w_nodata, &polygons, stats
     "tdx_polygonize": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
     "tdx_polygonize_dev": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    # the same with the rings closed on the device
+    "tdx_polygonize_gpu_rings": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
+    "tdx_polygonize_gpu_rings_dev": (C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(_P), _P]),
     # ctx, comm, w, nx, ny_local, row0, ny_total, w_nodata, &part, stats
     "tdx_polygonize_edges_strip": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I32, C.POINTER(_P), _P]),
     # keys, next_keys, ids, n, &part
@@ -423,6 +426,10 @@ _POLYGONIZE_SIGNATURES = {
     "tdx_polygonize_edges_free": (None, [_P]),
     # parts, n_parts, nx, ny, &polygons
     "tdx_polygonize_rings": (C.c_int, [_P, _I64, _I64, _I64, C.POINTER(_P)]),
+    # ctx, parts, n_parts, nx, ny, &polygons, stats
+    "tdx_polygonize_rings_gpu": (C.c_int, [_P, _P, _I64, _I64, _I64, C.POINTER(_P), _P]),
+    # polygons, ms, &rounds, &workspace_bytes
+    "tdx_polygons_ring_phases": (C.c_int, [_P, _P, C.POINTER(_I64), C.POINTER(_I64)]),
     # polygons, &n_polygons, &n_rings, &n_vertices, &n_edges
     "tdx_polygons_count": (_I64, [_P] + [C.POINTER(_I64)] * 4),
     # polygons, ids, cells, poly_first, ring_first, vert_first, vertices, phase_ms
@@ -431,9 +438,12 @@ _POLYGONIZE_SIGNATURES = {
     # path, polygons, gt
     "tdx_polygons_write": (C.c_int, [C.c_char_p, _P, _P]),
     "tdx_tool_watershedgridtoshp": (C.c_int, [C.c_char_p] * 2),
+    "tdx_tool_set_polygon_rings": (C.c_int, [C.c_int]),
 }
 POLYGONIZE_SYMBOLS = tuple(_POLYGONIZE_SIGNATURES)
 POLYGONIZE_PHASES = ("count", "scan", "emit", "download", "rings")
+POLYGONIZE_RING_PHASES = ("successor", "validate", "label", "per_ring", "rank", "holes", "order", "scatter")   # of the device ring builder
+POLYGONIZE_RINGS = ("host", "device")   # where the rings are closed: the value of tdx_tool_set_polygon_rings is the index
 
 # name -> (restype, argtypes): the symbols include/taudem_amd_regions.h declares, the eleventh extension header
 _RG_POLYGONS = [_P, _P, _P, _I64, _P, _P, _I64, _P, _I64]   # x, y, ring_first, n_rings, feature_first, values, n_features, gt, workspace_words

@@ -297,6 +297,12 @@ class _PolygonizeStage:
         library, so use it as a context manager or close() it."""
         return _ret(_polygonize(_Call(self), w, nodata), stats)
 
+    def polygonize_rings(self, w, nodata=-2147483647, *, rings="host", stats=False):
+        """polygons = polygonize_rings(w, rings="device"): polygonize(w) with the choice of where the rings are closed.  "host": what polygonize does.
+        "device": the edge columns stay on the device, the rings are closed, classified and ordered there and only the finished layer comes down; the
+        arrays are the same, Polygons.ring_phases holds the ring builder's sub-phases.  Any other word raises ValueError."""
+        return _ret(_polygonize(_Call(self), w, nodata, rings), stats)
+
 
 class _RegionGridStage:
     """Context.regiongrid; its entry points are those of include/taudem_amd_regions.h."""
@@ -1024,10 +1030,17 @@ class StreamNetLinks:
         self.close()
 
 
-def _polygonize(f, w, nodata):
+def _rings_word(rings):
+    if rings not in _lib.POLYGONIZE_RINGS:
+        raise ValueError(f"rings: {rings!r} is neither 'host' nor 'device'")
+    return rings
+
+
+def _polygonize(f, w, nodata, rings="host"):
+    symbol = "tdx_polygonize_gpu_rings" if _rings_word(rings) == "device" else "tdx_polygonize"
     pw = f.raster(w, np.int32, "w")
     handle = C.c_void_p()
-    st = f.call("tdx_polygonize", pw, f.nx, f.ny, int(nodata), C.byref(handle))
+    st = f.call(symbol, pw, f.nx, f.ny, int(nodata), C.byref(handle))
     return Polygons(handle=handle), st
 
 
@@ -1063,20 +1076,28 @@ def polygonize_edges_create(keys, next_keys, ids):
 
 class Polygons:
     """The watershed polygons of an id grid: of Context.polygonize (handle=), or from the edge parts of ALL strips of a raster in strip order
-    (parts=, nx=, ny=: StripPipeline.polygonize_edges; host code, no device).  features -> polygons -> rings -> vertices as offset lists:
+    (parts=, nx=, ny=: StripPipeline.polygonize_edges; host code, no device - or with rings="device" and ctx=, a Context, closed on its device).  features -> polygons -> rings -> vertices as offset lists:
     ids int32 [F] ascending; cells int64 [F]; poly_first int64 [F + 1]; ring_first int64 [P + 1] (the outer ring of a polygon first, then its holes);
     vert_first int64 [R + 1]; vertices int32 [V, 2] (column, row), every ring closed; phases: the milliseconds of count, scan, emit, download, rings.
+    ring_phases: the milliseconds of the device ring builder's sub-phases (empty when the host closed the rings), with ring_rounds (its jump rounds)
+    and ring_workspace_bytes.
     Owns its handle and the parts: close() frees them."""
 
-    def __init__(self, handle=None, parts=None, nx=None, ny=None):
+    def __init__(self, handle=None, parts=None, nx=None, ny=None, ctx=None, rings="host"):
         self._lib = _lib.load()
+        _rings_word(rings)
         self.parts = list(parts) if parts is not None else []
         if handle is None:
             if not self.parts or nx is None or ny is None:
                 raise ValueError("Polygons: need a handle, or parts with nx and ny")
             arr = (C.c_void_p * len(self.parts))(*[p.value for p in self.parts])
             handle = C.c_void_p()
-            check(self._lib.tdx_polygonize_rings(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), C.byref(handle)))
+            if rings == "device":
+                if ctx is None:
+                    raise ValueError("Polygons: rings='device' needs ctx=, the Context whose device closes the rings")
+                check(self._lib.tdx_polygonize_rings_gpu(ctx._h, C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), C.byref(handle), None), ctx._h)
+            else:
+                check(self._lib.tdx_polygonize_rings(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), C.byref(handle)))
         self.handle = handle
         lib = self._lib
         npoly, nring, nvert, nedge = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -1088,6 +1109,10 @@ class Polygons:
         ms = np.zeros(len(_lib.POLYGONIZE_PHASES), np.float64)
         lib.tdx_polygons_copy(handle, _v(self.ids), _v(self.cells), _v(self.poly_first), _v(self.ring_first), _v(self.vert_first), _v(self.vertices), _v(ms))
         self.phases = dict(zip(_lib.POLYGONIZE_PHASES, ms.tolist()))
+        rms, rounds, wsb = np.zeros(len(_lib.POLYGONIZE_RING_PHASES), np.float64), C.c_int64(0), C.c_int64(0)
+        on_device = lib.tdx_polygons_ring_phases(handle, _v(rms), C.byref(rounds), C.byref(wsb))
+        self.ring_phases = dict(zip(_lib.POLYGONIZE_RING_PHASES, rms.tolist())) if on_device else {}
+        self.ring_rounds, self.ring_workspace_bytes = int(rounds.value), int(wsb.value)
 
     def features(self):
         """[(id, cells, [polygon, ...])] with polygon = [ring, ...] (the outer ring first) and ring = [(column, row), ...], closed."""
@@ -1129,10 +1154,11 @@ class Polygons:
         self.close()
 
 
-def polygonize(w, nodata=-2147483647, device=0, **kw):
-    """Context(device).polygonize(...) for a single call."""
+def polygonize(w, nodata=-2147483647, device=0, *, rings="host", **kw):
+    """Context(device).polygonize(...) for a single call; rings="device" closes the rings on the device (Context.polygonize_rings)."""
+    _rings_word(rings)
     with Context(device) as ctx:
-        return ctx.polygonize(w, nodata, **kw)
+        return ctx.polygonize_rings(w, nodata, rings=rings, **kw) if rings != "host" else ctx.polygonize(w, nodata, **kw)
 
 
 class PackedPolygons:

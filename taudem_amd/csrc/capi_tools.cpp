@@ -79,6 +79,7 @@ using toolstrips::RankJob;
 
 int g_tool_device = -1;
 int g_tool_gpus = -1;
+int g_tool_polygon_rings = 0;   // tdx_tool_set_polygon_rings: 0 the host closes the rings of watershedgridtoshp, 1 the device
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -361,6 +362,11 @@ extern "C" {
 
 int tdx_tool_set_device(int device) { g_tool_device = device; return TDX_OK; }
 int tdx_tool_set_gpus(int ngpus) { g_tool_gpus = ngpus; return TDX_OK; }
+int tdx_tool_set_polygon_rings(int where) {
+    if (where != 0 && where != 1) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_set_polygon_rings: 0 (host) or 1 (device)");
+    g_tool_polygon_rings = where;
+    return TDX_OK;
+}
 
 int tdx_tool_pitremove(const char* demfile, const char* felfile, const char* /*sfdrfile*/, int /*usesfdr*/,
                        int verbose, int is_4Point, int use_mask, const char* maskfile) {
@@ -1912,7 +1918,7 @@ int tdx_tool_catchoutlets(const char* pfile, const char* streamnetsrc, const cha
 
 // Watershed Grid To Shapefile (pyfiles/WatershedGridToShapefile.py: arcpy.RasterToPolygon_conversion(w, shp, "NO_SIMPLIFY", "Value")).  With --gpus N
 // every rank uploads its rows WITH the neighbouring strips' rows as halo rows (the host holds the whole raster: no exchange), takes the edges of its
-// owned rows, and rank 0 closes the rings over the parts in strip order.
+// owned rows, and rank 0 closes the rings over the parts in strip order: on the host, or after tdx_tool_set_polygon_rings(1) on its device.
 int tdx_tool_watershedgridtoshp(const char* wfile, const char* polyfile) {
     if (!wfile || !polyfile) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_watershedgridtoshp: bad argument");
     if (tdx::layer_kind(polyfile) == tdx::LayerKind::None) return refuse_layer("watershedgridtoshp", polyfile);
@@ -1924,12 +1930,13 @@ int tdx_tool_watershedgridtoshp(const char* wfile, const char* polyfile) {
     const int64_t nx = w.info.nx, ny = w.info.ny;
     const int32_t w_nd = (int32_t)w.info.nodata;
     tdx_polygons* polys = nullptr;
+    const bool device_rings = g_tool_polygon_rings == 1;
     const int nranks = int(std::max<int64_t>(1, std::min<int64_t>(tool_gpus(), ny)));
     RankMeet meet; meet.n = nranks;
     std::atomic<int> failed{0};
     std::vector<tdx_polygonize_edges*> parts(size_t(nranks), nullptr);
     const bool ok = t.compute(
-        [&](tdx_context* c, tdx_stats* s) { return tdx_polygonize(c, w.l.data(), nx, ny, w_nd, &polys, s); },
+        [&](tdx_context* c, tdx_stats* s) { return device_rings ? tdx_polygonize_gpu_rings(c, w.l.data(), nx, ny, w_nd, &polys, s) : tdx_polygonize(c, w.l.data(), nx, ny, w_nd, &polys, s); },
         [&](RankJob& j, tdx_stats* s) {
             int32_t* d_w = j.strip<int32_t>(nullptr);
             int e = d_w ? TDX_OK : TDX_ERR_NOMEM;
@@ -1943,7 +1950,7 @@ int tdx_tool_watershedgridtoshp(const char* wfile, const char* polyfile) {
             if (e != TDX_OK) failed = e;
             meet.wait();
             if (failed == 0 && j.rank == 0) {
-                const int em = tdx_polygonize_rings(parts.data(), j.size, nx, ny, &polys);
+                const int em = device_rings ? tdx_polygonize_rings_gpu(j.ctx, parts.data(), j.size, nx, ny, &polys, nullptr) : tdx_polygonize_rings(parts.data(), j.size, nx, ny, &polys);
                 if (em != TDX_OK) { failed = em; e = em; }
             }
             meet.wait();

@@ -1,3 +1,5 @@
+// The host ring builder: the default, and the witness of the device ring builder (polygon_rings_device.hip), which must make the same arrays of the
+// same edges and refuse the same edges for the same reasons.  The tests hold the two against each other and both against tests/polygonize_model.py.
 #include "polygon_rings.hpp"
 
 #include <algorithm>

@@ -9,7 +9,9 @@
 // No atomic decides a rank: the same bytes on every run.  The 3 x 3 window of a thread is three runs of CELLS + 2 cells; where the first owned cell lies
 // on a 16-byte boundary and nx is a multiple of 4, every run's inner cells are two 16-byte loads, else cell-wide loads.  A cell outside the readable
 // rows reads as nodata, which is "not this id" for every id.
-// The rings are closed on the host (polygon_rings.cpp): a walk over the edges, a binary search per successor.
+// The rings are closed on the host (polygon_rings.cpp): a walk over the edges, a binary search per successor.  That is the default.  The _gpu_rings
+// entry points close them on the device instead (polygon_rings_device.hip): the edge columns stay where emit_kernel left them and only the finished layer
+// comes down.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -19,6 +21,7 @@
 #include "context.hpp"
 #include "device_common.hpp"
 #include "polygon_rings.hpp"
+#include "polygon_rings_device.hpp"
 #include "strips.hpp"
 #include "vector_layer.hpp"
 
@@ -30,6 +33,8 @@ struct tdx_polygons {
     polygons::Polygons P;
     int64_t edges = 0;
     double phase_ms[TDX_POLYGONIZE_PHASES] = {0, 0, 0, 0, 0};
+    bool device_rings = false;          // the rings were closed on the device: rs holds its sub-phases
+    polygons::DeviceRingStats rs;
 };
 
 namespace {
@@ -217,9 +222,14 @@ struct PhaseClock {
     }
 };
 
-// d_arr: an array of ny_local rows (halo == 0: the whole raster) or of ny_local + 2 rows (halo == 1: row 1 is the raster's row row0)
+// the edge columns where emit_kernel left them (scratch slot TDX_S_H)
+struct DeviceEdges { const int64_t* key = nullptr; const int64_t* next = nullptr; const int32_t* id = nullptr; uint64_t n = 0; };
+
+// d_arr: an array of ny_local rows (halo == 0: the whole raster) or of ny_local + 2 rows (halo == 1: row 1 is the raster's row row0).
+// dev == nullptr: the columns are downloaded into res->part and the call is ended.  Else they stay on the device, nothing is allocated on the host for
+// them, and the call stays open: the caller goes on with the rings and ends it.
 int edges_impl(tdx_context* ctx, const int32_t* d_arr, int64_t nx, int64_t ny_local, int halo, int64_t row0, int64_t ny_total, int32_t nd, tdx_polygonize_edges* res,
-               tdx_stats* stats, const char* who) {
+               tdx_stats* stats, const char* who, DeviceEdges* dev = nullptr) {
     TDX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     Grid g;
@@ -267,7 +277,7 @@ int edges_impl(tdx_context* ctx, const int32_t* d_arr, int64_t nx, int64_t ny_lo
     int64_t* d_key = reinterpret_cast<int64_t*>(buf);
     int64_t* d_next = reinterpret_cast<int64_t*>(buf + nep * 8);
     int32_t* d_id = reinterpret_cast<int32_t*>(buf + nep * 16);
-    try {
+    if (!dev) try {
         res->part.key.resize(size_t(ne)); res->part.next.resize(size_t(ne)); res->part.id.resize(size_t(ne));
     } catch (const std::bad_alloc&) {
         return tdx_fail(ctx, TDX_ERR_NOMEM, std::string(who) + ": out of host memory for the edges");
@@ -280,6 +290,11 @@ int edges_impl(tdx_context* ctx, const int32_t* d_arr, int64_t nx, int64_t ny_lo
         if (stats) stats->launches[TDX_K_STENCIL] += 1;
     }
     if ((rc = clock.lap(&res->phase_ms[TDX_POLYGONIZE_EMIT])) != TDX_OK) return rc;
+    if (dev) {
+        dev->key = d_key; dev->next = d_next; dev->id = d_id; dev->n = ne;
+        TDX_HIP_CHECK(ctx, hipGetLastError());
+        return TDX_OK;
+    }
     if (ne) {
         TdxSpan sp(ctx, TDX_K_MISC);
         TDX_HIP_CHECK(ctx, hipMemcpyAsync(res->part.key.data(), d_key, size_t(ne) * 8, hipMemcpyDeviceToHost, s));
@@ -315,7 +330,97 @@ int rings_impl(const tdx_polygonize_edges* const* parts, int64_t n_parts, int64_
     return TDX_OK;
 }
 
+// The rings of edge columns in device memory, closed there; the call (begin_call) is open and is ended here
+int device_rings_impl(tdx_context* ctx, const DeviceEdges& de, int64_t nx, int64_t ny, const double* edge_phase_ms, tdx_polygons** polygons, const char* who) {
+    tdx_polygons* res = new tdx_polygons;
+    res->edges = int64_t(de.n);
+    res->device_rings = true;
+    if (edge_phase_ms)
+        for (int i = 0; i < TDX_POLYGONIZE_PHASES; i++) res->phase_ms[i] = edge_phase_ms[i];
+    std::string err;
+    const int rc = polygons::build_rings_device(ctx, de.key, de.next, de.id, de.n, nx, ny, res->P, res->rs, err);
+    if (rc != TDX_OK) {
+        delete res;
+        if (rc == TDX_ERR_HIP && err.empty()) return rc;   // TDX_HIP_CHECK has said why
+        if (rc == TDX_ERR_NOMEM && err.empty()) { ctx->abort_call(); return rc; }   // scratch() has
+        return tdx_fail(ctx, rc, std::string(who) + ": " + err);
+    }
+    res->phase_ms[TDX_POLYGONIZE_DOWNLOAD] = res->rs.download_ms;
+    res->phase_ms[TDX_POLYGONIZE_RINGS] = 0;
+    for (int i = 0; i < polygons::RING_PHASES; i++) res->phase_ms[TDX_POLYGONIZE_RINGS] += res->rs.ms[i];
+    ctx->end_call();
+    *polygons = res;
+    return TDX_OK;
+}
+
 }  // namespace
+
+extern "C" int tdx_polygonize_gpu_rings_dev(tdx_context* ctx, const int32_t* d_w, int64_t nx, int64_t ny, int32_t w_nodata, tdx_polygons** polygons, tdx_stats* stats) {
+    if (!ctx || !d_w || !polygons || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_polygonize_gpu_rings_dev: bad argument");
+    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    *polygons = nullptr;
+    tdx_polygonize_edges part;
+    DeviceEdges de;
+    const int rc = edges_impl(ctx, d_w, nx, ny, 0, 0, ny, w_nodata, &part, stats, "tdx_polygonize_gpu_rings", &de);
+    if (rc != TDX_OK) return rc;
+    return device_rings_impl(ctx, de, nx, ny, part.phase_ms, polygons, "tdx_polygonize_gpu_rings");
+}
+
+extern "C" int tdx_polygonize_gpu_rings(tdx_context* ctx, const int32_t* w, int64_t nx, int64_t ny, int32_t w_nodata, tdx_polygons** polygons, tdx_stats* stats) {
+    if (!ctx || !w || !polygons || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_polygonize_gpu_rings: bad argument");
+    if (too_big(nx, ny)) return tdx_fail(ctx, TDX_ERR_ARG, "raster larger than 2^32 cells per device strip");
+    HostCall h(ctx, nx, ny);
+    const int32_t* d_w = h.in(TDX_S_IO0, w);
+    if (h.error) return h.error;
+    return h.finish(tdx_polygonize_gpu_rings_dev(ctx, d_w, nx, ny, w_nodata, polygons, stats));
+}
+
+extern "C" int tdx_polygonize_rings_gpu(tdx_context* ctx, const tdx_polygonize_edges* const* parts, int64_t n_parts, int64_t nx, int64_t ny, tdx_polygons** polygons,
+                                        tdx_stats* stats) {
+    if (!ctx || !parts || n_parts <= 0 || nx <= 0 || ny <= 0 || !polygons) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_polygonize_rings_gpu: bad argument");
+    for (int64_t k = 0; k < n_parts; k++)
+        if (!parts[k]) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_polygonize_rings_gpu: bad argument");
+    *polygons = nullptr;
+    size_t total = 0;
+    double ms[TDX_POLYGONIZE_PHASES] = {0, 0, 0, 0, 0};
+    for (int64_t k = 0; k < n_parts; k++) {
+        total += parts[k]->part.key.size();
+        for (int i = 0; i < TDX_POLYGONIZE_PHASES; i++) ms[i] = std::max(ms[i], parts[k]->phase_ms[i]);
+    }
+    // the parts joined in the edge columns' slot: key, successor key (int64), id (int32)
+    TDX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t nep = (total + 3) & ~size_t(3);
+    uint8_t* buf = static_cast<uint8_t*>(ctx->scratch(TDX_S_H, nep * 20 + 64));
+    if (!buf) return TDX_ERR_NOMEM;
+    ctx->begin_call(stats);
+    ctx->stage = "tdx_polygonize_rings_gpu";
+    size_t at = 0;
+    for (int64_t k = 0; k < n_parts; k++) {
+        const polygons::EdgePart& p = parts[k]->part;
+        const size_t n = p.key.size();
+        if (!n) continue;
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(buf + at * 8, p.key.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(buf + nep * 8 + at * 8, p.next.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(buf + nep * 16 + at * 4, p.id.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+        at += n;
+    }
+    TDX_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // the parts are the caller's: they may go once the call returns
+    DeviceEdges de;
+    de.key = reinterpret_cast<const int64_t*>(buf);
+    de.next = reinterpret_cast<const int64_t*>(buf + nep * 8);
+    de.id = reinterpret_cast<const int32_t*>(buf + nep * 16);
+    de.n = total;
+    return device_rings_impl(ctx, de, nx, ny, ms, polygons, "tdx_polygonize_rings_gpu");
+}
+
+extern "C" int tdx_polygons_ring_phases(const tdx_polygons* polygons, double* ms, int64_t* rounds, int64_t* workspace_bytes) {
+    const bool dev = polygons && polygons->device_rings;
+    if (ms)
+        for (int i = 0; i < polygons::RING_PHASES; i++) ms[i] = dev ? polygons->rs.ms[i] : 0.0;
+    if (rounds) *rounds = dev ? polygons->rs.rounds : 0;
+    if (workspace_bytes) *workspace_bytes = dev ? polygons->rs.workspace_bytes : 0;
+    return dev ? 1 : 0;
+}
 
 extern "C" int tdx_polygonize_dev(tdx_context* ctx, const int32_t* d_w, int64_t nx, int64_t ny, int32_t w_nodata, tdx_polygons** polygons, tdx_stats* stats) {
     if (!ctx || !d_w || !polygons || nx <= 0 || ny <= 0) return tdx_fail(ctx, TDX_ERR_ARG, "tdx_polygonize_dev: bad argument");

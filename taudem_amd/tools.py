@@ -237,6 +237,13 @@ def watershedgridtoshp(wfile, polyfile):
     return _lib.load().tdx_tool_watershedgridtoshp(_b(wfile), _b(polyfile))
 
 
+def set_polygon_rings(rings="host"):
+    """Where watershedgridtoshp closes the rings from now on: "host" (the default) or "device" (tdx_tool_set_polygon_rings); both write the same bytes."""
+    if rings not in _lib.POLYGONIZE_RINGS:
+        raise ValueError(f"rings: {rings!r} is neither 'host' nor 'device'")
+    return _lib.load().tdx_tool_set_polygon_rings(_lib.POLYGONIZE_RINGS.index(rings))
+
+
 def siregiontool(dem, parreg, att, parreg_in="", shp="", shp_att_name="ID", att_tmin=2.708, att_tmax=2.708, att_cmin=0.0, att_cmax=0.25, att_phimin=30.0,
                  att_phimax=45.0, att_soildens=2000.0):
     """pyfiles/SIRegionTool.py (the toolbox step Create Parameter Region Grid): the calibration region grid parreg (int16 GeoTIFF, nodata 0) on the grid
