@@ -16,7 +16,11 @@
  * edge, cell height} of the raster file (host, 4 doubles).  Outlets: HOST column / row / id lists in file order (outlet_id NULL: 1, 2, ...); an
  * outlet on a stream cell ends a link there, the last one on a cell wins, outlets off the raster or off the stream change nothing.
  * The two dense passes (the distance to the outlet along the stream, the catchment labels) and the compaction of the stream cells run on the
- * device; the link numbering walks the stream cells alone, on the host.  *links is owned by the caller: tdx_streamnet_links_free. */
+ * device; the link numbering walks the stream cells alone, on the host.  *links is owned by the caller: tdx_streamnet_links_free.
+ * tdx_streamnet_gpu_links / tdx_streamnet_gpu_links_dev: the same arguments and the same results, byte for byte, with the links built on the device too
+ * (the queue's pop order has a closed form): the compact columns, the labels and the orders never leave the device, only the tree and coord rows come
+ * down into the handle, which everything below takes unchanged.  They take fewer than 2^31 - 1 stream cells (TDX_ERR_ARG beyond).  The level pass of
+ * the device builder takes as many rounds as there are links on the longest path of the network. */
 typedef struct tdx_streamnet_links tdx_streamnet_links;
 int tdx_streamnet_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny,
                       int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt,
@@ -26,6 +30,14 @@ int tdx_streamnet(tdx_context* ctx, const int16_t* p, const int32_t* src, const 
                   int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
                   const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w,
                   tdx_streamnet_links** links, tdx_stats* stats);
+int tdx_streamnet_gpu_links_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny,
+                                int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt,
+                                const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed,
+                                int16_t* d_ord, int32_t* d_w, tdx_streamnet_links** links, tdx_stats* stats);
+int tdx_streamnet_gpu_links(tdx_context* ctx, const int16_t* p, const int32_t* src, const float* fel, const float* ad8, int64_t nx, int64_t ny, int16_t p_nodata,
+                            int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
+                            const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w,
+                            tdx_streamnet_links** links, tdx_stats* stats);
 /* Number of links; *n_points: rows of coord; *stream_cells: cells on the stream (either may be NULL). */
 int64_t tdx_streamnet_links_count(const tdx_streamnet_links* links, int64_t* n_points, int64_t* stream_cells);
 /* tree [links][9], coord [points][5], phase_ms [TDX_STREAMNET_PHASES]: wall milliseconds of the call's phases, each ended with the stream drained
@@ -33,13 +45,25 @@ int64_t tdx_streamnet_links_count(const tdx_streamnet_links* links, int64_t* n_p
 #define TDX_STREAMNET_SETUP 0    /* info words and steps of the length sweep */
 #define TDX_STREAMNET_LENGTH 1   /* the length sweep */
 #define TDX_STREAMNET_COMPACT 2  /* compaction of the stream cells and their copy to the host */
-#define TDX_STREAMNET_LINKS 3    /* the link builder, on the host */
+#define TDX_STREAMNET_LINKS 3    /* the link builder, whichever ran (host: the walk; device: its launches and the download of the rows) */
 #define TDX_STREAMNET_SCATTER 4  /* info words of the label sweep, labels and orders of the stream cells */
 #define TDX_STREAMNET_LABEL 5    /* the label sweep */
 #define TDX_STREAMNET_TOTAL 6    /* the sum of the six */
 #define TDX_STREAMNET_PHASES 7
 void tdx_streamnet_links_copy(const tdx_streamnet_links* links, int64_t* tree, double* coord, double* phase_ms);
 void tdx_streamnet_links_free(tdx_streamnet_links* links);
+/* The device builder's own record: 1 and the values when the links of the handle were built on the device, 0 (nothing written) otherwise.  ms
+ * [TDX_STREAMNET_DLINK_PHASES]: wall milliseconds of its sub-phases, each ended with the stream drained; the pointer-jumping rounds along the cells with
+ * one inflow; the rounds of the level pass over the link tree; the scratch bytes taken beside the columns, the coord rows included.  Any may be NULL. */
+#define TDX_STREAMNET_DLINK_CLASSIFY 0   /* outlets onto the cells, inflow table, classes, node numbers */
+#define TDX_STREAMNET_DLINK_JUMP 1       /* pointer jumping along the cells with one inflow */
+#define TDX_STREAMNET_DLINK_LEVEL 2      /* order, magnitude, h and root by levels over the link tree */
+#define TDX_STREAMNET_DLINK_NUMBER 3     /* the sort by (h, root) and the scan: link numbers */
+#define TDX_STREAMNET_DLINK_LINKS 4      /* the link table, labels and orders of the stream cells */
+#define TDX_STREAMNET_DLINK_ROWS 5       /* the tree rows and the coord rows */
+#define TDX_STREAMNET_DLINK_DOWNLOAD 6   /* tree and coord to the host */
+#define TDX_STREAMNET_DLINK_PHASES 7
+int tdx_streamnet_links_device_phases(const tdx_streamnet_links* links, double* ms, int64_t* jump_rounds, int64_t* level_rounds, int64_t* workspace_bytes);
 /* Row strips (arrays of ny_local + 2 rows; dxc / dyc of those rows; row0: the global row of the strip's first owned row).  The work is cut where the
  * data has to meet: every strip compacts the stream cells of its OWNED rows, the caller puts the parts together in strip order - that is the row-major
  * order of the whole raster - and builds the links once, and every strip gets its share of the labels back.  The result is byte for byte the
@@ -47,6 +71,9 @@ void tdx_streamnet_links_free(tdx_streamnet_links* links);
  *   tdx_streamnet_compact_strip   exchanges the halo rows of p and src (it writes them), runs the length sweep on the strip and returns the strip's part.
  *   tdx_streamnet_links_build     host code, no context: the parts of ALL strips in strip order (handles of this process) -> the links of the raster;
  *                                 outlets as for tdx_streamnet, with GLOBAL rows.
+ *   tdx_streamnet_links_build_gpu the same on the device of ctx: the parts are put together on the host, uploaded in strip order, and the links built
+ *                                 there; the labels and orders come down into the handle with the rows (a few bytes per stream cell), so that
+ *                                 tdx_streamnet_label_strip takes the handle unchanged on whichever context labels the strip.
  *   tdx_streamnet_label_strip     the strip's labels and orders (first_cell: the number of stream cells in the strips above it), the label sweep on the
  *                                 strip; d_ord / d_w of ny_local + 2 rows, the owned rows are the result.  p / src must still hold their halo rows. */
 typedef struct tdx_streamnet_compact tdx_streamnet_compact;
@@ -57,6 +84,9 @@ int64_t tdx_streamnet_compact_count(const tdx_streamnet_compact* part);
 void tdx_streamnet_compact_free(tdx_streamnet_compact* part);
 int tdx_streamnet_links_build(const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, double dxA, double dyA, const double* gt,
                               const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, tdx_streamnet_links** links);
+int tdx_streamnet_links_build_gpu(tdx_context* ctx, const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, double dxA, double dyA,
+                                  const double* gt, const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets,
+                                  tdx_streamnet_links** links);
 int tdx_streamnet_label_strip(tdx_context* ctx, const tdx_comm* comm, const int16_t* d_p, const int32_t* d_src, int64_t nx, int64_t ny_local, int16_t p_nodata,
                               int32_t src_nodata, const tdx_streamnet_compact* part, const tdx_streamnet_links* links, int64_t first_cell,
                               int single_watershed, int16_t* d_ord, int32_t* d_w, tdx_stats* stats);
@@ -86,5 +116,8 @@ int tdx_streamnet_net_write(const tdx_streamnet_links* links, int geographic, co
 int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfile, const char* ad8file, const char* elevfile, const char* treefile,
                        const char* coordfile, const char* outletsds, const char* lyrname, int uselayername, int lyrno, const char* wfile,
                        const char* streamnetsrc, const char* streamnetlyr, long useOutlets, long ordert, int verbose);
+/* Where tdx_tool_streamnet builds the links from now on: 0 the host (the default), 1 the device - with --gpus N rank 0 builds them on its device.  Both
+ * write the same bytes.  TDX_ERR_ARG for any other value. */
+int tdx_tool_set_streamnet_links(int where);
 
 #endif /* TAUDEM_AMD_STREAMNET_H */

@@ -3,7 +3,11 @@
 compaction, host link build, scatter, label sweep, total: tdx_streamnet's own clocks, each phase ended with the stream drained; mean and spread over the
 timed steps after a warm-up) and, from the same run, the times of d8hdisttostrm (same src) and gagewatershed (gauges on the largest stream ends) on the
 same p: the two new sweeps use their engine, so these are the yardstick.
-usage: python scripts/bench_streamnet.py [--size 16384] [--steps 3 (40 below 8192^2)] [--warmup 1] [--share 0.01] [--out profiles/streamnet_bench_<size>.json]"""
+--links both: the two link builders instead, alternating in one process on the same HBM-resident inputs (host, device, host, device, ...: one warm-up
+pair, then timed pairs): for either the phases and the wall time of the call, for the device builder its sub-phases, round counts, workspace and the
+bytes of coord that come down; ord, w, tree and coord of the two are compared once, and no record is written if they differ.  That record goes to
+profiles/streamnet_links_bench_<size>.json.
+usage: python scripts/bench_streamnet.py [--size 16384] [--steps 3 (40 below 8192^2)] [--warmup 1] [--share 0.01] [--links host|both] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,12 +19,14 @@ ap.add_argument("--size", type=int, default=16384)
 ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 3 from 8192^2 up, 40 below, so that the timed window is about a second)")
 ap.add_argument("--warmup", type=int, default=1)
 ap.add_argument("--share", type=float, default=0.01)
+ap.add_argument("--links", default="host", choices=("host", "both"))
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 n = a.size
 if a.steps is None:
     a.steps = 3 if n >= 8192 else 40
-out_path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"streamnet_bench_{n}.json")
+out_path = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                 f"streamnet_links_bench_{n}.json" if a.links == "both" else f"streamnet_bench_{n}.json")
 ctx = T.Context(0)
 dem = ctx.synth_dem(n, seed=1234)
 fel = ctx.pitremove(dem, -9999.0)
@@ -44,6 +50,53 @@ def spread(v):
     return {"mean_ms": float(v.mean()), "min_ms": float(v.min()), "max_ms": float(v.max())}
 
 
+def write(res):
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if a.links == "both":
+    runs, kept, same, shape = {"host": [], "device": []}, {}, True, {}
+    for i in range(a.warmup + a.steps):
+        for where in ("host", "device"):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ordg, w, tree, coord, ms = ctx.streamnet(p, src, fel, ad8, dx=30.0, dy=30.0, phases=True, links=where)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            sub = ms.pop("links_device", None)
+            rec = {"call_ms": (t1 - t0) * 1e3, "phases": ms, "links_device": sub}
+            shape = {"links": int(tree.shape[0]), "points": int(coord.shape[0]), "tree_bytes": int(tree.nbytes), "coord_bytes": int(coord.nbytes)}
+            if i == 0:   # the two builders' outputs, compared once
+                kept[where] = (ordg.cpu().numpy(), w.cpu().numpy(), tree, coord.view(np.uint64))
+            print(f"call {i} {where}: {rec['call_ms']:.1f} ms, phases {ms}, device builder {sub}", flush=True)
+            if i >= a.warmup:
+                runs[where].append(rec)
+            del ordg, w, tree, coord
+        if i == 0:
+            same = all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(kept["host"], kept["device"]))
+            kept = {}
+            if not same:
+                sys.exit("the two link builders gave different ord, w, tree or coord: no record written")
+
+    def path(recs):
+        out = {"call_wall": spread([r["call_ms"] for r in recs]), "phases": {k: spread([r["phases"][k] for r in recs]) for k in recs[0]["phases"]}}
+        sub = recs[0]["links_device"]
+        if sub:
+            out["links_device"] = {k: spread([r["links_device"][k] for r in recs]) for k in T._lib.STREAMNET_LINK_PHASES}
+            out.update(jump_rounds=sub["jump_rounds"], level_rounds=sub["level_rounds"], workspace_bytes=sub["workspace_bytes"])
+        return out
+
+    host, dev = path(runs["host"]), path(runs["device"])
+    write({"size": n, "cells": n * n, "threshold": thresh, "stream_share": share, "stream_cells": int(round(share * n * n)), **shape, "steps": a.steps, "warmup": a.warmup,
+           "order": "host, device alternating in one process", "same_ord_w_tree_coord": bool(same), "host": host, "device": dev,
+           "link_phase_host_over_device": host["phases"]["links"]["mean_ms"] / dev["phases"]["links"]["mean_ms"],
+           "call_host_over_device": host["call_wall"]["mean_ms"] / dev["call_wall"]["mean_ms"]})
+    sys.exit(0)
+
 phases, calls, dist_ms, gage_ms, links = [], [], [], [], 0
 for i in range(a.warmup + a.steps):
     torch.cuda.synchronize()
@@ -65,8 +118,4 @@ res = {"size": n, "cells": n * n, "threshold": thresh, "stream_share": share, "s
        "yardstick": {"d8hdisttostrm": spread(dist_ms), "gagewatershed": spread(gage_ms)},
        "length_sweep_over_d8hdisttostrm": float(np.mean([m["length"] for m in phases]) / np.mean(dist_ms)),
        "label_sweep_over_gagewatershed": float(np.mean([m["label"] for m in phases]) / np.mean(gage_ms))}
-os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-with open(out_path, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write(res)

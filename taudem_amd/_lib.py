@@ -283,6 +283,11 @@ _STREAMNET_SIGNATURES = {
     # &links, stats
     "tdx_streamnet": (C.c_int, _STREAMNET_HEAD),
     "tdx_streamnet_dev": (C.c_int, _STREAMNET_HEAD),
+    # the same with the links built on the device (streamnet_links_device.hip)
+    "tdx_streamnet_gpu_links": (C.c_int, _STREAMNET_HEAD),
+    "tdx_streamnet_gpu_links_dev": (C.c_int, _STREAMNET_HEAD),
+    # links, ms [STREAMNET_LINK_PHASES], jump_rounds, level_rounds, workspace_bytes -> 1 when the device built the links
+    "tdx_streamnet_links_device_phases": (C.c_int, [_P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "tdx_streamnet_links_count": (_I64, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "tdx_streamnet_links_copy": (None, [_P, _P, _P, _P]),
     "tdx_streamnet_links_free": (None, [_P]),
@@ -293,14 +298,19 @@ _STREAMNET_SIGNATURES = {
     # parts, n_parts, nx, ny, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, &links
     "tdx_streamnet_links_build": (C.c_int, [_P, _I64, _I64, _I64, _D, _D, _P, _P, _P, _P, _I64, C.POINTER(_P)]),
     # ctx, comm, p, src, nx, ny_local, p_nodata, src_nodata, part, links, first_cell, single_watershed, ord, w, stats
+    # ctx, then the arguments of tdx_streamnet_links_build
+    "tdx_streamnet_links_build_gpu": (C.c_int, [_P, _P, _I64, _I64, _I64, _D, _D, _P, _P, _P, _P, _I64, C.POINTER(_P)]),
     "tdx_streamnet_label_strip": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I16, C.c_int32, _P, _P, _I64, _INT, _P, _P, _P]),
     "tdx_streamnet_write_text": (C.c_int, [_P, C.c_char_p, C.c_char_p]),
     "tdx_streamnet_net_rows": (C.c_int, [_P, _P, _I64, _I64, C.c_int, _I64, _P, _P, _P, _P]),
     "tdx_streamnet_net_write": (C.c_int, [_P, C.c_int, C.c_char_p]),
     "tdx_tool_streamnet": (C.c_int, [C.c_char_p] * 9 + [C.c_int, C.c_int] + [C.c_char_p] * 3 + [C.c_long, C.c_long, C.c_int]),
+    "tdx_tool_set_streamnet_links": (C.c_int, [C.c_int]),
 }
 STREAMNET_SYMBOLS = tuple(_STREAMNET_SIGNATURES)
 STREAMNET_PHASES = ("setup", "length", "compact", "links", "scatter", "label", "total")
+STREAMNET_LINKS = ("host", "device")   # where the links are built: the value of tdx_tool_set_streamnet_links is the index
+STREAMNET_LINK_PHASES = ("classify", "jump", "level", "number", "links", "rows", "download")   # the device builder's sub-phases
 
 # name -> (restype, argtypes): the symbols include/taudem_amd_outlets.h declares, the fifth extension header
 # MoveOutletsToStrm: ctx, p, src, nx, ny, p_nodata, src_nodata, maxdist, outlet_x, outlet_y, n_outlets, out_x, out_y, dist_moved, stats

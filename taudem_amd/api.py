@@ -183,7 +183,7 @@ class _StreamNetStage:
     """Context.streamnet; its entry points are those of include/taudem_amd_streamnet.h."""
 
     def streamnet(self, p, src, fel, ad8, outlets=None, single_watershed=False, *, dx=1.0, dy=1.0, geotransform=None, nodata=int(P_NODATA),
-                  src_nodata=int(P_NODATA), out=None, phases=False, stats=False, net=None, geographic=False):
+                  src_nodata=int(P_NODATA), out=None, phases=False, stats=False, net=None, geographic=False, links="host"):
         """ord, w, tree, coord = streamnet(p, src, fel, ad8)  (src/streamnet.cpp:372): the stream network of the stream raster src on the D8 directions p.
         net=path also writes the stream network line layer (the reference's -net: a shapefile or GeoJSON by the extension, 17 fields per link) from the
         links once the call has returned them; geographic: the raster's flag, which decides how the layer's lengths are measured.
@@ -196,8 +196,13 @@ class _StreamNetStage:
         src int32, fel / ad8 float32 (read without a nodata test).  outlets: (columns, rows[, ids]) in file order: an outlet on a stream cell ends a
         link there.  geotransform: GDAL's six numbers of the raster file (default: left edge 0, top edge 0, cells of dx x dy of the middle row).
         tree and coord are numpy arrays on the host for either side; phases=True also returns, after coord, the wall milliseconds of the call's
-        phases as a dict (setup, length, compact, links, scatter, label, total).  out: (ord, w)."""
-        return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net, geographic), stats)
+        phases as a dict (setup, length, compact, links, scatter, label, total).  out: (ord, w).
+        links: "host" (the default) builds the links in a walk on one host core; "device" builds them on the GPU (tdx_streamnet_gpu_links: the same
+        bytes; the stream cells' columns, labels and orders never leave the device).  With phases=True the dict of a device build also holds
+        "links_device": the builder's sub-phases in milliseconds (classify, jump, level, number, links, rows, download), jump_rounds, level_rounds and
+        workspace_bytes."""
+        return _ret(_streamnet(_Call(self), p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net, geographic, links),
+                    stats)
 
 
 class _OutletToolsStage:
@@ -919,7 +924,9 @@ def _dropanalysis(f, ad8, p, fel, ssa, outlets, thresh_min, thresh_max, nthresh,
     return (thresh, n1, n2, sums, length, scal[0], text.value.decode(), scal[1] if found[0] else None) + extra + (st,)
 
 
-def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net=None, geographic=False):
+def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransform, nodata, src_nodata, out, phases, net=None, geographic=False, links="host"):
+    if links not in _lib.STREAMNET_LINKS:
+        raise ValueError(f"links: one of {_lib.STREAMNET_LINKS}, not {links!r}")
     pp = f.raster(p, np.int16, "p")
     ps = f.raster(src, np.int32, "src")
     pf = f.raster(fel, np.float32, "fel")
@@ -941,9 +948,9 @@ def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransf
     o_ord, o_w = out if out is not None else (None, None)
     ordg, po = f.out(o_ord, np.int16, "ord")
     w, pw = f.out(o_w, np.int32, "w")
-    links = C.c_void_p()
+    where, links = links, C.c_void_p()
     lib = f.ctx._lib
-    st = f.call("tdx_streamnet", pp, ps, pf, pa, f.nx, f.ny, int(nodata), int(src_nodata), pdx, pdy, dxa, dya, _v(g4), _v(ox) if ox.size else None,
+    st = f.call("tdx_streamnet" if where == "host" else "tdx_streamnet_gpu_links", pp, ps, pf, pa, f.nx, f.ny, int(nodata), int(src_nodata), pdx, pdy, dxa, dya, _v(g4), _v(ox) if ox.size else None,
                 _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), int(bool(single_watershed)), po, pw, C.byref(links))
     try:
         tree, coord, ms = _links_rows(lib, links, phases=True)
@@ -958,12 +965,26 @@ def _streamnet(f, p, src, fel, ad8, outlets, single_watershed, dx, dy, geotransf
 
 
 def _links_rows(lib, links, phases=False):
-    """(tree, coord[, phase dict]) of a tdx_streamnet_links handle."""
+    """(tree, coord[, phase dict]) of a tdx_streamnet_links handle; the dict of a device build holds the builder's own record as "links_device"."""
     npts = C.c_int64(0)
     nl = int(lib.tdx_streamnet_links_count(links, C.byref(npts), None))
     tree, coord, ms = np.empty((nl, 9), np.int64), np.empty((npts.value, 5), np.float64), np.zeros(len(_lib.STREAMNET_PHASES), np.float64)
     lib.tdx_streamnet_links_copy(links, _v(tree), _v(coord), _v(ms))
-    return (tree, coord, dict(zip(_lib.STREAMNET_PHASES, ms.tolist()))) if phases else (tree, coord)
+    if not phases:
+        return tree, coord
+    d = dict(zip(_lib.STREAMNET_PHASES, ms.tolist()))
+    sub = _link_phases(lib, links)
+    if sub is not None:
+        d["links_device"] = sub
+    return tree, coord, d
+
+
+def _link_phases(lib, links):
+    """The device link builder's record of a handle (tdx_streamnet_links_device_phases), None when the host built the links."""
+    sub, jr, lr, wb = np.zeros(len(_lib.STREAMNET_LINK_PHASES), np.float64), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    if not lib.tdx_streamnet_links_device_phases(links, _v(sub), C.byref(jr), C.byref(lr), C.byref(wb)):
+        return None
+    return dict(zip(_lib.STREAMNET_LINK_PHASES, sub.tolist()), jump_rounds=jr.value, level_rounds=lr.value, workspace_bytes=wb.value)
 
 
 def _streamnet_compact(f, p, src, fel, ad8, row0, dx, dy, nodata, src_nodata):
@@ -988,10 +1009,16 @@ def _streamnet_label(f, p, src, part, links, first_cell, single_watershed, nodat
 
 
 class StreamNetLinks:
-    """The links of a raster from the parts of ALL its strips in strip order (StripPipeline.streamnet_compact): host code, no device.  tree / coord as
-    Context.streamnet returns them; first_cell[k] is what strip k hands to StripPipeline.streamnet_label.  Owns the parts: close() frees them too."""
+    """The links of a raster from the parts of ALL its strips in strip order (StripPipeline.streamnet_compact): host code, no device - or with
+    links="device" and a Context as ctx, built on that context's device (tdx_streamnet_links_build_gpu: the same bytes; link_phases then holds the
+    builder's record).  tree / coord as Context.streamnet returns them; first_cell[k] is what strip k hands to StripPipeline.streamnet_label.  Owns the
+    parts: close() frees them too."""
 
-    def __init__(self, parts, nx, ny, dx, dy, geotransform=None, outlets=None):
+    def __init__(self, parts, nx, ny, dx, dy, geotransform=None, outlets=None, links="host", ctx=None):
+        if links not in _lib.STREAMNET_LINKS:
+            raise ValueError(f"links: one of {_lib.STREAMNET_LINKS}, not {links!r}")
+        if links == "device" and ctx is None:
+            raise ValueError('links="device" needs ctx, the Context whose device builds the links')
         self._lib = _lib.load()
         self.parts = list(parts)
         counts = [int(self._lib.tdx_streamnet_compact_count(p)) for p in self.parts]
@@ -1007,9 +1034,14 @@ class StreamNetLinks:
             ids = _flat(outlets[2], np.int32) if len(outlets) > 2 else np.arange(1, ox.size + 1, dtype=np.int32)
         arr = (C.c_void_p * len(self.parts))(*[p.value for p in self.parts])
         self.handle = C.c_void_p()
-        check(self._lib.tdx_streamnet_links_build(C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), dxa, dya, _v(g4), _v(ox) if ox.size else None,
-                                                  _v(oy) if ox.size else None, _v(ids) if ox.size else None, int(ox.size), C.byref(self.handle)))
+        tail = (C.cast(arr, C.c_void_p), len(self.parts), int(nx), int(ny), dxa, dya, _v(g4), _v(ox) if ox.size else None, _v(oy) if ox.size else None,
+                _v(ids) if ox.size else None, int(ox.size), C.byref(self.handle))
+        if links == "device":
+            check(self._lib.tdx_streamnet_links_build_gpu(ctx._h, *tail), ctx._h)
+        else:
+            check(self._lib.tdx_streamnet_links_build(*tail))
         self.tree, self.coord = _links_rows(self._lib, self.handle)
+        self.link_phases = _link_phases(self._lib, self.handle)
 
     def write_net(self, path, geographic=False):
         """The stream network line layer of the links (tdx_streamnet_net_write): the file Context.streamnet(..., net=path) writes."""

@@ -79,6 +79,7 @@ using toolstrips::RankJob;
 
 int g_tool_device = -1;
 int g_tool_gpus = -1;
+int g_tool_streamnet_links = 0;   // tdx_tool_set_streamnet_links: 0 the host builds the links of streamnet, 1 the device
 int g_tool_polygon_rings = 0;   // tdx_tool_set_polygon_rings: 0 the host closes the rings of watershedgridtoshp, 1 the device
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -362,6 +363,11 @@ extern "C" {
 
 int tdx_tool_set_device(int device) { g_tool_device = device; return TDX_OK; }
 int tdx_tool_set_gpus(int ngpus) { g_tool_gpus = ngpus; return TDX_OK; }
+int tdx_tool_set_streamnet_links(int where) {
+    if (where != 0 && where != 1) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_set_streamnet_links: 0 (host) or 1 (device)");
+    g_tool_streamnet_links = where;
+    return TDX_OK;
+}
 int tdx_tool_set_polygon_rings(int where) {
     if (where != 0 && where != 1) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_tool_set_polygon_rings: 0 (host) or 1 (device)");
     g_tool_polygon_rings = where;
@@ -929,7 +935,8 @@ int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfi
     const int32_t src_nd = (int32_t)(int16_t)src.info.nodata;
     const int sw = ordert == 0;
     tdx_streamnet_links* links = nullptr;
-    // --gpus N: every rank compacts its strip, the ranks meet, rank 0 builds the links of the whole raster on the host, they meet again, every rank labels
+    // --gpus N: every rank compacts its strip, the ranks meet, rank 0 builds the links of the whole raster (on the host, or after
+    // tdx_tool_set_streamnet_links(1) on its device), they meet again, every rank labels
     // its strip.  A rank that fails still comes to both meetings, so that nobody waits there for it.
     const int nranks = int(std::min<int64_t>(tool_gpus(), ny));
     std::vector<tdx_streamnet_compact*> parts(size_t(std::max(nranks, 1)), nullptr);
@@ -943,9 +950,10 @@ int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfi
     } meet;
     meet.n = std::max(nranks, 1);
     std::atomic<int> failed{0};
+    const bool device_links = g_tool_streamnet_links == 1;
     const bool ok = t.compute(
         [&](tdx_context* c, tdx_stats* s) {
-            return tdx_streamnet(c, p.s.data(), src32.data(), fel.f.data(), ad8.f.data(), nx, ny, p_nd, src_nd, src.info.dxc.data(), src.info.dyc.data(), src.info.dxA(),
+            return (device_links ? tdx_streamnet_gpu_links : tdx_streamnet)(c, p.s.data(), src32.data(), fel.f.data(), ad8.f.data(), nx, ny, p_nd, src_nd, src.info.dxc.data(), src.info.dyc.data(), src.info.dxA(),
                                  src.info.dyA(), gt, nout ? o.xs() : nullptr, nout ? o.ys() : nullptr, nout ? o.ids.data() : nullptr, nout, sw, ord.data(), w.data(), &links, s);
         },
         [&](RankJob& j, tdx_stats* s) {
@@ -959,8 +967,10 @@ int tdx_tool_streamnet(const char* pfile, const char* srcfile, const char* ordfi
             if (e != TDX_OK) failed = e;
             meet.wait();
             if (failed == 0 && j.rank == 0) {
-                const int eb = tdx_streamnet_links_build(parts.data(), j.size, nx, ny, src.info.dxA(), src.info.dyA(), gt, nout ? o.xs() : nullptr, nout ? o.ys() : nullptr,
-                                                         nout ? o.ids.data() : nullptr, nout, &links);
+                const int eb = device_links ? tdx_streamnet_links_build_gpu(j.ctx, parts.data(), j.size, nx, ny, src.info.dxA(), src.info.dyA(), gt, nout ? o.xs() : nullptr,
+                                                                            nout ? o.ys() : nullptr, nout ? o.ids.data() : nullptr, nout, &links)
+                                            : tdx_streamnet_links_build(parts.data(), j.size, nx, ny, src.info.dxA(), src.info.dyA(), gt, nout ? o.xs() : nullptr,
+                                                                        nout ? o.ys() : nullptr, nout ? o.ids.data() : nullptr, nout, &links);
                 if (eb != TDX_OK) failed = eb;
             }
             meet.wait();

@@ -13,7 +13,9 @@
 //                              receiver has src >= 1" of the reference's seeds is simply "the receiver's record is not pending".
 // Between them the stream cells are compacted in row-major order (a block scan and a scan of the block totals; a rank grid and one gather give each cell
 // the compact rank of its receiver), the host builds the links over the compact arrays (streamnet_links.cpp: the reference's FIFO and its link numbers
-// are sequential by definition, and touch ~1 % of the cells), and the per-cell labels and orders are scattered back.
+// are sequential by definition, and touch ~1 % of the cells), and the per-cell labels and orders are scattered back.  That is the default.  The
+// _gpu_links entry points build the links on the device instead (streamnet_links_device.hip: the queue's order has a closed form): the compact columns
+// stay where gather_kernel left them, the labels and orders are scattered from where the builder wrote them, and only the tree and coord rows come down.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -24,11 +26,14 @@
 #include "d8_sweep.hpp"
 #include "device_common.hpp"
 #include "streamnet_links.hpp"
+#include "streamnet_links_device.hpp"
 
 struct tdx_streamnet_links {
     streamnet::Links links;
     int64_t stream_cells = 0;
     double phase_ms[TDX_STREAMNET_PHASES] = {0, 0, 0, 0, 0, 0, 0};
+    bool device_built = false;             // the links came from streamnet_links_device.hip
+    streamnet::DeviceLinkStats dstats;     // its sub-phases, rounds and workspace (tdx_streamnet_links_device_phases)
 };
 
 // the stream cells of one strip's owned rows (tdx_streamnet_compact_strip), in row-major order
@@ -260,7 +265,8 @@ struct PhaseClock {
 
 int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int nx, int ny, int16_t p_nodata,
                    int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x, const int32_t* outlet_y,
-                   const int32_t* outlet_id, int64_t nout, int sw, int16_t* d_ord, int32_t* d_w, tdx_streamnet_links* res, tdx_stats* stats) {
+                   const int32_t* outlet_id, int64_t nout, int sw, int16_t* d_ord, int32_t* d_w, tdx_streamnet_links* res, tdx_stats* stats,
+                   bool device_links) {
     TDX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const Strip st = strip_single(nx, ny);
@@ -328,17 +334,20 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
     int16_t* cp = reinterpret_cast<int16_t*>(buf + ncp * 24);
     int16_t* corder = reinterpret_cast<int16_t*>(buf + ncp * 26);
     uint8_t* cflag = buf + ncp * 28;
-    std::vector<uint32_t> h_idx(nc);
-    std::vector<int16_t> h_p(nc);
-    std::vector<float> h_fel(nc), h_ad8(nc), h_len(nc);
-    std::vector<int32_t> h_recv(nc);
-    std::vector<uint8_t> h_flag(nc);
+    const unsigned nh = device_links ? 0u : nc;   // the host builder's copies of the columns
+    std::vector<uint32_t> h_idx(nh);
+    std::vector<int16_t> h_p(nh);
+    std::vector<float> h_fel(nh), h_ad8(nh), h_len(nh);
+    std::vector<int32_t> h_recv(nh);
+    std::vector<uint8_t> h_flag(nh);
     {
         TdxSpan sp(ctx, TDX_K_MISC);
         hipLaunchKernelGGL(rank_kernel, dim3(nblocks), dim3(256), 0, s, d_p, d_src, n, p_nodata, src_nodata, block_off, rank, cidx, 0u);
         if (nc) {
             hipLaunchKernelGGL(gather_kernel, dim3(tdx_blocks_for(nc, 256)), dim3(256), 0, s, cidx, nc, d_p, d_src, d_fel, d_ad8, len, rank, nx, ny, src_nodata, cp, cfel,
                                cad8, clen, crecv, cflag);
+        }
+        if (nh) {
             TDX_HIP_CHECK(ctx, hipMemcpyAsync(h_idx.data(), cidx, size_t(nc) * 4, hipMemcpyDeviceToHost, s));
             TDX_HIP_CHECK(ctx, hipMemcpyAsync(h_p.data(), cp, size_t(nc) * 2, hipMemcpyDeviceToHost, s));
             TDX_HIP_CHECK(ctx, hipMemcpyAsync(h_fel.data(), cfel, size_t(nc) * 4, hipMemcpyDeviceToHost, s));
@@ -350,7 +359,17 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
         if (stats) stats->launches[TDX_K_MISC] += 4;
     }
     if ((rc = clock.lap(&res->phase_ms[TDX_STREAMNET_COMPACT])) != TDX_OK) return rc;
-    {   // ---- links, on the host
+    if (device_links) {   // ---- links, on the device: label and order are written where the scatter reads them
+        streamnet::DeviceColumns DC;
+        DC.n = nc; DC.cidx = cidx; DC.p = cp; DC.fel = cfel; DC.ad8 = cad8; DC.len = clen; DC.recv = crecv; DC.flags = cflag;
+        std::string why;
+        rc = streamnet::build_links_device(ctx, DC, outlet_x, outlet_y, outlet_id, nout, nx, ny, dxA, dyA, gt, clabel, corder, res->links, res->dstats, why);
+        if (rc != TDX_OK) return why.empty() ? rc : tdx_fail(ctx, rc, "tdx_streamnet_gpu_links: " + why);
+        res->device_built = true;
+        res->stream_cells = nc;
+        info = static_cast<uint32_t*>(ctx->scratch(TDX_S_A, n * 4));   // (the builder's workspace took the slot)
+        if (!info) return TDX_ERR_NOMEM;
+    } else {   // ---- links, on the host
         std::vector<int64_t> idx(h_idx.begin(), h_idx.end());
         std::vector<int32_t> outlet(nc, streamnet::LINK_NONE);
         for (int64_t o = 0; o < nout; o++) {   // :514-521: outlets off the raster are dropped, the last one on a cell wins; off the stream they change nothing
@@ -371,8 +390,10 @@ int streamnet_impl(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, c
         TDX_HIP_CHECK(ctx, hipMemsetAsync(d_ord, 0, n * 2, s));   // the order grid is 0 off the stream, nodata cells included (:1461-1468)
         hipLaunchKernelGGL(label_setup_kernel, grid2, dim3(256), 0, s, d_p, d_src, nx, ny, p_nodata, src_nodata, sw, info, d_w);
         if (nc) {
-            TDX_HIP_CHECK(ctx, hipMemcpyAsync(clabel, res->links.label.data(), size_t(nc) * 4, hipMemcpyHostToDevice, s));
-            TDX_HIP_CHECK(ctx, hipMemcpyAsync(corder, res->links.order.data(), size_t(nc) * 2, hipMemcpyHostToDevice, s));
+            if (!device_links) {
+                TDX_HIP_CHECK(ctx, hipMemcpyAsync(clabel, res->links.label.data(), size_t(nc) * 4, hipMemcpyHostToDevice, s));
+                TDX_HIP_CHECK(ctx, hipMemcpyAsync(corder, res->links.order.data(), size_t(nc) * 2, hipMemcpyHostToDevice, s));
+            }
             hipLaunchKernelGGL(scatter_kernel, dim3(tdx_blocks_for(nc, 256)), dim3(256), 0, s, cidx, nc, clabel, corder, sw, d_w, d_ord);
         }
         if (stats) stats->launches[TDX_K_STENCIL] += 2;
@@ -563,26 +584,25 @@ int streamnet_check(tdx_context* ctx, const void* p, const void* src, const void
 
 }  // namespace
 
-extern "C" int tdx_streamnet_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny,
-                                 int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt,
-                                 const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed,
-                                 int16_t* d_ord, int32_t* d_w, tdx_streamnet_links** links, tdx_stats* stats) {
-    if (int rc = streamnet_check(ctx, d_p, d_src, d_fel, d_ad8, nx, ny, dxc, dyc, gt, outlet_x, outlet_y, n_outlets, d_ord, d_w, links, "tdx_streamnet_dev: bad argument"))
-        return rc;
+namespace {
+int streamnet_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny, int16_t p_nodata,
+                  int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x, const int32_t* outlet_y,
+                  const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* d_ord, int32_t* d_w, tdx_streamnet_links** links, tdx_stats* stats,
+                  bool device_links, const char* who) {
+    if (int rc = streamnet_check(ctx, d_p, d_src, d_fel, d_ad8, nx, ny, dxc, dyc, gt, outlet_x, outlet_y, n_outlets, d_ord, d_w, links, who)) return rc;
     *links = nullptr;
     tdx_streamnet_links* res = new tdx_streamnet_links;
     const int rc = streamnet_impl(ctx, d_p, d_src, d_fel, d_ad8, int(nx), int(ny), p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets,
-                                  single_watershed != 0, d_ord, d_w, res, stats);
+                                  single_watershed != 0, d_ord, d_w, res, stats, device_links);
     if (rc != TDX_OK) { delete res; return rc; }   // (a call that had begun was aborted where it failed)
     *links = res;
     return TDX_OK;
 }
-
-extern "C" int tdx_streamnet(tdx_context* ctx, const int16_t* p, const int32_t* src, const float* fel, const float* ad8, int64_t nx, int64_t ny, int16_t p_nodata,
-                             int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
-                             const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w,
-                             tdx_streamnet_links** links, tdx_stats* stats) {
-    if (int rc = streamnet_check(ctx, p, src, fel, ad8, nx, ny, dxc, dyc, gt, outlet_x, outlet_y, n_outlets, ord, w, links, "tdx_streamnet: bad argument")) return rc;
+int streamnet_host(tdx_context* ctx, const int16_t* p, const int32_t* src, const float* fel, const float* ad8, int64_t nx, int64_t ny, int16_t p_nodata, int32_t src_nodata,
+                   const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x, const int32_t* outlet_y,
+                   const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w, tdx_streamnet_links** links, tdx_stats* stats,
+                   bool device_links, const char* who) {
+    if (int rc = streamnet_check(ctx, p, src, fel, ad8, nx, ny, dxc, dyc, gt, outlet_x, outlet_y, n_outlets, ord, w, links, who)) return rc;
     HostCall h(ctx, nx, ny);
     int16_t* d_p = h.in(TDX_S_IO0, p);
     int32_t* d_s = h.in(TDX_S_IO1, src);
@@ -591,10 +611,50 @@ extern "C" int tdx_streamnet(tdx_context* ctx, const int16_t* p, const int32_t* 
     int32_t* d_w = h.out(TDX_S_IO4, w);
     int16_t* d_o = h.out(TDX_S_E, ord);
     if (h.error) return h.error;
-    const int rc = h.finish(tdx_streamnet_dev(ctx, d_p, d_s, d_f, d_a, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets,
-                                              single_watershed, d_o, d_w, links, stats));
+    const int rc = h.finish(streamnet_dev(ctx, d_p, d_s, d_f, d_a, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets,
+                                          single_watershed, d_o, d_w, links, stats, device_links, who));
     if (rc != TDX_OK && *links) { delete *links; *links = nullptr; }
     return rc;
+}
+}  // namespace
+
+extern "C" int tdx_streamnet_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny,
+    int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
+    const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* d_ord, int32_t* d_w, tdx_streamnet_links** links,
+    tdx_stats* stats) {
+    return streamnet_dev(ctx, d_p, d_src, d_fel, d_ad8, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, single_watershed, d_ord, d_w,
+                         links, stats, false, "tdx_streamnet_dev: bad argument");
+}
+extern "C" int tdx_streamnet(tdx_context* ctx, const int16_t* p, const int32_t* src, const float* fel, const float* ad8, int64_t nx, int64_t ny,
+    int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
+    const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w, tdx_streamnet_links** links,
+    tdx_stats* stats) {
+    return streamnet_host(ctx, p, src, fel, ad8, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, single_watershed, ord, w, links,
+                          stats, false, "tdx_streamnet: bad argument");
+}
+// the same calls with the links built on the device (streamnet_links_device.hip)
+extern "C" int tdx_streamnet_gpu_links_dev(tdx_context* ctx, const int16_t* d_p, const int32_t* d_src, const float* d_fel, const float* d_ad8, int64_t nx, int64_t ny,
+    int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
+    const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* d_ord, int32_t* d_w, tdx_streamnet_links** links,
+    tdx_stats* stats) {
+    return streamnet_dev(ctx, d_p, d_src, d_fel, d_ad8, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, single_watershed, d_ord, d_w,
+                         links, stats, true, "tdx_streamnet_gpu_links_dev: bad argument");
+}
+extern "C" int tdx_streamnet_gpu_links(tdx_context* ctx, const int16_t* p, const int32_t* src, const float* fel, const float* ad8, int64_t nx, int64_t ny,
+    int16_t p_nodata, int32_t src_nodata, const double* dxc, const double* dyc, double dxA, double dyA, const double* gt, const int32_t* outlet_x,
+    const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, int single_watershed, int16_t* ord, int32_t* w, tdx_streamnet_links** links,
+    tdx_stats* stats) {
+    return streamnet_host(ctx, p, src, fel, ad8, nx, ny, p_nodata, src_nodata, dxc, dyc, dxA, dyA, gt, outlet_x, outlet_y, outlet_id, n_outlets, single_watershed, ord, w, links,
+                          stats, true, "tdx_streamnet_gpu_links: bad argument");
+}
+extern "C" int tdx_streamnet_links_device_phases(const tdx_streamnet_links* links, double* ms, int64_t* jump_rounds, int64_t* level_rounds, int64_t* workspace_bytes) {
+    if (!links || !links->device_built) return 0;
+    static_assert(int(streamnet::DLINK_PHASES) == TDX_STREAMNET_DLINK_PHASES, "the header's count of sub-phases");
+    if (ms) memcpy(ms, links->dstats.ms, sizeof links->dstats.ms);
+    if (jump_rounds) *jump_rounds = links->dstats.jump_rounds;
+    if (level_rounds) *level_rounds = links->dstats.level_rounds;
+    if (workspace_bytes) *workspace_bytes = links->dstats.workspace_bytes;
+    return 1;
 }
 
 extern "C" int64_t tdx_streamnet_links_count(const tdx_streamnet_links* links, int64_t* n_points, int64_t* stream_cells) {
@@ -649,43 +709,115 @@ extern "C" int tdx_streamnet_compact_strip(tdx_context* ctx, const tdx_comm* com
 extern "C" int64_t tdx_streamnet_compact_count(const tdx_streamnet_compact* part) { return part ? int64_t(part->cidx.size()) : 0; }
 extern "C" void tdx_streamnet_compact_free(tdx_streamnet_compact* part) { delete part; }
 
-extern "C" int tdx_streamnet_links_build(const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, double dxA, double dyA, const double* gt,
-                                         const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, tdx_streamnet_links** links) {
+namespace {
+// the parts of all strips put together in strip order: local ranks to global ones
+struct MergedParts {
+    std::vector<int64_t> idx;
+    std::vector<int16_t> p;
+    std::vector<float> fel, ad8, len;
+    std::vector<int32_t> recv;
+    std::vector<uint8_t> flags;
+};
+int merge_parts(const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, const double* gt, const int32_t* outlet_x, const int32_t* outlet_y,
+                int64_t n_outlets, tdx_streamnet_links** links, const std::string& who, MergedParts& M) {
     if (!parts || n_parts <= 0 || nx <= 0 || ny <= 0 || !gt || !links || n_outlets < 0 || (n_outlets > 0 && (!outlet_x || !outlet_y)))
-        return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_streamnet_links_build: bad argument");
+        return tdx_fail(nullptr, TDX_ERR_ARG, who + ": bad argument");
     std::vector<int64_t> offset(size_t(n_parts) + 1, 0);
     for (int64_t k = 0; k < n_parts; k++) {
-        if (!parts[k] || parts[k]->nx != nx) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_streamnet_links_build: bad argument");
+        if (!parts[k] || parts[k]->nx != nx) return tdx_fail(nullptr, TDX_ERR_ARG, who + ": bad argument");
         offset[size_t(k) + 1] = offset[size_t(k)] + int64_t(parts[k]->cidx.size());
     }
     const size_t nc = size_t(offset.back());
-    if (nc > 0x7ffffff0ull) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_streamnet_links_build: more than 2^31 stream cells");
-    std::vector<int64_t> idx(nc);
-    std::vector<int16_t> p(nc);
-    std::vector<float> fel(nc), ad8(nc), len(nc);
-    std::vector<int32_t> recv(nc), outlet(nc, streamnet::LINK_NONE);
-    std::vector<uint8_t> flags(nc);
+    if (nc > 0x7ffffff0ull) return tdx_fail(nullptr, TDX_ERR_ARG, who + ": more than 2^31 stream cells");
+    M.idx.resize(nc); M.p.resize(nc); M.fel.resize(nc); M.ad8.resize(nc); M.len.resize(nc); M.recv.resize(nc); M.flags.resize(nc);
     for (int64_t k = 0; k < n_parts; k++) {
         const tdx_streamnet_compact& P = *parts[k];
         for (size_t i = 0, o = size_t(offset[size_t(k)]); i < P.cidx.size(); i++, o++) {
-            idx[o] = int64_t(P.cidx[i]) + P.row_shift * nx;
-            p[o] = P.p[i]; fel[o] = P.fel[i]; ad8[o] = P.ad8[i]; len[o] = P.len[i]; flags[o] = P.flags[i];
+            M.idx[o] = int64_t(P.cidx[i]) + P.row_shift * nx;
+            M.p[o] = P.p[i]; M.fel[o] = P.fel[i]; M.ad8[o] = P.ad8[i]; M.len[o] = P.len[i]; M.flags[o] = P.flags[i];
             const int64_t owner = k + P.recv_strip[i];
-            recv[o] = (P.recv[i] < 0 || owner < 0 || owner >= n_parts) ? -1 : int32_t(offset[size_t(owner)] + P.recv[i]);
+            M.recv[o] = (P.recv[i] < 0 || owner < 0 || owner >= n_parts) ? -1 : int32_t(offset[size_t(owner)] + P.recv[i]);
         }
     }
+    return TDX_OK;
+}
+}  // namespace
+
+extern "C" int tdx_streamnet_links_build(const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, double dxA, double dyA, const double* gt,
+                                         const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets, tdx_streamnet_links** links) {
+    MergedParts M;
+    if (int rc = merge_parts(parts, n_parts, nx, ny, gt, outlet_x, outlet_y, n_outlets, links, "tdx_streamnet_links_build", M)) return rc;
+    const size_t nc = M.idx.size();
+    std::vector<int32_t> outlet(nc, streamnet::LINK_NONE);
     for (int64_t o = 0; o < n_outlets; o++) {
         if (outlet_x[o] < 0 || outlet_x[o] >= nx || outlet_y[o] < 0 || outlet_y[o] >= ny) continue;
         const int64_t c = int64_t(outlet_y[o]) * nx + outlet_x[o];
-        const auto it = std::lower_bound(idx.begin(), idx.end(), c);
-        if (it != idx.end() && *it == c) outlet[size_t(it - idx.begin())] = outlet_id ? outlet_id[o] : int32_t(o + 1);
+        const auto it = std::lower_bound(M.idx.begin(), M.idx.end(), c);
+        if (it != M.idx.end() && *it == c) outlet[size_t(it - M.idx.begin())] = outlet_id ? outlet_id[o] : int32_t(o + 1);
     }
     streamnet::Compact C;
-    C.n = int64_t(nc); C.idx = idx.data(); C.p = p.data(); C.fel = fel.data(); C.ad8 = ad8.data(); C.len = len.data(); C.outlet = outlet.data(); C.recv = recv.data();
-    C.flags = flags.data();
+    C.n = int64_t(nc); C.idx = M.idx.data(); C.p = M.p.data(); C.fel = M.fel.data(); C.ad8 = M.ad8.data(); C.len = M.len.data(); C.outlet = outlet.data();
+    C.recv = M.recv.data(); C.flags = M.flags.data();
     tdx_streamnet_links* res = new tdx_streamnet_links;
     streamnet::build_links(C, nx, dxA, dyA, gt, res->links);
     res->stream_cells = int64_t(nc);
+    *links = res;
+    return TDX_OK;
+}
+
+// The same on the device of ctx: the merged columns are uploaded, the links built there, and label / order come down into the handle with the rows, so
+// that tdx_streamnet_label_strip takes the handle unchanged whichever context labels the strip.
+extern "C" int tdx_streamnet_links_build_gpu(tdx_context* ctx, const tdx_streamnet_compact* const* parts, int64_t n_parts, int64_t nx, int64_t ny, double dxA, double dyA,
+                                             const double* gt, const int32_t* outlet_x, const int32_t* outlet_y, const int32_t* outlet_id, int64_t n_outlets,
+                                             tdx_streamnet_links** links) {
+    if (!ctx) return tdx_fail(nullptr, TDX_ERR_ARG, "tdx_streamnet_links_build_gpu: bad argument");
+    MergedParts M;
+    if (int rc = merge_parts(parts, n_parts, nx, ny, gt, outlet_x, outlet_y, n_outlets, links, "tdx_streamnet_links_build_gpu", M)) return rc;
+    *links = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nc = M.idx.size(), ncp = (nc + 3) & ~size_t(3);
+    TDX_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // idx (i64), fel, ad8, len (f32), recv, label (i32), p, order (i16), flags (u8)
+    uint8_t* buf = static_cast<uint8_t*>(ctx->scratch(TDX_S_H, ncp * (8 + 5 * 4 + 2 * 2 + 1) + 64));
+    if (!buf) return tdx_fail(ctx, TDX_ERR_NOMEM, "tdx_streamnet_links_build_gpu: out of device memory");
+    int64_t* d_idx = reinterpret_cast<int64_t*>(buf);
+    float* d_fel = reinterpret_cast<float*>(buf + ncp * 8);
+    float* d_ad8 = reinterpret_cast<float*>(buf + ncp * 12);
+    float* d_len = reinterpret_cast<float*>(buf + ncp * 16);
+    int32_t* d_recv = reinterpret_cast<int32_t*>(buf + ncp * 20);
+    int32_t* d_label = reinterpret_cast<int32_t*>(buf + ncp * 24);
+    int16_t* d_p = reinterpret_cast<int16_t*>(buf + ncp * 28);
+    int16_t* d_order = reinterpret_cast<int16_t*>(buf + ncp * 30);
+    uint8_t* d_flags = buf + ncp * 32;
+    if (nc) {
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, M.idx.data(), nc * 8, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_fel, M.fel.data(), nc * 4, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_ad8, M.ad8.data(), nc * 4, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_len, M.len.data(), nc * 4, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_recv, M.recv.data(), nc * 4, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_p, M.p.data(), nc * 2, hipMemcpyHostToDevice, s));
+        TDX_HIP_CHECK(ctx, hipMemcpyAsync(d_flags, M.flags.data(), nc, hipMemcpyHostToDevice, s));
+    }
+    tdx_streamnet_links* res = new tdx_streamnet_links;
+    streamnet::DeviceColumns DC;
+    DC.n = int64_t(nc); DC.idx64 = d_idx; DC.p = d_p; DC.fel = d_fel; DC.ad8 = d_ad8; DC.len = d_len; DC.recv = d_recv; DC.flags = d_flags;
+    std::string why;
+    int rc = streamnet::build_links_device(ctx, DC, outlet_x, outlet_y, outlet_id, n_outlets, nx, ny, dxA, dyA, gt, d_label, d_order, res->links, res->dstats, why);
+    if (rc == TDX_OK) {
+        res->links.label.resize(nc);
+        res->links.order.resize(nc);
+        if (nc) {
+            const hipError_t e1 = hipMemcpyAsync(res->links.label.data(), d_label, nc * 4, hipMemcpyDeviceToHost, s);
+            const hipError_t e2 = hipMemcpyAsync(res->links.order.data(), d_order, nc * 2, hipMemcpyDeviceToHost, s);
+            const hipError_t e3 = hipStreamSynchronize(s);
+            if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { rc = TDX_ERR_HIP; why = "the labels did not come down"; }
+        }
+    }
+    if (rc != TDX_OK) { delete res; return why.empty() ? rc : tdx_fail(ctx, rc, "tdx_streamnet_links_build_gpu: " + why); }
+    res->device_built = true;
+    res->stream_cells = int64_t(nc);
+    res->phase_ms[TDX_STREAMNET_LINKS] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *links = res;
     return TDX_OK;
 }

@@ -1,7 +1,8 @@
-// streamnet -fel fel -p p -ad8 ad8 -src src -ord ord -tree tree -coord coord -w w [-o outlets] [-lyrname n] [-lyrno i] [-sw] [-v]
+// streamnet -fel fel -p p -ad8 ad8 -src src -ord ord -tree tree -coord coord -w w [-o outlets] [-lyrname n] [-lyrno i] [-sw] [-v] [-links host|device]
 // (flag surface of src/streamnetmn.cpp:51-270), or streamnet <basefilename>.
 // -net / -netlyr are recognised and refused before anything runs: the stream network layer is not written (every one of its fields follows from the
-// tree and coord files).  The simple form writes the other four outputs and says so.
+// tree and coord files).  The simple form writes the other four outputs and says so.  -links says where the links are built (host: the default);
+// any other word ends the run with status 2 before anything is read.  Both write the same bytes.
 #include "cli_common.hpp"
 
 static void usage(const char* prog) {
@@ -25,7 +26,7 @@ static void usage(const char* prog) {
 
 int main(int argc, char** argv) {
     cli::take_gpus(argc, argv);
-    std::string pfile, srcfile, ordfile, ad8file, elevfile, wfile, outletsds, lyrname, netfile, netlyr, treefile, coordfile;
+    std::string pfile, srcfile, ordfile, ad8file, elevfile, wfile, outletsds, lyrname, netfile, netlyr, treefile, coordfile, linkswhere = "host";
     int uselayername = 0, lyrno = 0, verbose = 0;
     long ordert = 1, useoutlets = 0;
     if (argc < 2) {
@@ -48,6 +49,7 @@ int main(int argc, char** argv) {
         else if (a.is("-w")) { if (!a.value(wfile)) usage(argv[0]); }
         else if (a.is("-net")) { if (!a.value(netfile)) usage(argv[0]); }
         else if (a.is("-netlyr")) { if (!a.value(netlyr)) usage(argv[0]); }
+        else if (a.is("-links")) { if (!a.value(linkswhere)) usage(argv[0]); }
         else if (a.is("-sw")) { a.flag(); ordert = 0; }
         else if (a.is("-v")) { a.flag(); verbose = 1; }
         else usage(argv[0]);
@@ -57,6 +59,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "streamnet: -net / -netlyr are not supported: the stream network layer is not written; its fields follow from the -tree and -coord files\n");
         return 2;
     }
+    if (linkswhere != "host" && linkswhere != "device") {
+        fprintf(stderr, "streamnet: -links takes host or device, not %s\n", linkswhere.c_str());
+        return 2;
+    }
+    tdx_tool_set_streamnet_links(linkswhere == "device" ? 1 : 0);
     if (argc == 2) {
         const std::string base = argv[1];
         elevfile = cli::nameadd(base, "fel"); pfile = cli::nameadd(base, "p"); ad8file = cli::nameadd(base, "ad8"); srcfile = cli::nameadd(base, "src");

@@ -272,6 +272,13 @@ def netsetup(pfile, srcfile, ordfile, ad8file, elevfile, treefile, coordfile, ou
 streamnet = netsetup
 
 
+def set_streamnet_links(links="host"):
+    """Where netsetup builds the links from now on: "host" (the default) or "device" (tdx_tool_set_streamnet_links); both write the same bytes."""
+    if links not in _lib.STREAMNET_LINKS:
+        raise ValueError(f"links: one of {_lib.STREAMNET_LINKS}, not {links!r}")
+    return _lib.load().tdx_tool_set_streamnet_links(_lib.STREAMNET_LINKS.index(links))
+
+
 def outletstosrc(pfile, srcfile, outletsdatasrc, outletslayer="", uselyrname=0, lyrno=0, outletmoveddatasrc="", outletmovedlayer="", maxdist=50):
     """src/MoveOutletsToStrm.cpp:80 (MoveOutletsToStrm).  The moved outlets go to a shapefile (.shp) or GeoJSON (.json / .geojson) layer; any other
     output is refused before anything is read.  The layer arguments are accepted and ignored."""
